@@ -1,7 +1,12 @@
 #!/usr/bin/env python3
 """bench.py -- LQR problem-steps/s of the MI355X LQR step at BASELINE.json's headline workload.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--bounded] [--impl {0..5}] [--no-extra]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--bounded] [--impl {0..5}] [--dump-outputs DIR] [--full [--no-extra]]
+
+A plain run sets up, warms up, times the K steps and prints the line.  Everything else this script measures or checks (the
+oracle parity of the timed results, the re-timings `roofline.same_set` / `repeat_kernel_ms`, `extra`, `cpu_baseline`) runs
+only with --full.  --dump-outputs DIR writes the last timed step's results (new_x, new_u and the per-problem vectors) as
+DIR/<name>.npy; the inputs depend on the arguments only, so two builds can be compared output for output.
 
 Workload (configs[3] of BASELINE.json, the one `metric` is quoted on): synthetic random linear
 dynamics, n_state=12, n_ctrl=4, T=50, batch=4096 PER GPU, fp32, contiguous time-major tensors
@@ -1031,6 +1036,27 @@ def contract_line(out):
     return s
 
 
+DUMP_MAX_BYTES = 64 << 20
+DUMP_NAMES = ("new_x", "new_u", "costs", "old_costs", "full_du_norm", "alpha_du_norm", "alphas")
+
+
+def dump_outputs(r, d):
+    """--dump-outputs: what a caller of the timed step receives, DIR/<name>.npy.  Above DUMP_MAX_BYTES in all, a fixed seeded
+    sample of the problems (the same for every array, listed in problem_index.npy) is written instead of the whole batch."""
+    import numpy as np
+    arrs = {k: r[k].detach().cpu().numpy() for k in DUMP_NAMES}
+    arrs = {k: a if a.dtype in (np.float32, np.float64) else a.astype(np.float64) for k, a in arrs.items()}
+    B = int(arrs["new_x"].shape[1])
+    total = sum(a.nbytes for a in arrs.values())
+    if total > DUMP_MAX_BYTES:
+        idx = np.sort(np.random.default_rng(0).choice(B, size=max(1, B * DUMP_MAX_BYTES // (total + 8 * B)), replace=False))
+        arrs = {k: np.ascontiguousarray(np.take(a, idx, axis=1 if a.ndim == 3 else 0)) for k, a in arrs.items()}
+        arrs["problem_index"] = idx.astype(np.float64)
+    os.makedirs(d, exist_ok=True)
+    for k, a in arrs.items():
+        np.save(os.path.join(d, k + ".npy"), a)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -1041,8 +1067,12 @@ def main():
     ap.add_argument("--impl", type=int, default=0, help="0 auto, 1 generic, 2 fused MFMA, 3 DPP 4-problems-per-wave")
     ap.add_argument("--batch", type=int, default=B_PER_GPU)
     ap.add_argument("--seed", type=int, default=1000, help="seed of the synthetic problem (rank r uses seed + r)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-extra", action="store_true", help="skip the secondary rows (`extra`)")
+    ap.add_argument("--full", action="store_true",
+                    help="also the oracle parity of the timed results, the re-timings, the secondary rows and the CPU baseline")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the last timed step's outputs as DIR/<name>.npy (float32 / float64, at most 64 MB in all)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip `cpu_baseline`")
+    ap.add_argument("--no-extra", action="store_true", help="with --full: skip the secondary rows (`extra`)")
     ap.add_argument("--one-set", action="store_true", help="re-launch ONE problem set (rounds 1-4) instead of alternating between two")
     ap.add_argument("--verify-nominal", action="store_true",
                     help="do not vouch for the nominal: the kernel verifies at every timestep that current_x is the rollout "
@@ -1164,9 +1194,11 @@ def main():
         slots.gather()
     elapsed, kern_ms = finish_timing(t0, ev, args.steps, barrier)
     p = psets[(turn[0] - 1) % len(plans)]          # the set of the LAST timed launch: its results are what `r` holds and what is certified
+    if args.dump_outputs and rank == 0:
+        dump_outputs(r, args.dump_outputs)
     n_all = settle + args.warmup + args.steps
     same_set = None
-    if dist is None and len(plans) > 1:
+    if args.full and dist is None and len(plans) > 1:
         # the figure of rounds 1-4 beside it: the same number of launches on ONE set, back to back (outside the timed region)
         _w, ms_same, _r = timed(plans[0], args.steps, 0)
         same_set = {"kernel_ms": ms_same, "frac": algorithmic_bytes_per_problem(NS, NC, T_H) * B / (ms_same * 1e-3) / 1e9 / HBM_PEAK_GBS,
@@ -1178,7 +1210,7 @@ def main():
     # them; a box that stalled for milliseconds inside (seen once in ten runs: 0.79 ms per step where every other measure of the
     # run said 0.09) shows as `repeat_kernel_ms` far below `kernel_ms`
     repeat_ms = None
-    if dist is None:
+    if args.full and dist is None:
         _w, repeat_ms, _r = timed(step, args.steps, 0)
         r = plans[(turn[0] - 1) % len(plans)]() if len(plans) > 1 else step()
         p = psets[(turn[0] - 1) % len(plans)]
@@ -1212,16 +1244,18 @@ def main():
         plain = [torch.empty_like(slots.buf[rank]) for _ in range(world)]
         dist.all_gather(plain, slots.buf[rank].clone())
         arrived = arrived and all(bool(torch.equal(plain[q], slots.buf[q])) for q in range(world))
-        # + 16 problems of every rank's block through the oracle
-        try:
-            par_rank = parity_check(p, r, args.bounded, n=16, be=be)
-        except Exception as e:
-            par_rank = {"ok": False, "error": "%s: %s" % (type(e).__name__, e)}
-        okt = torch.tensor([1.0 if (par_rank["ok"] and arrived and ranks_seen == world) else 0.0], device=dev)
+        # + 16 problems of every rank's block through the oracle (--full)
+        par_rank = None
+        if args.full:
+            try:
+                par_rank = parity_check(p, r, args.bounded, n=16, be=be)
+            except Exception as e:
+                par_rank = {"ok": False, "error": "%s: %s" % (type(e).__name__, e)}
+        okt = torch.tensor([1.0 if ((par_rank is None or par_rank["ok"]) and arrived and ranks_seen == world) else 0.0], device=dev)
         dist.all_reduce(okt, op=dist.ReduceOp.MIN)
         ok = ok and bool(okt.item() > 0)
     dist_extra = None
-    if dist is not None and not args.no_extra:
+    if dist is not None and args.full and not args.no_extra:
         # SURVEY.md 8(d).4 / BASELINE configs[3], configs[4]: the STRONG-scaling case (4096 problems over the ranks) and
         # config 5 (8192 problems of 32/8, T = 64 over the ranks) beside the weak-scaling headline
         k_d = max(10, min(args.steps, 50))
@@ -1284,12 +1318,13 @@ def main():
                                      launches_all=n_all, problem_sets=len(plans), same_set=same_set, repeat_kernel_ms=repeat_ms),
         }
         if dist is not None:
-            out["parity"] = dict(par_rank, scope="rank 0's first 16 problems; every rank checks its own 16 and the run's `finite` is the MIN over ranks")
+            if par_rank is not None:
+                out["parity"] = dict(par_rank, scope="rank 0's first 16 problems; every rank checks its own 16 and the run's `finite` is the MIN over ranks")
             if dist_extra is not None:
                 out["extra"] = dist_extra
                 if not all(v.get("finite", True) for v in dist_extra.values()):
                     out["config"]["finite"] = ok = False
-        if dist is None:
+        if dist is None and args.full:
             # self-certification: the results of the launches just timed, against the oracle
             try:
                 par = parity_check(p, r, args.bounded, be=be)
@@ -1298,7 +1333,7 @@ def main():
             out["parity"] = par
             if not par["ok"]:
                 out["config"]["finite"] = ok = False
-        if dist is None and not args.no_extra:
+        if dist is None and args.full and not args.no_extra:
             try:
                 out["extra"] = attach_traffic(extra_rows(be, dev, args.steps))
                 bad_rows = [k for k, v in out["extra"].items() if isinstance(v, dict) and "parity" in v and not v["parity"].get("ok")]
@@ -1306,7 +1341,7 @@ def main():
                     out["extra_rows_out_of_tolerance"] = bad_rows
             except Exception as e:      # the contract line must survive a failing secondary row
                 out["extra"] = {"error": "%s: %s" % (type(e).__name__, e)}
-        if world == 1 and not args.no_cpu_baseline:
+        if world == 1 and args.full and not args.no_cpu_baseline:
             out["cpu_baseline"] = cpu_baseline(512, args.bounded, timed=(p, r))
             pv = out["cpu_baseline"].get("parity_vs_gpu")
             if pv is not None and pv.get("asserted") and not pv["ok"]:

@@ -155,18 +155,58 @@ def test_extra_rows_certify_themselves_box_constrained_step_and_backward():
     assert not bench.kkt_parity_check(p, nx, nu, gx, gu, grads, True)["ok"]
 
 
-def test_cpu_baseline_times_the_unmodified_reference_where_it_is_on_the_box():
+# the reference's interface as tools/ref_cpu_child.py calls it, answered by the oracle: a stand-in package named `mpc` in a directory
+# of its own, so that the CPU suite exercises bench.py's reference leg without a copy of the reference
+_STAND_IN_MPC = """
+class QuadCost:
+    def __init__(self, C, c):
+        self.C, self.c = C, c
+
+
+class LinDx:
+    def __init__(self, F, f=None):
+        self.F, self.f = F, f
+"""
+_STAND_IN_LQR_STEP = """
+import sys
+sys.path.insert(0, %r)
+import numpy as np
+import torch
+from oracle import lqr_oracle as O
+
+
+class LQRStep:
+    def __init__(self, n_state, n_ctrl, T, u_lower=None, u_upper=None, true_cost=None, true_dynamics=None, delta_space=True,
+                 current_x=None, current_u=None):
+        self.lo, self.hi, self.x, self.u = u_lower, u_upper, current_x, current_u
+
+    def __call__(self, x_init, C, c, F, f):
+        h = lambda t: None if t is None or t.numel() == 0 else t.double().numpy()
+        o = O.lqr_step(h(x_init), h(C), h(c), h(F), h(f), h(self.x), h(self.u), self.lo, self.hi, lockstep=False)
+        t = lambda a: torch.from_numpy(np.asarray(a)).float()
+        return t(o["new_x"]), t(o["new_u"]), 0, t(o["costs"]), None, None
+"""
+
+
+def test_cpu_baseline_times_the_unmodified_reference_where_it_is_on_the_box(tmp_path, monkeypatch):
     """north_star: "the reference timed on the host cores of the same box (core count stated) in the same run".  bench.py tries:
-    with $MPC_REFERENCE_DIR or /root/reference on the box, the unmodified LQRStep forward runs in a child interpreter on a chunk
-    of the timed batch and its float32 results are held against the timed results (here: the oracle's numbers stand in for
-    the kernel's).  The GPU box has no reference: the function then returns (None, None) and the port stands alone."""
+    with the reference on the box ($MPC_REFERENCE_DIR), its LQRStep forward runs in a child interpreter (tools/ref_cpu_child.py)
+    on a chunk of the timed batch and its float32 results are held against the timed results (here: an oracle-backed stand-in
+    package plays the reference, and the oracle's numbers stand in for the kernel's).  Where there is no reference the function
+    returns (None, None) and the port stands alone."""
     import numpy as np
     sys.path.insert(0, ROOT)
     import bench
     from oracle import lqr_oracle as O
-    if bench.reference_dir() is None:
+    with monkeypatch.context() as m:
+        m.setattr(bench, "reference_dir", lambda: None)
         assert bench.reference_cpu_baseline({}, False) == (None, None)
-        pytest.skip("no reference on this box")
+    (tmp_path / "mpc").mkdir()
+    (tmp_path / "mpc" / "__init__.py").write_text("")
+    (tmp_path / "mpc" / "mpc.py").write_text(_STAND_IN_MPC)
+    (tmp_path / "mpc" / "lqr_step.py").write_text(_STAND_IN_LQR_STEP % ROOT)
+    monkeypatch.setenv("MPC_REFERENCE_DIR", str(tmp_path))
+    assert bench.reference_dir() == str(tmp_path)
     p = _small_headline_problem(24, T=10)
     row, o = bench.reference_cpu_baseline(p, False, reps=1)
     assert o is not None, row
@@ -224,12 +264,12 @@ def test_contract_line_fits_the_driver_whatever_the_run_recorded():
 
 @pytest.mark.gpu
 def test_bench_stdout_is_one_short_json_line():
-    """The driver's own call, shortened (no secondary rows): stdout is exactly one line, < 4 KB, json.loads gives `roofline`
-    and `cpu_baseline`; the full record is on stderr and in bench_full.json."""
+    """The driver's own call with --full, shortened (no secondary rows): stdout is exactly one line, < 4 KB, json.loads gives
+    `roofline` and `cpu_baseline`; the full record is on stderr and in bench_full.json."""
     import json
     import tempfile
     with tempfile.TemporaryDirectory() as td:
-        r = _run(["--gpus", "1", "--steps", "5", "--warmup", "2", "--no-extra"], {"MPC_BENCH_RECORD_DIR": td})
+        r = _run(["--gpus", "1", "--steps", "5", "--warmup", "2", "--full", "--no-extra"], {"MPC_BENCH_RECORD_DIR": td})
         assert r.returncode == 0, r.stderr[-2000:]
         lines = r.stdout.strip().splitlines()
         assert len(lines) == 1 and len(lines[0]) < 4096
@@ -238,3 +278,54 @@ def test_bench_stdout_is_one_short_json_line():
         assert d["steps"] == 5 and d["warmup"] == 2 and d["n_gpus"] == 1
         full = json.load(open(os.path.join(td, "bench_full.json")))
         assert full["value"] == pytest.approx(d["value"], rel=1e-4) and "bench.py full record: " in r.stderr
+
+
+def test_dump_outputs_writes_what_the_step_returns_and_samples_a_large_batch(tmp_path, monkeypatch):
+    """--dump-outputs: the step's float outputs as DIR/<name>.npy in their own precision; above the size cap, one fixed seeded
+    sample of the problems (the same for every array, listed in problem_index.npy)."""
+    import numpy as np
+    sys.path.insert(0, ROOT)
+    import bench
+    T, B, ns, nc = 6, 40, 3, 2
+    g = torch.Generator().manual_seed(0)
+    r = dict(new_x=torch.randn(T, B, ns, generator=g), new_u=torch.randn(T, B, nc, generator=g),
+             **{k: torch.randn(B, generator=g) for k in bench.DUMP_NAMES[2:]}, qp_iters=torch.zeros(B, dtype=torch.int32))
+    bench.dump_outputs(r, str(tmp_path / "all"))
+    for k in bench.DUMP_NAMES:
+        a = np.load(tmp_path / "all" / (k + ".npy"))
+        assert a.dtype == np.float32 and np.array_equal(a, r[k].numpy()), k
+    assert not (tmp_path / "all" / "problem_index.npy").exists()
+    monkeypatch.setattr(bench, "DUMP_MAX_BYTES", 2000)
+    for d in ("a", "b"):
+        bench.dump_outputs(r, str(tmp_path / d))
+    idx = np.load(tmp_path / "a" / "problem_index.npy")
+    assert np.array_equal(idx, np.load(tmp_path / "b" / "problem_index.npy")) and 0 < len(idx) < B
+    files = [tmp_path / "a" / (k + ".npy") for k in bench.DUMP_NAMES + ("problem_index",)]
+    assert sum(np.load(f).nbytes for f in files) <= 2000
+    ii = idx.astype(np.int64)
+    assert np.array_equal(np.load(tmp_path / "a" / "new_x.npy"), r["new_x"].numpy()[:, ii])
+    assert np.array_equal(np.load(tmp_path / "a" / "costs.npy"), r["costs"].numpy()[ii])
+
+
+@pytest.mark.gpu
+def test_plain_bench_run_times_the_headline_only_and_dumps_the_same_outputs_every_run(tmp_path):
+    """A plain run (no --full): one JSON line with the contract keys, `steps` as asked, no checks or secondary rows; with
+    --dump-outputs the last timed step's results, the same from run to run."""
+    import json
+    import numpy as np
+    outs = []
+    for i in range(2):
+        d = tmp_path / ("out%d" % i)
+        r = _run(["--gpus", "1", "--steps", "7", "--warmup", "3", "--dump-outputs", str(d)], {"MPC_BENCH_RECORD_DIR": str(tmp_path)})
+        assert r.returncode == 0, r.stderr[-2000:]
+        lines = r.stdout.strip().splitlines()
+        assert len(lines) == 1
+        line = json.loads(lines[0])
+        assert line["steps"] == 7 and line["warmup"] == 3 and line["ms_per_step"] > 0 and line["higher_is_better"] is True
+        assert line["dtype"] == "f32" and line["config"]["finite"] is True
+        assert not set(("parity", "cpu_baseline", "extra_digest")) & set(line)
+        outs.append({k: np.load(d / (k + ".npy")) for k in ("new_x", "new_u", "costs", "alphas")})
+    assert outs[0]["new_x"].shape == (50, 4096, 12) and outs[0]["new_u"].shape == (50, 4096, 4) and outs[0]["new_x"].dtype == np.float32
+    for k in outs[0]:
+        assert np.isfinite(outs[0][k]).all(), k
+        np.testing.assert_allclose(outs[1][k], outs[0][k], rtol=1e-6, atol=1e-7, err_msg=k)

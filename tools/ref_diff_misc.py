@@ -1,21 +1,20 @@
 #!/usr/bin/env python3
-"""No GPU, BUILD CONTAINER ONLY: the oracle's other entry points against the UNMODIFIED reference on random inputs -- pnqp
+"""No GPU: the oracle's other entry points against the UNMODIFIED reference on random inputs -- pnqp
 (mpc/pnqp.py:5-82: solution, free set, iteration count, batched), util.get_traj / get_cost (mpc/util.py:102-153), NNDynamics
 forward and grad_input (mpc/dynamics.py:57-128: the checker of the network kernels), the shipped simulators (mpc/env_dx: next state, and the
 Jacobian + affine term MPC.linearize_dynamics(AUTO_DIFF) forms, controls past their clamp included).  float64.
-    python tools/ref_diff_misc.py [cases [seed]]"""
-import os, pickle, subprocess, sys, tempfile, types
+The reference's answers: recorded under tests/golden/ or the reference itself, as in tools/ref_diff_mpc.py.
+    python tools/ref_diff_misc.py [cases [seed]] [--record]"""
+import os, sys, types
 import numpy as np
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-REF = os.environ.get("MPC_REFERENCE_DIR", "/root/reference")
-if not os.path.isdir(os.path.join(REF, "mpc")):
-    print("no reference under %s: nothing to compare with" % REF); sys.exit(0)
+sys.path.insert(0, os.path.join(ROOT, "tools"))
+from ref_results import parse_argv, reference_results
 sys.path.insert(0, ROOT)
 from oracle import lqr_oracle as O
 from oracle import env_oracle as E
 
-n_cases = int(sys.argv[1]) if len(sys.argv) > 1 else 150
-seed0 = int(sys.argv[2]) if len(sys.argv) > 2 else 0
+n_cases, seed0, record = parse_argv(150)
 cases = []
 for i in range(n_cases):
     rng = np.random.default_rng(seed0 * 777767 + i)
@@ -56,11 +55,9 @@ for i in range(n_cases):
         N = int(rng.integers(1, 40))
         cases.append(dict(kind=kind, ns=ns, nc=nc, hidden=hidden, act=str(rng.choice(["sigmoid", "relu"])), passthrough=bool(rng.integers(0, 2)),
                           Ws=Ws, bs=bs, x=rng.standard_normal((N, ns)), u=rng.standard_normal((N, nc))))
-tmp = tempfile.mkdtemp()
-pickle.dump(cases, open(os.path.join(tmp, "cases.pkl"), "wb"))
-env = dict(os.environ); env.pop("PYTHONPATH", None)
-subprocess.check_call([sys.executable, os.path.join(ROOT, "tools", "ref_diff_misc_child.py"), os.path.join(tmp, "cases.pkl"), os.path.join(tmp, "ref.pkl")], env=env, cwd=tmp)
-ref = pickle.load(open(os.path.join(tmp, "ref.pkl"), "rb"))
+ref = reference_results("misc", "ref_diff_misc_child.py", cases, n_cases, seed0, record)
+if ref is None:
+    print("no recorded results of the reference for %d cases, seed %d, and no $MPC_REFERENCE_DIR: nothing to compare with" % (n_cases, seed0)); sys.exit(0)
 bad = broken = 0
 rel = lambda a, b: float("%.3g" % (np.abs(a - b).max() / max(1.0, np.abs(b).max()))) if np.asarray(a).size else 0.0
 for i, (cs, r) in enumerate(zip(cases, ref)):

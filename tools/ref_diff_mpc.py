@@ -1,16 +1,17 @@
 #!/usr/bin/env python3
-"""No GPU, BUILD CONTAINER ONLY (needs the reference under /root/reference): `mpc.MPC` of this package -- the host logic around
+"""No GPU: `mpc.MPC` of this package -- the host logic around
 the kernels: iteration, best-iterate bookkeeping, convergence exits, detach_unconverged, the autograd wiring of LQRStep -- on the
 oracle-backed stand-in (tests/oracle_backend.py, batch-lockstep like the reference) against the UNMODIFIED reference's `mpc.MPC`
 on random configurations: shape, horizon, batch, bounds, lqr_iter, eps, not_improved_lim, best_cost_eps, delta_u, line-search
 settings, u_init, exit_unconverged / detach_unconverged, gradients of a random functional of u w.r.t. C, c, x_init.  float64.
-    python tools/ref_diff_mpc.py [cases [seed]]"""
-import os, pickle, subprocess, sys, tempfile, warnings
+The reference's answers come from tests/golden/refdiff_mpc_<cases>_<seed>_part*.npz, or from the reference itself under
+$MPC_REFERENCE_DIR (`--record`: run it and write the fixture; tools/ref_results.py).
+    python tools/ref_diff_mpc.py [cases [seed]] [--record]"""
+import os, sys, warnings
 import numpy as np
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-REF = os.environ.get("MPC_REFERENCE_DIR", "/root/reference")
-if not os.path.isdir(os.path.join(REF, "mpc")):
-    print("no reference under %s: nothing to compare with" % REF); sys.exit(0)
+sys.path.insert(0, os.path.join(ROOT, "tools"))
+from ref_results import parse_argv, reference_results
 sys.path.insert(0, ROOT); sys.path.insert(0, os.path.join(ROOT, "tests")); sys.path.insert(0, os.path.join(ROOT, "mpc.pytorch_amd"))
 import torch
 from mpc import _native, mpc
@@ -18,8 +19,7 @@ from mpc.mpc import QuadCost, LinDx
 from oracle_backend import OracleBackend
 warnings.filterwarnings("ignore")
 
-n_cases = int(sys.argv[1]) if len(sys.argv) > 1 else 100
-seed0 = int(sys.argv[2]) if len(sys.argv) > 2 else 0
+n_cases, seed0, record = parse_argv(100)
 cases = []
 for i in range(n_cases):
     rng = np.random.default_rng(seed0 * 1000003 + i)
@@ -101,11 +101,9 @@ for i in range(n_cases):
         continue
     cases.append(dict(ns=ns, nc=nc, T=T, B=B, C=C, c=c, F=F, f=f, x_init=rng.standard_normal((B, ns)), kw=kw, grads=grads, ref_norm=ref_norm,
                       w=rng.standard_normal((T, B, nc))))
-tmp = tempfile.mkdtemp()
-pickle.dump(cases, open(os.path.join(tmp, "cases.pkl"), "wb"))
-env = dict(os.environ); env.pop("PYTHONPATH", None)
-subprocess.check_call([sys.executable, os.path.join(ROOT, "tools", "ref_diff_child.py"), os.path.join(tmp, "cases.pkl"), os.path.join(tmp, "ref.pkl")], env=env, cwd=tmp)
-ref = pickle.load(open(os.path.join(tmp, "ref.pkl"), "rb"))
+ref = reference_results("mpc", "ref_diff_child.py", cases, n_cases, seed0, record)
+if ref is None:
+    print("no recorded results of the reference for %d cases, seed %d, and no $MPC_REFERENCE_DIR: nothing to compare with" % (n_cases, seed0)); sys.exit(0)
 
 prev = _native.set_backend_for_testing(OracleBackend(lockstep=True))
 bad = errors_both = 0

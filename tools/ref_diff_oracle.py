@@ -1,21 +1,20 @@
 #!/usr/bin/env python3
-"""No GPU, BUILD CONTAINER ONLY: the CPU oracle (oracle/) against the UNMODIFIED reference's LQRStep on RANDOM problems -- the
+"""No GPU: the CPU oracle (oracle/) against the UNMODIFIED reference's LQRStep on RANDOM problems -- the
 pin of tests/test_oracle_golden.py (72 fixtures) widened to thousands of cases: forward (new_x, new_u, costs, pnqp iteration total,
 the batch's du norm) with lockstep semantics, and LQRStepFn.backward through the reference's own autograd against kkt_backward.
 Shapes, horizons, batches, bounds (none / scalar / tensor), delta_u, u_zero_I, f on / off, line-search depth, nominals on and off
-their rollout, float64.      python tools/ref_diff_oracle.py [cases [seed]]"""
-import os, pickle, subprocess, sys, tempfile
+their rollout, float64.  The reference's answers: recorded under tests/golden/ or the reference itself, as in
+tools/ref_diff_mpc.py.      python tools/ref_diff_oracle.py [cases [seed]] [--record]"""
+import os, sys
 import numpy as np
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-REF = os.environ.get("MPC_REFERENCE_DIR", "/root/reference")
-if not os.path.isdir(os.path.join(REF, "mpc")):
-    print("no reference under %s: nothing to compare with" % REF); sys.exit(0)
+sys.path.insert(0, os.path.join(ROOT, "tools"))
+from ref_results import parse_argv, reference_results
 sys.path.insert(0, ROOT); sys.path.insert(0, os.path.join(ROOT, "tests"))
 from oracle import lqr_oracle as O
 from helpers import scrambled_du_norm
 
-n_cases = int(sys.argv[1]) if len(sys.argv) > 1 else 100
-seed0 = int(sys.argv[2]) if len(sys.argv) > 2 else 0
+n_cases, seed0, record = parse_argv(100)
 cases = []
 for i in range(n_cases):
     rng = np.random.default_rng(seed0 * 999983 + i)
@@ -55,11 +54,9 @@ def alone(cs, b):
     d["B"] = 1; d["grads"] = False
     return d
 singles = [alone(cs, b) for cs in cases for b in range(cs["B"])]
-tmp = tempfile.mkdtemp()
-pickle.dump(cases + singles, open(os.path.join(tmp, "cases.pkl"), "wb"))
-env = dict(os.environ); env.pop("PYTHONPATH", None)
-subprocess.check_call([sys.executable, os.path.join(ROOT, "tools", "ref_diff_oracle_child.py"), os.path.join(tmp, "cases.pkl"), os.path.join(tmp, "ref.pkl")], env=env, cwd=tmp)
-ref_all = pickle.load(open(os.path.join(tmp, "ref.pkl"), "rb"))
+ref_all = reference_results("oracle", "ref_diff_oracle_child.py", cases + singles, n_cases, seed0, record)
+if ref_all is None:
+    print("no recorded results of the reference for %d cases, seed %d, and no $MPC_REFERENCE_DIR: nothing to compare with" % (n_cases, seed0)); sys.exit(0)
 ref, ref1 = ref_all[:len(cases)], ref_all[len(cases):]
 bad = ref_broken = coupled = 0
 k1 = 0
