@@ -289,7 +289,7 @@ int mpc_env_linearize(const mpc_env_dynamics *env, int dtype, int64_t N, const v
 /* (6d) mpc.dynamics.NNDynamics (mpc/dynamics.py:15-128) as the dynamics: a fully connected network
  *      [x;u] -> x' whose weights are shared by the whole batch, fp32.  W[l] / b[l] are nn.Linear's own tensors
  *      (row-major [widths[l+1]][widths[l]], [widths[l+1]]), device pointers; the same activation follows every layer
- *      but the last; `passthrough` adds x to the output (:74-75).  n_state <= 16. */
+ *      but the last; `passthrough` adds x to the output (:74-75).  n_state <= 32. */
 enum { MPC_ACT_SIGMOID = 0, MPC_ACT_RELU = 1, MPC_ACT_ELU = 2 };
 #define MPC_MLP_MAX_LAYERS 4
 typedef struct mpc_mlp_dynamics {

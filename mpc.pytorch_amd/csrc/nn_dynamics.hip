@@ -19,6 +19,10 @@
 //                        W_L diag(s_{L-1}) W_{L-1} ... diag(s_1) W_1 per point, every product after the first an MFMA
 //                        whose B operand is the previous product's accumulator; f = net(x, u) - F [x;u]
 //
+// n_state <= 16 is one accumulator tile of output features; 16 < n_state <= 32 is two (nn_wide_rollout_kernel,
+// nn_wide_linearize_kernel: the same bodies with the tile count ST = 2 -- lane (q, r) owns state features 16 s + 4q + v,
+// s < ST; the second tile lives in registers, the LDS staging areas are the same).
+//
 // Weights are re-packed once per call into zero-padded [out_pad][in_pad] blocks (multiples of 16) in the workspace.
 #include <string>
 
@@ -100,16 +104,22 @@ __device__ __forceinline__ f32x4 slope_fn(f32x4 z, int kind)
 
 // All layers for the sixteen columns staged in tauS (row r = column's [x;u], zero padded to wp[0]).  Hidden
 // activations go to zbase: layer l at zbase + l * 16 * ZS when KEEP (the Jacobian needs them all), else ping-pong.
-// Returns the output layer's accumulator: features 4q..4q+3 of column r (n_state <= 16: one tile).
+// Returns the output layer's accumulators: tile s holds features 16 s + 4q .. + 3 of column r (ST tiles: n_state <= 16 ST).
 // wts: the packed network (LDS or global).  The operand loads of the next K-step are issued before the current
 // one's MFMAs: with one wavefront per SIMD nothing else hides their latency.
-template <bool KEEP>
-__device__ __forceinline__ f32x4 mlp_forward(const MlpDesc &m, const float *wts, const float *tauS, int TS, float *zbase,
-                                             int ZS, int q, int r)
+template <int ST> struct OutTiles {
+    f32x4 t[ST];
+};
+
+template <bool KEEP, int ST>
+__device__ __forceinline__ OutTiles<ST> mlp_forward(const MlpDesc &m, const float *wts, const float *tauS, int TS, float *zbase,
+                                                    int ZS, int q, int r)
 {
     const float *in = tauS;
     int is = TS;
-    f32x4 res = {0.f, 0.f, 0.f, 0.f};
+    OutTiles<ST> res;
+#pragma unroll
+    for (int s = 0; s < ST; ++s) res.t[s] = f32x4{0.f, 0.f, 0.f, 0.f};
     for (int l = 0; l < m.L; ++l) {
         const int nin_t = m.wp[l] >> 4, nout_t = m.wp[l + 1] >> 4, ldp = m.wp[l] + 4;
         const float *W = wts + m.woff[l], *bias = wts + m.boff[l];
@@ -137,8 +147,10 @@ __device__ __forceinline__ f32x4 mlp_forward(const MlpDesc &m, const float *wts,
             f32x4 acc = (a0 + a1) + (a2 + a3);
             if (!last) {
                 *reinterpret_cast<f32x4 *>(dst + r * ZS + 16 * to + 4 * q) = act_fn(acc, m.act);
-            } else if (to == 0) {
-                res = acc;
+            } else {
+                // (a constant index per branch: a register array indexed by the loop counter would go to scratch memory)
+                if (to == 0) res.t[0] = acc;
+                if (ST > 1 && to == 1) res.t[ST - 1] = acc;
             }
         }
         wave_sync();
@@ -173,10 +185,10 @@ __device__ __forceinline__ float line_search_delta(float tau_i, float d_i, float
 // ---------------------------------------------------------------------------------------------------------------
 // lqr_forward through the network (mpc/lqr_step.py:164-261), sixteen problems per wavefront.
 // lane (q, r): problem r of the group, quarter q of every per-problem loop (controls i = q, q+4, ..; cost rows likewise);
-// the state x' is the output accumulator: features 4q..4q+3.
+// the state x' is the output accumulators: features 16 s + 4q .. + 3 of state tile s < ST (n_state <= 16 ST).
 // ---------------------------------------------------------------------------------------------------------------
-template <bool WL>
-__global__ void __launch_bounds__(256) nn_rollout_kernel(StepParams<float> p, MlpDesc m, int TS, int ZS, int wave_floats)
+template <bool WL, int ST>
+__device__ __forceinline__ void rollout_tiles(StepParams<float> p, MlpDesc m, int TS, int ZS, int wave_floats)
 {
     extern __shared__ __attribute__((aligned(16))) float lds[];
     const float *wts = stage_weights<WL>(m, lds);
@@ -201,24 +213,28 @@ __global__ void __launch_bounds__(256) nn_rollout_kernel(StepParams<float> p, Ml
     bool active = valid;
     const int max_ls = has_gain ? p.max_ls : 1;
     for (int pass = 0; pass < max_ls; ++pass) {
-        float xr[4];
+        float xr[ST][4];
 #pragma unroll
-        for (int v = 0; v < 4; ++v) {
-            const int f = 4 * q + v;
-            xr[v] = f < ns ? p.x_init[b * ns + f] : 0.f;
-            if (active && f < ns) p.new_x[b * ns + f] = xr[v];
-        }
+        for (int s = 0; s < ST; ++s)
+#pragma unroll
+            for (int v = 0; v < 4; ++v) {
+                const int f = 16 * s + 4 * q + v;
+                xr[s][v] = f < ns ? p.x_init[b * ns + f] : 0.f;
+                if (active && f < ns) p.new_x[b * ns + f] = xr[s][v];
+            }
         float ca = 0.f, da = 0.f;
         for (int t = 0; t < T; ++t) {
             const long tb = (long)t * B + b;
 #pragma unroll
-            for (int v = 0; v < 4; ++v) {
-                const int f = 4 * q + v;
-                if (f < ns) {
-                    tauS[r * TS + f] = xr[v];
-                    dxS[r * TS + f] = has_gain ? xr[v] - p.cur_x[tb * ns + f] : 0.f;      // :227
+            for (int s = 0; s < ST; ++s)
+#pragma unroll
+                for (int v = 0; v < 4; ++v) {
+                    const int f = 16 * s + 4 * q + v;
+                    if (f < ns) {
+                        tauS[r * TS + f] = xr[s][v];
+                        dxS[r * TS + f] = has_gain ? xr[s][v] - p.cur_x[tb * ns + f] : 0.f;   // :227
+                    }
                 }
-            }
             wave_sync();
             for (int i = q; i < nc; i += 4) {
                 const float u = p.cur_u[tb * nc + i];
@@ -267,15 +283,17 @@ __global__ void __launch_bounds__(256) nn_rollout_kernel(StepParams<float> p, Ml
                 }
             }
             if (t < T - 1) {                                                                // :223-225
-                const f32x4 o = mlp_forward<false>(m, wts, tauS, TS, zb, ZS, q, r);
+                const OutTiles<ST> o = mlp_forward<false, ST>(m, wts, tauS, TS, zb, ZS, q, r);
 #pragma unroll
-                for (int v = 0; v < 4; ++v) {
-                    const int f = 4 * q + v;
-                    // mpc/dynamics.py:74-75; an augmented state's first entries are the control just applied (:139-147)
-                    const float skip = f < m.carry ? tauS[r * TS + ns + f] : (m.pass ? xr[v] : 0.f);
-                    xr[v] = f < ns ? o[v] + skip : 0.f;
-                    if (active && f < ns) p.new_x[((long)(t + 1) * B + b) * ns + f] = xr[v];
-                }
+                for (int s = 0; s < ST; ++s)
+#pragma unroll
+                    for (int v = 0; v < 4; ++v) {
+                        const int f = 16 * s + 4 * q + v;
+                        // mpc/dynamics.py:74-75; an augmented state's first entries are the control just applied (:139-147)
+                        const float skip = f < m.carry ? tauS[r * TS + ns + f] : (m.pass ? xr[s][v] : 0.f);
+                        xr[s][v] = f < ns ? o.t[s][v] + skip : 0.f;
+                        if (active && f < ns) p.new_x[((long)(t + 1) * B + b) * ns + f] = xr[s][v];
+                    }
                 wave_sync();
             } else {
                 wave_sync();
@@ -305,15 +323,28 @@ __global__ void __launch_bounds__(256) nn_rollout_kernel(StepParams<float> p, Ml
     }
 }
 
+template <bool WL>
+__global__ void __launch_bounds__(256) nn_rollout_kernel(StepParams<float> p, MlpDesc m, int TS, int ZS, int wave_floats)
+{
+    rollout_tiles<WL, 1>(p, m, TS, ZS, wave_floats);
+}
+// 16 < n_state <= 32: two state tiles, the second one in registers next to the first (same LDS staging, same launch)
+template <bool WL>
+__global__ void __launch_bounds__(256) nn_wide_rollout_kernel(StepParams<float> p, MlpDesc m, int TS, int ZS, int wave_floats)
+{
+    rollout_tiles<WL, 2>(p, m, TS, ZS, wave_floats);
+}
+
 // ---------------------------------------------------------------------------------------------------------------
 // F = d net / d [x;u], f = net(x, u) - F [x;u] at N points (mpc/mpc.py:495-512 + mpc/dynamics.py:82-128), sixteen
 // points per wavefront: one forward pass for all sixteen, then the chain of one point at a time.  A product
 // G_l = diag(s_l) W_l G_{l-1} is [width_l x n]: tile (to, tj) in accumulator layout is rows 16 to + 4q + v, column
 // 16 tj + r -- written to this lane's own LDS slot and read back by this lane as the B operand of layer l + 1.
 // ---------------------------------------------------------------------------------------------------------------
-template <bool WL>
-__global__ void __launch_bounds__(512) nn_linearize_kernel(MlpDesc m, long N, int ns, int nc, const float *x, const float *u,
-                                                           float *F, float *f, int TS, int ZS, int GT, int wave_floats)
+// ST: row tiles of the output layer (n_state <= 16 ST).
+template <bool WL, int ST>
+__device__ __forceinline__ void linearize_tiles(MlpDesc m, long N, int ns, int nc, const float *x, const float *u,
+                                                float *F, float *f, int TS, int ZS, int GT, int wave_floats)
 {
     extern __shared__ __attribute__((aligned(16))) float lds[];
     const float *wts = stage_weights<WL>(m, lds);
@@ -333,10 +364,12 @@ __global__ void __launch_bounds__(512) nn_linearize_kernel(MlpDesc m, long N, in
         }
     }
     wave_sync();
-    f32x4 out = mlp_forward<true>(m, wts, tauS, TS, zb, ZS, q, r);
+    OutTiles<ST> out = mlp_forward<true, ST>(m, wts, tauS, TS, zb, ZS, q, r);
     if (m.pass) {
 #pragma unroll
-        for (int v = 0; v < 4; ++v) out[v] += (4 * q + v < ns) ? tauS[r * TS + 4 * q + v] : 0.f;
+        for (int s = 0; s < ST; ++s)
+#pragma unroll
+            for (int v = 0; v < 4; ++v) out.t[s][v] += (16 * s + 4 * q + v < ns) ? tauS[r * TS + 16 * s + 4 * q + v] : 0.f;
     }
     const int Lh = m.L - 1;
     for (int pp = 0; pp < 16; ++pp) {
@@ -373,55 +406,91 @@ __global__ void __launch_bounds__(512) nn_linearize_kernel(MlpDesc m, long N, in
             Gprev = Gcur;
             Gcur = sw;
         }
-        // output layer: J = W_L G_{L-1}  (n_state <= 16: one row tile)
-        float fs[4] = {0.f, 0.f, 0.f, 0.f};
+        // output layer: J = W_L G_{L-1}, ST row tiles side by side (one read of G_{L-1} feeds them all)
+        float fs[ST][4];
+#pragma unroll
+        for (int s = 0; s < ST; ++s)
+#pragma unroll
+            for (int v = 0; v < 4; ++v) fs[s][v] = 0.f;
         {
             const int l = Lh, nin_t = m.wp[l] >> 4, ld = m.wp[l] + 4;
             const float *W = wts + m.woff[l];
             for (int tj = 0; tj < NTJ; ++tj) {
-                f32x4 J;
+                f32x4 J[ST];
                 if (Lh == 0) {
 #pragma unroll
-                    for (int v = 0; v < 4; ++v) J[v] = W[(4 * q + v) * ld + 16 * tj + r];
+                    for (int s = 0; s < ST; ++s)
+#pragma unroll
+                        for (int v = 0; v < 4; ++v) J[s][v] = W[(16 * s + 4 * q + v) * ld + 16 * tj + r];
                 } else {
-                    f32x4 a0 = {0.f, 0.f, 0.f, 0.f}, a1 = a0, a2 = a0, a3 = a0;
+                    f32x4 a0[ST], a1[ST], a2[ST], a3[ST];
+#pragma unroll
+                    for (int s = 0; s < ST; ++s) a0[s] = a1[s] = a2[s] = a3[s] = f32x4{0.f, 0.f, 0.f, 0.f};
                     const float *wrow = W + r * ld + 4 * q;
                     for (int ti = 0; ti < nin_t; ++ti) {
-                        const f32x4 a = *reinterpret_cast<const f32x4 *>(wrow + 16 * ti);
+                        f32x4 a[ST];
+#pragma unroll
+                        for (int s = 0; s < ST; ++s) a[s] = *reinterpret_cast<const f32x4 *>(wrow + 16 * s * ld + 16 * ti);
                         const f32x4 gp = Gprev[(ti * NTJ + tj) * 64 + lane];
-                        a0 = mfma(a[0], gp[0], a0);
-                        a1 = mfma(a[1], gp[1], a1);
-                        a2 = mfma(a[2], gp[2], a2);
-                        a3 = mfma(a[3], gp[3], a3);
+#pragma unroll
+                        for (int s = 0; s < ST; ++s) {
+                            a0[s] = mfma(a[s][0], gp[0], a0[s]);
+                            a1[s] = mfma(a[s][1], gp[1], a1[s]);
+                            a2[s] = mfma(a[s][2], gp[2], a2[s]);
+                            a3[s] = mfma(a[s][3], gp[3], a3[s]);
+                        }
                     }
-                    J = (a0 + a1) + (a2 + a3);
+#pragma unroll
+                    for (int s = 0; s < ST; ++s) J[s] = (a0[s] + a1[s]) + (a2[s] + a3[s]);
                 }
                 const int j = 16 * tj + r;
                 const float tj_tau = tauS[pp * TS + j];
 #pragma unroll
-                for (int v = 0; v < 4; ++v) {
-                    const int i = 4 * q + v;
-                    if (m.pass && i == j && j < ns) J[v] += 1.f;                            // mpc/dynamics.py:118-125
-                    if (i < ns && j < n) F[((p0 + pp) * ns + i) * n + j] = J[v];
-                    fs[v] = fmaf(J[v], tj_tau, fs[v]);
-                }
+                for (int s = 0; s < ST; ++s)
+#pragma unroll
+                    for (int v = 0; v < 4; ++v) {
+                        const int i = 16 * s + 4 * q + v;
+                        if (m.pass && i == j && j < ns) J[s][v] += 1.f;                     // mpc/dynamics.py:118-125
+                        if (i < ns && j < n) F[((p0 + pp) * ns + i) * n + j] = J[s][v];
+                        fs[s][v] = fmaf(J[s][v], tj_tau, fs[s][v]);
+                    }
             }
         }
 #pragma unroll
-        for (int v = 0; v < 4; ++v) {
-            float s = fs[v];
-            s += __shfl_xor(s, 1);
-            s += __shfl_xor(s, 2);
-            s += __shfl_xor(s, 4);
-            s += __shfl_xor(s, 8);
-            fs[v] = s;
-        }
+        for (int s = 0; s < ST; ++s)
+#pragma unroll
+            for (int v = 0; v < 4; ++v) {
+                float a = fs[s][v];
+                a += __shfl_xor(a, 1);
+                a += __shfl_xor(a, 2);
+                a += __shfl_xor(a, 4);
+                a += __shfl_xor(a, 8);
+                fs[s][v] = a;
+            }
         if (r == pp) {
 #pragma unroll
-            for (int v = 0; v < 4; ++v)
-                if (4 * q + v < ns) f[(p0 + pp) * ns + 4 * q + v] = out[v] - fs[v];        // mpc/mpc.py:508-509
+            for (int s = 0; s < ST; ++s)
+#pragma unroll
+                for (int v = 0; v < 4; ++v) {
+                    const int i = 16 * s + 4 * q + v;
+                    if (i < ns) f[(p0 + pp) * ns + i] = out.t[s][v] - fs[s][v];               // mpc/mpc.py:508-509
+                }
         }
     }
+}
+
+template <bool WL>
+__global__ void __launch_bounds__(512) nn_linearize_kernel(MlpDesc m, long N, int ns, int nc, const float *x, const float *u,
+                                                           float *F, float *f, int TS, int ZS, int GT, int wave_floats)
+{
+    linearize_tiles<WL, 1>(m, N, ns, nc, x, u, F, f, TS, ZS, GT, wave_floats);
+}
+// 16 < n_state <= 32: two row tiles of the output layer, of F and of f
+template <bool WL>
+__global__ void __launch_bounds__(512) nn_wide_linearize_kernel(MlpDesc m, long N, int ns, int nc, const float *x, const float *u,
+                                                                float *F, float *f, int TS, int ZS, int GT, int wave_floats)
+{
+    linearize_tiles<WL, 2>(m, N, ns, nc, x, u, F, f, TS, ZS, GT, wave_floats);
 }
 
 // ===============================================================================================================
@@ -888,7 +957,7 @@ int mlp_prepare(const mpc_mlp_dynamics *net, int ns, int nc, void *workspace, in
     if (net->n_layers < 1 || net->n_layers > MPC_MLP_MAX_LAYERS) { set_last_error("network: 1..4 Linear layers"); return MPC_E_ARG; }
     if (net->activation < MPC_ACT_SIGMOID || net->activation > MPC_ACT_ELU) { set_last_error("network: unknown activation"); return MPC_E_ARG; }
     if (net->widths[0] != ns + nc || net->widths[net->n_layers] != ns) { set_last_error("network: widths[0] must be n_state + n_ctrl, widths[L] n_state"); return MPC_E_DIMS; }
-    if (ns > 16) { set_last_error("network kernels: n_state <= 16"); return MPC_E_DIMS; }
+    if (ns > 32) { set_last_error("network kernels: n_state <= 32"); return MPC_E_DIMS; }
     for (int l = 0; l <= net->n_layers; ++l)
         if (net->widths[l] < 1 || net->widths[l] > 4096) { set_last_error("network: layer width out of range"); return MPC_E_DIMS; }
     if (mpc_mlp_workspace_bytes(net) > bytes || !workspace || ((uintptr_t)workspace & 15)) {
@@ -945,7 +1014,7 @@ template <typename K> void allow_lds(K kernel, size_t lds)
 // (a 1024-unit layer is a legal NNDynamics, it just keeps the host-driven path).  bit 0: rollout, bit 1: linearisation.
 int nn_budget(const mpc_mlp_dynamics *net, int ns, int nc)
 {
-    if (!net || net->n_layers < 1 || net->n_layers > MPC_MLP_MAX_LAYERS || ns < 1 || ns > 16 || nc < 1) return 0;
+    if (!net || net->n_layers < 1 || net->n_layers > MPC_MLP_MAX_LAYERS || ns < 1 || ns > 32 || nc < 1) return 0;
     if (net->widths[0] != ns + nc || net->widths[net->n_layers] != ns) return 0;
     int wp[MPC_MLP_MAX_LAYERS + 1], total = 0, hid = 16;
     for (int l = 0; l <= net->n_layers; ++l) {
@@ -1007,7 +1076,16 @@ int launch_nn_rollout(const StepParams<float> &p, const mpc_mlp_dynamics *net, v
     while (nw > 1 && (wl ? wbytes : 0) + nw * per_wave > LDS_MAX) nw >>= 1;
     const size_t lds = (wl ? wbytes : 0) + nw * per_wave;
     const unsigned grid = (unsigned)((groups + nw - 1) / nw);
-    if (wl) {
+    if (p.ns > 16) {
+        // two state tiles (the extra one lives in registers: same staging, same grid)
+        if (wl) {
+            allow_lds(&nn_wide_rollout_kernel<true>, lds);
+            hipLaunchKernelGGL(nn_wide_rollout_kernel<true>, dim3(grid), dim3(64 * nw), lds, st, p, d, TS, ZS, wave_floats);
+        } else {
+            allow_lds(&nn_wide_rollout_kernel<false>, lds);
+            hipLaunchKernelGGL(nn_wide_rollout_kernel<false>, dim3(grid), dim3(64 * nw), lds, st, p, d, TS, ZS, wave_floats);
+        }
+    } else if (wl) {
         allow_lds(&nn_rollout_kernel<true>, lds);
         hipLaunchKernelGGL(nn_rollout_kernel<true>, dim3(grid), dim3(64 * nw), lds, st, p, d, TS, ZS, wave_floats);
     } else {
@@ -1052,7 +1130,15 @@ int launch_nn_linearize(const mpc_mlp_dynamics *net, long N, int ns, int nc, con
     while (nw > 1 && (wl ? wbytes : 0) + nw * per_wave > LDS_MAX) nw >>= 1;
     const size_t lds = (wl ? wbytes : 0) + nw * per_wave;
     const unsigned grid = (unsigned)((groups + nw - 1) / nw);
-    if (wl) {
+    if (ns > 16) {
+        if (wl) {
+            allow_lds(&nn_wide_linearize_kernel<true>, lds);
+            hipLaunchKernelGGL(nn_wide_linearize_kernel<true>, dim3(grid), dim3(64 * nw), lds, st, d, N, ns, nc, x, u, F, f, TS, ZS, GT, wave_floats);
+        } else {
+            allow_lds(&nn_wide_linearize_kernel<false>, lds);
+            hipLaunchKernelGGL(nn_wide_linearize_kernel<false>, dim3(grid), dim3(64 * nw), lds, st, d, N, ns, nc, x, u, F, f, TS, ZS, GT, wave_floats);
+        }
+    } else if (wl) {
         allow_lds(&nn_linearize_kernel<true>, lds);
         hipLaunchKernelGGL(nn_linearize_kernel<true>, dim3(grid), dim3(64 * nw), lds, st, d, N, ns, nc, x, u, F, f, TS, ZS, GT, wave_floats);
     } else {

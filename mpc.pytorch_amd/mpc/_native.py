@@ -139,11 +139,11 @@ class MlpSpec:
 
     @staticmethod
     def supported(weights, activation, like):
-        """fp32 on the device of `like`, at most four layers, n_state <= 16, and layer widths whose staging areas fit the
+        """fp32 on the device of `like`, at most four layers, n_state <= 32, and layer widths whose staging areas fit the
         160 KiB of LDS the kernels work in -- the library's own test (mpc_mlp_supported: both the rollout and the
         linearisation kernel must take the network, e.g. NNDynamics(4, 1, [1024]) does not and keeps the module path)."""
         if not (like.is_cuda and like.dtype == torch.float32 and 1 <= len(weights) <= MLP_MAX_LAYERS
-                and activation in ACT_CODES and weights[-1].shape[0] <= 16
+                and activation in ACT_CODES and weights[-1].shape[0] <= 32
                 and all(W.shape[0] <= 4096 for W in weights)
                 and all(W.is_cuda and W.dtype == torch.float32 for W in weights)):
             return False

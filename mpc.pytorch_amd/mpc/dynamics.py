@@ -91,7 +91,7 @@ class NNDynamics(nn.Module):
 
     def native_net(self, like):
         """The network as the kernels take it (csrc/nn_dynamics.hip: layers on MFMA, 16 problems per wavefront), or None
-        when this network / tensor is outside their limits (fp32 on the device, <= 4 layers, n_state <= 16) -- the
+        when this network / tensor is outside their limits (fp32 on the device, <= 4 layers, n_state <= 32) -- the
         caller then calls the module timestep by timestep like the reference (mpc/lqr_step.py:223-225)."""
         from ._native import MlpSpec
         # the kernels rebuild the computation from fcs / activation / passthrough: a subclass that overrides forward
@@ -151,12 +151,12 @@ class CtrlPassthroughDynamics(nn.Module):
         return out.squeeze() if was_vector else out
 
     def native_net(self, like):
-        """Around an NNDynamics the kernels can run (fp32, augmented n_state <= 16): the augmented network, else None."""
+        """Around an NNDynamics the kernels can run (fp32, augmented n_state <= 32): the augmented network, else None."""
         if type(self).forward is not CtrlPassthroughDynamics.forward or self._forward_hooks or self._forward_pre_hooks:
             return None
         inner = getattr(self.dynamics, "native_net", None)
         net = inner(like) if inner is not None and not isinstance(self.dynamics, CtrlPassthroughDynamics) else None
-        if net is None or net.n_state + net.n_ctrl > 16:
+        if net is None or net.n_state + net.n_ctrl > 32:
             return None
         return net.augmented()
 

@@ -246,7 +246,7 @@ class MPC(Module):
                 and self.grad_method in (GradMethods.ANALYTIC, GradMethods.AUTO_DIFF) and T > 1 and not ref_norm):
             sim = dx.native_env()
         be = _native.backend()
-        # NNDynamics the kernels take (fp32 on the device, <= 4 layers, n_state <= 16), ANALYTIC linearisation: the whole
+        # NNDynamics the kernels take (fp32 on the device, <= 4 layers, n_state <= 32), ANALYTIC linearisation: the whole
         # iteration is three pre-bound C calls (round 5; the general loop below pays allocations, struct rebuilds, an autograd
         # node and a device synchronisation per iteration: 1.1 ms an iteration for 0.52 ms of kernels at the headline shape)
         net = None

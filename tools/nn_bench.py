@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Timings of the NNDynamics path on the GPU box: the three kernels of csrc/nn_dynamics.hip against this package's
 host-driven path (the module called timestep by timestep; torch's batched grad_input), and a whole MPC.forward.
-usage: python tools/nn_bench.py [B] [T] [hidden]"""
+usage: python tools/nn_bench.py [B] [T] [hidden] [n_state] [n_ctrl]      (defaults 4096 50 100 12 4)"""
 import json
 import os
 import sys
@@ -32,7 +32,8 @@ def main():
     B = int(sys.argv[1]) if len(sys.argv) > 1 else 4096
     T = int(sys.argv[2]) if len(sys.argv) > 2 else 50
     H = int(sys.argv[3]) if len(sys.argv) > 3 else 100
-    ns, nc = 12, 4
+    ns = int(sys.argv[4]) if len(sys.argv) > 4 else 12
+    nc = int(sys.argv[5]) if len(sys.argv) > 5 else 4
     n = ns + nc
     dev = "cuda:0"
     torch.manual_seed(0)
@@ -51,7 +52,7 @@ def main():
     F, f = Fl.view(T - 1, B, ns, n), fl.view(T - 1, B, ns)
     opts = StepOptions(u_lower=-1.0, u_upper=1.0)
     sw = be.lqr_step(x0, C, c, F, f, xs, u0, StepOptions(u_lower=-1.0, u_upper=1.0, max_linesearch_iter=1), want_gains=True)
-    res = {"B": B, "T": T, "hidden": H}
+    res = {"B": B, "T": T, "hidden": H, "n_state": ns, "n_ctrl": nc}
     res["kernel_get_traj_ms"] = timed(lambda: be.mlp_traj_cost(x0, u0, net))
     res["kernel_linearize_ms"] = timed(lambda: be.mlp_linearize(net, X, U))
     res["kernel_sweep_ms"] = timed(lambda: be.lqr_step(x0, C, c, F, f, xs, u0, StepOptions(u_lower=-1.0, u_upper=1.0, max_linesearch_iter=1), want_gains=True))
@@ -95,8 +96,10 @@ def main():
     a, b = solve(dyn), solve(plain)
     res["solve_cost_rel_diff"] = float(((a[2] - b[2]).abs() / (1 + b[2].abs())).max())
     print(json.dumps(res, indent=1))
-    os.makedirs(os.path.join(ROOT, "gpurun_out"), exist_ok=True)
-    json.dump(res, open(os.path.join(ROOT, "gpurun_out", "nn_bench_B%d_T%d_H%d.json" % (B, T, H)), "w"), indent=1)
+    # the record goes where bench.py's goes (MPC_BENCH_RECORD_DIR), else to bench_records/ in the tree
+    out_dir = os.environ.get("MPC_BENCH_RECORD_DIR") or os.path.join(ROOT, "bench_records")
+    os.makedirs(out_dir, exist_ok=True)
+    json.dump(res, open(os.path.join(out_dir, "nn_bench_%d_%d_B%d_T%d_H%d.json" % (ns, nc, B, T, H)), "w"), indent=1)
 
 
 if __name__ == "__main__":
