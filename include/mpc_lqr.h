@@ -286,6 +286,21 @@ int mpc_env_traj_cost(const mpc_lqr_problem *p, const mpc_env_dynamics *env, voi
 int mpc_env_linearize(const mpc_env_dynamics *env, int dtype, int64_t N, const void *x, const void *u,
                       void *F, void *f, void *stream);
 
+/* (6c') The backward of (6c) with respect to the simulator's parameters -- what makes a solve through a shipped simulator
+ *     trainable in its physical parameters (GradMethods.AUTO_DIFF with params.requires_grad).  With x, u constants
+ *     (mpc/mpc.py:495-497) and cotangents gF [N,ns,ns+1], gf [N,ns] of F, f:
+ *         gparams[k] = sum_i  sum_r gf_ir d env_r / d p_k  +  sum_rj (gF_irj - gf_ir [x;u]_ij) d^2 env_r / d [x;u]_j d p_k
+ *     for the 3 / 5 / 4 parameters of env->kind, in `dtype`.  The derivatives are the transition's own (csrc/env_param_grad.h
+ *     runs the kernels' env_step on numbers that carry a tangent per parameter); the clamp of the control has derivative 1 on
+ *     the closed interval, 0 outside.  One point per lane, per-lane and all later sums in double for both dtypes, no atomics:
+ *     the result is bitwise reproducible and depends on the prior contents of neither gparams nor the workspace.
+ *     workspace: mpc_env_param_grad_workspace_bytes(N) bytes (positive, non-decreasing in N), 8-byte aligned; a shorter one is
+ *     MPC_E_DIMS.  N = 0 succeeds and writes nothing (there is no point to sum: the caller's zeros stand). */
+int64_t mpc_env_param_grad_workspace_bytes(int64_t N);
+int mpc_env_param_grad(const mpc_env_dynamics *env, int dtype, int64_t N, const void *x, const void *u,
+                       const void *gF, const void *gf, void *gparams, void *workspace, int64_t workspace_bytes,
+                       void *stream);
+
 /* (6d) mpc.dynamics.NNDynamics (mpc/dynamics.py:15-128) as the dynamics: a fully connected network
  *      [x;u] -> x' whose weights are shared by the whole batch, fp32.  W[l] / b[l] are nn.Linear's own tensors
  *      (row-major [widths[l+1]][widths[l]], [widths[l+1]]), device pointers; the same activation follows every layer

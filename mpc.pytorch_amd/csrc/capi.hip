@@ -352,7 +352,7 @@ int mpc_lqr_abi_version(void) { return MPC_LQR_ABI_VERSION; }
 const char *mpc_lqr_build_info(void)
 {
     return "libmpc_lqr_hip gfx950 (CDNA4) | kernels: lqr_step_generic<f32,f64>, lqr_step_mfma16<f32,f64>, lqr_step_dpp16<f32>, lqr_step_dpp16_padded<f32>, "
-           "lqr_step_tiny<f32,f64>, lqr_step_wave1<f32>, lqr_step_mfma40<f32>, lqr_step_mfma40_padded<f32>, nn_rollout<f32>, nn_linearize<f32>, env_linearize, kkt_grads, kkt_fused<f32>, kkt_fused_padded<f32>, pnqp, traj_cost, select_best | built " __DATE__ " " __TIME__;
+           "lqr_step_tiny<f32,f64>, lqr_step_wave1<f32>, lqr_step_mfma40<f32>, lqr_step_mfma40_padded<f32>, nn_rollout<f32>, nn_linearize<f32>, env_linearize, env_param_grad<f32,f64>, kkt_grads, kkt_fused<f32>, kkt_fused_padded<f32>, pnqp, traj_cost, select_best | built " __DATE__ " " __TIME__;
 }
 
 const char *mpc_lqr_last_error(void) { return g_last_error.c_str(); }
@@ -623,6 +623,35 @@ int mpc_env_linearize(const mpc_env_dynamics *env, int dtype, int64_t N, const v
     EnvDesc<double> e;
     set_env(e, env);
     return launch_env_linearize<double>(e, (long)N, (const double *)x, (const double *)u, (double *)F, (double *)f, st);
+}
+
+int64_t mpc_env_param_grad_workspace_bytes(int64_t N) { return env_param_grad_workspace_bytes(N < 0 ? 0 : N); }
+
+int mpc_env_param_grad(const mpc_env_dynamics *env, int dtype, int64_t N, const void *x, const void *u, const void *gF,
+                       const void *gf, void *gparams, void *workspace, int64_t workspace_bytes, void *stream)
+{
+    if (!env) return fail(MPC_E_NULL, "simulator is NULL");
+    if (dtype != MPC_F32 && dtype != MPC_F64) return fail(MPC_E_DTYPE, "bad dtype");
+    if (env->kind < MPC_ENV_PENDULUM || env->kind > MPC_ENV_CARTPOLE) return fail(MPC_E_ARG, "unknown simulator kind");
+    int rc = check_env(env, env_ns(env->kind), 1);
+    if (rc) return rc;
+    if (N < 0) return fail(MPC_E_DIMS, "N < 0");
+    if (N == 0) return MPC_OK;
+    if (!x || !u || !gF || !gf || !gparams || !workspace) return fail(MPC_E_NULL, "env_param_grad: NULL argument");
+    if (workspace_bytes < env_param_grad_workspace_bytes(N))
+        return fail(MPC_E_DIMS, "workspace too small (see mpc_env_param_grad_workspace_bytes)");
+    if ((uintptr_t)workspace % 8) return fail(MPC_E_ARG, "env_param_grad: the workspace must be 8-byte aligned");
+    hipStream_t st = (hipStream_t)stream;
+    if (dtype == MPC_F32) {
+        EnvDesc<float> e;
+        set_env(e, env);
+        return launch_env_param_grad<float>(e, (long)N, (const float *)x, (const float *)u, (const float *)gF, (const float *)gf,
+                                            (float *)gparams, (double *)workspace, st);
+    }
+    EnvDesc<double> e;
+    set_env(e, env);
+    return launch_env_param_grad<double>(e, (long)N, (const double *)x, (const double *)u, (const double *)gF, (const double *)gf,
+                                         (double *)gparams, (double *)workspace, st);
 }
 
 int64_t mpc_mlp_workspace_bytes(const mpc_mlp_dynamics *net)

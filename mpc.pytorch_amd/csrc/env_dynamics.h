@@ -113,6 +113,10 @@ MPC_HD void rotate_direction(real c, real s, real delta, real &c2, real &s2)
     s2 = su * cd + cu * sd;
 }
 
+// "the caller passed a Jacobian buffer".  A function so that a number type can answer at compile time (env_param_grad.h:
+// its instantiation always wants J, and a run-time test of a private-memory pointer keeps the buffer out of registers).
+template <typename real> MPC_HD bool env_wants_jacobian(const real *J) { return J != nullptr; }
+
 // One transition x+ = env(x,u).  If J != nullptr also d x+ / d [x;u], row-major [ns][ns+1].
 // The control passes through clamp(u, -u_max, u_max) (pendulum.py:66, cartpole.py:73); its
 // derivative is 1 on the closed interval, as torch.clamp's.
@@ -138,7 +142,7 @@ MPC_HD void env_step(const EnvDesc<real> &e, const real *x, real u, real *out, r
         out[2] = c2;
         out[3] = s2;
         out[4] = w + dt * ta;
-        if (J) {
+        if (env_wants_jacobian(J)) {
             const real ir2 = env_inv(c * c + s * s);
             const real th_c = -s * ir2, th_s = c * ir2;
             // columns: 0 x, 1 v, 2 c, 3 s, 4 w, 5 u
@@ -185,7 +189,7 @@ MPC_HD void env_step(const EnvDesc<real> &e, const real *x, real u, real *out, r
     out[0] = c2;
     out[1] = s2;
     out[2] = w2;
-    if (J) {
+    if (env_wants_jacobian(J)) {
         const real ir2 = env_inv(c * c + s * s);
         const real th_c = -s * ir2, th_s = c * ir2;
         real w_c, w_s;

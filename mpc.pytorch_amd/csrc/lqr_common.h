@@ -37,6 +37,11 @@ template <typename real> int launch_select_best(int B, int T, int ns, int nc, in
 template <typename real> int launch_du_norm_reference(int T, int B, int nc, const real *u, const real *new_u, real *out, hipStream_t st);
 template <typename real> int launch_env_linearize(const EnvDesc<real> &env, long N, const real *x, const real *u,
                                                   real *F, real *f, hipStream_t st);
+// its backward with respect to the simulator's parameters (env_param_grad.hip): gparams [env_np(kind)], ws = workspace of
+// env_param_grad_workspace_bytes(N) bytes, 8-byte aligned
+int64_t env_param_grad_workspace_bytes(int64_t N);
+template <typename real> int launch_env_param_grad(const EnvDesc<real> &env, long N, const real *x, const real *u,
+                                                   const real *gF, const real *gf, real *gparams, double *ws, hipStream_t st);
 size_t generic_lds_bytes(int ns, int nc, size_t elem);
 
 // 4-problems-per-wave DPP path for n_state = 12, n_ctrl = 4, f32 (lqr_dpp16.hip)

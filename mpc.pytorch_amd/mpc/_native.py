@@ -61,6 +61,7 @@ class EnvSpec:
         self.linearize = bool(linearize)     # the step kernel linearises the simulator itself (F, f not passed)
         self.n_state = 5 if self.kind == ENV_CARTPOLE else 3
         self.n_ctrl = 1
+        self.n_params = {ENV_PENDULUM: 3, ENV_PENDULUM_FULL: 5}.get(self.kind, 4)
 
     def to_struct(self, like):
         prm = _device_copy_of(self.params, like.device, like.dtype)
@@ -186,6 +187,7 @@ class Outputs(ctypes.Structure):
 EXPORTS = ("mpc_lqr_abi_version", "mpc_lqr_build_info", "mpc_lqr_last_error", "mpc_lqr_workspace_bytes",
            "mpc_lqr_step", "mpc_lqr_impl_supported", "mpc_lqr_qp_record", "mpc_lqr_sweep", "mpc_lqr_rollout", "mpc_lqr_kkt_grads", "mpc_lqr_kkt_prepare",
            "mpc_pnqp", "mpc_pnqp_lu", "mpc_traj_cost", "mpc_env_traj_cost", "mpc_env_linearize", "mpc_select_best",
+           "mpc_env_param_grad_workspace_bytes", "mpc_env_param_grad",
            "mpc_mlp_workspace_bytes", "mpc_mlp_rollout", "mpc_mlp_linearize",
            "mpc_mlp_supported", "mpc_lqr_kkt_fused_supported", "mpc_lqr_kkt_fused_workspace_bytes", "mpc_lqr_kkt_fused",
            "mpc_du_norm_reference")
@@ -236,6 +238,9 @@ def load():
     L.mpc_traj_cost.argtypes = [PP, _vp, _vp, _vp]
     L.mpc_env_traj_cost.argtypes = [PP, ctypes.POINTER(EnvDynamics), _vp, _vp, _vp]
     L.mpc_env_linearize.argtypes = [ctypes.POINTER(EnvDynamics), ctypes.c_int, _i64, _vp, _vp, _vp, _vp, _vp]
+    L.mpc_env_param_grad_workspace_bytes.restype = _i64
+    L.mpc_env_param_grad_workspace_bytes.argtypes = [_i64]
+    L.mpc_env_param_grad.argtypes = [ctypes.POINTER(EnvDynamics), ctypes.c_int, _i64] + [_vp] * 6 + [_i64, _vp]
     L.mpc_select_best.argtypes = [ctypes.c_int] * 6 + [_f64] + [_vp] * 10 + [ctypes.c_int32, _vp, _vp]
     MP = ctypes.POINTER(MlpDynamics)
     L.mpc_mlp_workspace_bytes.restype = _i64
@@ -371,6 +376,7 @@ class HipBackend:
     """Tensor-level front of the C ABI.  All methods enqueue on torch's current stream."""
 
     name = "hip-gfx950"
+    device_only = True      # every call wants ROCm device tensors (a caller that may also hold host tensors asks before routing here)
 
     # -- helpers -------------------------------------------------------------------------------
     @staticmethod
@@ -818,6 +824,27 @@ class HipBackend:
                                    F.data_ptr(), f.data_ptr(), _stream(dev)), "mpc_env_linearize")
         return F, f
 
+    def env_linearize_backward(self, env, x, u, gF, gf):
+        """The backward of `env_linearize` with respect to the simulator's parameters: x [N,ns], u [N,1] (constants) and the
+        cotangents gF [N,ns,ns+1], gf [N,ns] of (F, f) -> gparams [env.n_params] on the device, in the dtype of x
+        (mpc_env_param_grad: one kernel over the points, sums in double, bitwise reproducible)."""
+        dev = _require_device(x, u, gF, gf)
+        L = load()
+        N, ns = x.shape
+        kw = dict(device=dev, dtype=x.dtype)
+        x = x.detach().contiguous(); u = u.detach().contiguous()
+        gF = gF.detach().to(x.dtype).contiguous(); gf = gf.detach().to(x.dtype).contiguous()
+        assert u.numel() == N and gF.numel() == N * ns * (ns + 1) and gf.numel() == N * ns
+        if N == 0:
+            return torch.zeros(env.n_params, **kw)
+        out = torch.empty(env.n_params, **kw)
+        nbytes = int(L.mpc_env_param_grad_workspace_bytes(N))
+        ws = torch.empty(nbytes, device=dev, dtype=torch.uint8)
+        e, prm = env.to_struct(x)
+        _check(L.mpc_env_param_grad(ctypes.byref(e), _dtype_code(x), N, x.data_ptr(), u.data_ptr(), gF.data_ptr(), gf.data_ptr(),
+                                    out.data_ptr(), ws.data_ptr(), nbytes, _stream(dev)), "mpc_env_param_grad")
+        return out
+
     # -- (6d) NNDynamics in the kernels --------------------------------------------------------
     def mlp_rollout(self, x_init, C, c, K, k, cur_x, cur_u, old_costs, opts, net, out_x=None, out_u=None):
         """lqr_forward with the network as true_dynamics (mpc/lqr_step.py:164-261): gains K, k and the nominal's
@@ -1035,6 +1062,29 @@ class HipBackend:
         """The 16-byte device block mpc_select_best reports in, as its two views (int32 word, real maximum)."""
         blk = torch.empty(16, dtype=torch.uint8, device=device)
         return blk[0:4].view(torch.int32), blk[8:8 + torch.empty(0, dtype=dtype).element_size()].view(dtype)
+
+
+class EnvLinearizeFn(torch.autograd.Function):
+    """(F, f) = linearisation of a shipped simulator at N points, differentiable in the simulator's parameters:
+    forward = backend().env_linearize, backward = backend().env_linearize_backward (one kernel each).  `params` is the
+    caller's tensor (`env.params`, usually on the host): its gradient comes back in its dtype and on its device.  x and u
+    are constants (MPC.linearize_dynamics hands in detached leaves, mpc/mpc.py:495-497); the backward is not itself
+    differentiable."""
+
+    @staticmethod
+    def forward(ctx, params, env, x, u):
+        be = backend()
+        F, f = be.env_linearize(env, x, u)
+        ctx.be, ctx.env, ctx.like = be, env, params
+        ctx.save_for_backward(x, u)
+        return F, f
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, gF, gf):
+        x, u = ctx.saved_tensors
+        g = ctx.be.env_linearize_backward(ctx.env, x, u, gF, gf)
+        return g.to(device=ctx.like.device, dtype=ctx.like.dtype).view(ctx.like.shape), None, None, None
 
 
 _backend = None

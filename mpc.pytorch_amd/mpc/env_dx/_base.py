@@ -38,10 +38,24 @@ class SimulatorDx(nn.Module):
         """EnvSpec for the kernels (include/mpc_lqr.h: mpc_env_dynamics)."""
         return _native.EnvSpec(self._kind, self.params, self.dt, self._u_max)
 
+    def native_param_grad(self):
+        """EnvSpec for the differentiable linearisation on the kernels (_native.EnvLinearizeFn: the gradient of F, f with
+        respect to `params` from mpc_env_param_grad), or None when the kernels would not compute what this module does:
+        they rebuild the transition from kind / params / dt / u_max, so a subclass that overrides `forward` or
+        `_transition`, a registered forward hook, or a hidden `native_env` keep the module path (as NNDynamics.native_net)."""
+        shipped = next((c for c in type(self).__mro__ if c.__module__.startswith(__package__ + ".") and "_transition" in vars(c)), None)
+        if shipped is None or type(self)._transition is not shipped._transition or type(self).forward is not SimulatorDx.forward:
+            return None
+        if self._forward_hooks or self._forward_pre_hooks:
+            return None
+        env = getattr(self, "native_env", None)
+        return env() if callable(env) else None
+
     def grad_input(self, x, u):
         """R = d f/dx [N,ns,ns], S = d f/du [N,ns,1] at N points, closed form, one kernel
         (what GradMethods.ANALYTIC asks of a dynamics module, mpc/mpc.py:504).  Not differentiable
-        w.r.t. the parameters -- use GradMethods.AUTO_DIFF when learning them."""
+        w.r.t. the parameters: to learn them use GradMethods.AUTO_DIFF, whose differentiable linearisation of a shipped
+        simulator is a pair of kernels (_native.EnvLinearizeFn)."""
         F, _ = _native.backend().env_linearize(self.native_env(), x, u)
         ns = self.n_state
         return F[:, :, :ns], F[:, :, ns:]

@@ -48,6 +48,19 @@ def _any_requires_grad(obj):
     return False
 
 
+def _only_params_require_grad(dx):
+    """Is `dx.params` the one tensor of the module (searched like _any_requires_grad) that asks for a gradient?"""
+    prm = getattr(dx, "params", None)
+    if not (torch.is_tensor(prm) and prm.requires_grad):
+        return False
+    for m in dx.modules():
+        for v in list(m.parameters(recurse=False)) + list(vars(m).values()):
+            for t in (v if isinstance(v, (list, tuple)) else (v,)):
+                if torch.is_tensor(t) and t.requires_grad and t is not prm:
+                    return False
+    return True
+
+
 _PINNED = collections.OrderedDict()     # (device, stream, host thread) -> [pinned block, its int32 view, tag counter]; LRU, see _FlagReader
 _PINNED_MAX = 64                         # a thread-per-request server would otherwise page-lock a block per thread for ever (ADVICE r04)
 
@@ -583,6 +596,19 @@ class MPC(Module):
                 return hessians.detach(), grads.detach(), costs.detach()
             return hessians, grads, costs
 
+    def _param_grad_env(self, dynamics, x):
+        """The EnvSpec of `dynamics` when its differentiable linearisation (GradMethods.AUTO_DIFF, diff=True) runs as
+        _native.EnvLinearizeFn, else None (the module path through torch): a shipped simulator as it came (SimulatorDx.
+        native_param_grad), `params` its only tensor that asks for a gradient, T > 1, float32 / float64, and a backend that has the
+        backward (and, when it takes device tensors only, a trajectory on the device)."""
+        be = _native.backend()
+        fn = getattr(dynamics, "native_param_grad", None)
+        if (fn is None or self.T <= 1 or not isinstance(dynamics, Module) or not hasattr(be, "env_linearize_backward")
+                or x.dtype not in (torch.float32, torch.float64) or (getattr(be, "device_only", False) and not x.is_cuda)
+                or not _only_params_require_grad(dynamics)):
+            return None
+        return fn()
+
     def linearize_dynamics(self, x, u, dynamics, diff):
         """F_t = [df/dx | df/du], f_t = f(x_t,u_t) - F_t [x_t;u_t] along the trajectory
         (mpc/mpc.py:490-601).  ANALYTIC uses the module's grad_input over all (T-1)*B points at
@@ -608,6 +634,14 @@ class MPC(Module):
             F = torch.cat((R.reshape(T - 1, B, ns, ns), S.reshape(T - 1, B, ns, nc)), 3)
             return F, f
         if self.grad_method == GradMethods.AUTO_DIFF:
+            env = self._param_grad_env(dynamics, x) if diff else None
+            if env is not None:
+                # a shipped simulator whose parameters are being learned: closed-form kernel forward, its parameter
+                # gradient kernel backward (x, u constants as below) -- not n_state double-backward passes through torch
+                with torch.enable_grad():
+                    Fl, fl = _native.EnvLinearizeFn.apply(dynamics.params, env, x[:-1].reshape(-1, ns).detach(),
+                                                          u[:-1].reshape(-1, nc).detach())
+                return Fl.view(T - 1, B, ns, ns + nc), fl.view(T - 1, B, ns)
             with torch.enable_grad():
                 xt = x[:-1].reshape(-1, ns).detach().requires_grad_(True)
                 ut = u[:-1].reshape(-1, nc).detach().requires_grad_(True)
