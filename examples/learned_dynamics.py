@@ -4,7 +4,10 @@ is trained so that MPC on the NETWORK reproduces the controls an expert computes
 is on the controller's output, the gradient reaches the network's weights through the KKT backward of the LQR step.
 
 Every MPC.forward here runs the network inside the kernels (trajectory, analytic linearisation, line-searched
-rollout: csrc/nn_dynamics.hip); only the last, differentiable linearisation of a solve goes through autograd.
+rollout: csrc/nn_dynamics.hip).  The last, differentiable linearisation of a solve goes through the module and autograd by
+default; a controller built with `weight_grad_kernel=True` runs it as a kernel pair instead -- the same linearisation
+kernel forward, the weight-gradient kernel backward (csrc/nn_param_grad.h, _native.MlpLinearizeFn).  An opt-in because it
+is faster than the module route at (12, 4, [100]) and slower at (32, 8, [100]): docs/history/r10.md.
 
     python examples/learned_dynamics.py [n_batch] [epochs]"""
 import os

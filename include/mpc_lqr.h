@@ -322,9 +322,12 @@ typedef struct mpc_mlp_dynamics {
     const void *b[MPC_MLP_MAX_LAYERS];
 } mpc_mlp_dynamics;
 
-/* Which of the two calls below take this network at these sizes (widths and the 160 KiB of LDS the staged kernels work
- * in; pointers are not looked at): bit 0 = mpc_mlp_rollout, bit 1 = mpc_mlp_linearize.  0 = neither (the caller keeps
- * calling the module itself). */
+/* Which of the calls below take this network at these sizes (widths and the 160 KiB of LDS the staged kernels work
+ * in; pointers are not looked at): bit 0 = mpc_mlp_rollout, bit 1 = mpc_mlp_linearize, bit 2 = mpc_mlp_param_grad (also
+ * looks at `activation` and `ctrl_carry`, and is answered for a complete description only: every W[l], b[l] of the
+ * layers non-NULL.  A probe by widths alone keeps answering in bits 0 and 1, so a caller older than bit 2 that compares
+ * such a probe with == 3 is not disturbed).  A clear bit = the caller keeps calling the module itself for that step.
+ * A caller that asks "rollout and linearisation" masks: (mpc_mlp_supported(...) & 3) == 3. */
 int mpc_mlp_supported(const mpc_mlp_dynamics *net, int n_state, int n_ctrl);
 
 /* device scratch (16-byte aligned) the two calls below need for the re-packed weights */
@@ -348,6 +351,35 @@ int mpc_mlp_rollout(const mpc_lqr_problem *p, const mpc_lqr_options *o, const mp
  *      mpc/dynamics.py:82-128) at N points x [N,ns], u [N,nc]: F [N,ns,ns+nc], f [N,ns] = net(x,u) - F [x;u]. */
 int mpc_mlp_linearize(const mpc_mlp_dynamics *net, int n_state, int n_ctrl, int64_t N, const void *x, const void *u,
                       void *F, void *f, void *workspace, int64_t workspace_bytes, void *stream);
+
+/*      The backward of mpc_mlp_linearize with respect to the network's weights and biases -- what makes a solve through a
+ *      trainable NNDynamics trainable on the device (GradMethods.ANALYTIC with diff=True, mpc/mpc.py:625-635).  With x, u
+ *      constants and cotangents gF [N,ns,ns+nc], gf [N,ns] of F, f, and tau = [x;u], a_0 = tau, h_l = W_l a_{l-1} + b_l,
+ *      a_l = act(h_l), s_l = act'(h_l), P_0 = I, M_l = W_l P_{l-1}, P_l = diag(s_l) M_l (layers l = 1..L):
+ *          G = gF - gf tau'   (the passthrough identity is a constant),   ch_L = gf,   cM_L = G
+ *          gW_l += cM_l P_{l-1}' + ch_l a_{l-1}',   gb_l += ch_l,   cP_{l-1} = W_l' cM_l,   ca_{l-1} = W_l' ch_l
+ *          ch_l = s_l . ca_l + act''(h_l) . rowsum(cP_l . M_l),   cM_l = diag(s_l) cP_l          (l < L)
+ *      summed over the N points.  out->gW[l] / out->gb[l], l < n_layers: float32 device buffers in nn.Linear's own layouts
+ *      ([widths[l+1]][widths[l]], [widths[l+1]]); entries l >= n_layers are not looked at.
+ *      Sixteen points per wavefront on fp32 MFMA; a wavefront keeps its gW tiles in registers across its grid-stride loop,
+ *      a block writes one partial into the workspace and a second launch adds the partials in block order.  No atomics: the
+ *      result is bitwise reproducible and depends on the prior contents of neither the outputs nor the workspace.
+ *      At most MPC_MLP_PARAM_GRAD_MAX_BLOCKS blocks of at most 4 wavefronts: one pass of the grid covers at most
+ *      MPC_MLP_PARAM_GRAD_MAX_BLOCKS * 64 points.
+ *      workspace: mpc_mlp_param_grad_workspace_bytes(net, N) bytes (non-decreasing in N; -1 when bit 2 of
+ *      mpc_mlp_supported is clear), 16-byte aligned; it includes the re-packed weights.
+ *      Codes as mpc_mlp_linearize (n_state / n_ctrl / N out of range MPC_E_DIMS, a NULL argument MPC_E_NULL); a shorter
+ *      workspace, ctrl_carry != 0, MPC_ACT_ELU and a network bit 2 does not cover are MPC_E_DIMS with a message.
+ *      N = 0 succeeds and writes zeros (x, u, gF, gf may then be NULL). */
+#define MPC_MLP_PARAM_GRAD_MAX_BLOCKS 256
+typedef struct mpc_mlp_param_grads {
+    void *gW[MPC_MLP_MAX_LAYERS];
+    void *gb[MPC_MLP_MAX_LAYERS];
+} mpc_mlp_param_grads;
+int64_t mpc_mlp_param_grad_workspace_bytes(const mpc_mlp_dynamics *net, int64_t N);
+int mpc_mlp_param_grad(const mpc_mlp_dynamics *net, int n_state, int n_ctrl, int64_t N, const void *x, const void *u,
+                       const void *gF, const void *gf, const mpc_mlp_param_grads *out, void *workspace,
+                       int64_t workspace_bytes, void *stream);
 
 /* (7) Device-side pieces of the iLQR driver loop (mpc/mpc.py:271-285, 299):
  *     per-problem best-iterate select without host round trips, ONE launch.

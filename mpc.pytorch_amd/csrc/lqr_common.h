@@ -119,6 +119,10 @@ int nn_budget(const mpc_mlp_dynamics *net, int ns, int nc);     // bit 0: the ro
 int launch_nn_rollout(const StepParams<float> &p, const mpc_mlp_dynamics *net, void *workspace, int64_t bytes, hipStream_t st);
 int launch_nn_linearize(const mpc_mlp_dynamics *net, long N, int ns, int nc, const float *x, const float *u, float *F,
                         float *f, void *workspace, int64_t bytes, hipStream_t st);
+// ... and the linearisation's weight gradient (nn_param_grad.h); nn_budget bit 2 says whether it takes the network
+int64_t nn_param_grad_workspace_bytes(const mpc_mlp_dynamics *net, int64_t N);     // -1: outside the kernel
+int launch_nn_param_grad(const mpc_mlp_dynamics *net, long N, int ns, int nc, const float *x, const float *u, const float *gF,
+                         const float *gf, const mpc_mlp_param_grads *out, void *workspace, int64_t bytes, hipStream_t st);
 
 // fused MFMA path for n <= 16, f32 (lqr_mfma16.hip)
 bool mfma16_supported(const StepParams<float> &p);

@@ -1007,11 +1007,15 @@ template <typename K> void allow_lds(K kernel, size_t lds)
         (void)hipFuncSetAttribute(reinterpret_cast<const void *>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
 }
 
+#include "nn_param_grad.h"
+
 }  // namespace
 
 // Does the general (LDS-staged) kernel of either entry point fit a network of these layer widths?  The same two budget
 // tests the launchers below apply -- exported as mpc_mlp_supported so that a caller can ask BEFORE it routes a module here
-// (a 1024-unit layer is a legal NNDynamics, it just keeps the host-driven path).  bit 0: rollout, bit 1: linearisation.
+// (a 1024-unit layer is a legal NNDynamics, it just keeps the host-driven path).  bit 0: rollout, bit 1: linearisation,
+// bit 2: the linearisation's weight gradient (nn_param_grad.h: sigmoid / relu, no ctrl_carry, at most PG_MAX_TILES tiles of gW,
+// one point's matrices in LDS).
 int nn_budget(const mpc_mlp_dynamics *net, int ns, int nc)
 {
     if (!net || net->n_layers < 1 || net->n_layers > MPC_MLP_MAX_LAYERS || ns < 1 || ns > 32 || nc < 1) return 0;
@@ -1031,7 +1035,13 @@ int nn_budget(const mpc_mlp_dynamics *net, int ns, int nc)
     const size_t lin = (size_t)(16 * TS + (L > 1 ? L - 1 : 1) * 16 * ZS + 2 * GT * 64 * 4) * 4;
     auto fits = [&](size_t per_wave) { return (wbytes <= WEIGHTS_IN_LDS_MAX && wbytes + per_wave <= LDS_MAX) || per_wave <= LDS_MAX; };
     const bool fast = L == 2 && wp[0] == 16 && wp[1] <= 128;          // the register-resident kernels: no staging at all
-    return ((fast || fits(roll)) ? 1 : 0) | ((fast || fits(lin)) ? 2 : 0);
+    // bit 2 is answered for a complete description only (weights and biases non-NULL): a probe by widths alone, which is all
+    // that bits 0 and 1 need and what callers older than this bit compare with == 3, keeps its answer
+    PgPlan pl;
+    bool grad = (net->activation == MPC_ACT_SIGMOID || net->activation == MPC_ACT_RELU) && net->ctrl_carry == 0;
+    for (int l = 0; l < L; ++l) grad = grad && net->W[l] && net->b[l];
+    grad = grad && pg_plan(net->widths, L, ns, nc, pl);
+    return ((fast || fits(roll)) ? 1 : 0) | ((fast || fits(lin)) ? 2 : 0) | (grad ? 4 : 0);
 }
 
 int launch_nn_rollout(const StepParams<float> &p, const mpc_mlp_dynamics *net, void *workspace, int64_t bytes, hipStream_t st)
@@ -1146,6 +1156,71 @@ int launch_nn_linearize(const mpc_mlp_dynamics *net, long N, int ns, int nc, con
         hipLaunchKernelGGL(nn_linearize_kernel<false>, dim3(grid), dim3(64 * nw), lds, st, d, N, ns, nc, x, u, F, f, TS, ZS, GT, wave_floats);
     }
     return check_launch("nn_linearize_kernel");
+}
+
+// workspace of launch_nn_param_grad: the packed network, then one partial per block.  -1: the network is outside the kernel.
+int64_t nn_param_grad_workspace_bytes(const mpc_mlp_dynamics *net, int64_t N)
+{
+    if (!net || net->n_layers < 1 || net->n_layers > MPC_MLP_MAX_LAYERS) return -1;
+    const int ns = net->widths[net->n_layers], nc = net->widths[0] - ns;
+    if (!(nn_budget(net, ns, nc) & 4)) return -1;
+    PgPlan pl;
+    pg_plan(net->widths, net->n_layers, ns, nc, pl);
+    const int64_t packed = (mpc_mlp_workspace_bytes(net) + 255) & ~(int64_t)255;
+    const int blocks = pg_blocks(N < 0 ? 0 : (long)N, pl.nw);
+    return packed + (int64_t)(blocks > 0 ? blocks : 1) * pl.g.psize * 4;
+}
+
+int launch_nn_param_grad(const mpc_mlp_dynamics *net, long N, int ns, int nc, const float *x, const float *u, const float *gF,
+                         const float *gf, const mpc_mlp_param_grads *out, void *workspace, int64_t bytes, hipStream_t st)
+{
+    if (!net) { set_last_error("network is NULL"); return MPC_E_NULL; }
+    if (net->ctrl_carry) { set_last_error("mlp_param_grad: ctrl_carry describes a rollout only (differentiate the network itself)"); return MPC_E_DIMS; }
+    if (net->activation == MPC_ACT_ELU) { set_last_error("mlp_param_grad: sigmoid and relu only (an ELU network keeps the module path)"); return MPC_E_DIMS; }
+    if (net->n_layers < 1 || net->n_layers > MPC_MLP_MAX_LAYERS) { set_last_error("network: 1..4 Linear layers"); return MPC_E_ARG; }
+    if (net->activation < MPC_ACT_SIGMOID || net->activation > MPC_ACT_ELU) { set_last_error("network: unknown activation"); return MPC_E_ARG; }
+    if (net->widths[0] != ns + nc || net->widths[net->n_layers] != ns) { set_last_error("network: widths[0] must be n_state + n_ctrl, widths[L] n_state"); return MPC_E_DIMS; }
+    const int64_t need = nn_param_grad_workspace_bytes(net, N);
+    if (need < 0) { set_last_error("mlp_param_grad: the network is outside the kernel (see mpc_mlp_supported, bit 2)"); return MPC_E_DIMS; }
+    if (bytes < need) { set_last_error("mlp_param_grad: workspace too small (see mpc_mlp_param_grad_workspace_bytes)"); return MPC_E_DIMS; }
+    MlpDesc d;
+    int rc = mlp_prepare(net, ns, nc, workspace, bytes, d, st);
+    if (rc) return rc;
+    PgPlan pl;
+    pg_plan(net->widths, d.L, ns, nc, pl);
+    const int64_t packed = (mpc_mlp_workspace_bytes(net) + 255) & ~(int64_t)255;
+    float *partials = reinterpret_cast<float *>(static_cast<char *>(workspace) + packed);
+    const int blocks = pg_blocks(N, pl.nw);
+    if (blocks > 0) {
+#define MPC_NN_PG(WL_, MAXT_)                                                                                                       \
+        do {                                                                                                                        \
+            allow_lds(&nn_param_grad_kernel<WL_, MAXT_>, pl.lds);                                                                   \
+            hipLaunchKernelGGL((nn_param_grad_kernel<WL_, MAXT_>), dim3(blocks), dim3(64 * pl.nw), pl.lds, st, d, pl.g, N, ns, nc, x, u, \
+                               gF, gf, partials, pl.TS, pl.ZS, pl.wave_floats);                                                     \
+        } while (0)
+        if (pl.g.ntiles <= 16) { if (pl.wl) MPC_NN_PG(true, 16); else MPC_NN_PG(false, 16); }
+        else { if (pl.wl) MPC_NN_PG(true, PG_MAX_TILES); else MPC_NN_PG(false, PG_MAX_TILES); }
+#undef MPC_NN_PG
+        rc = check_launch("nn_param_grad_kernel");
+        if (rc) return rc;
+    }
+    PgFinalArgs a;
+    a.L = d.L;
+    a.ntiles = pl.g.ntiles;
+    a.psize = pl.g.psize;
+    a.nparts = blocks;
+    a.partials = partials;
+    long entries = 0;
+    for (int l = 0; l <= d.L; ++l) { a.w[l] = d.w[l]; a.wp[l] = d.wp[l]; }
+    for (int k = 0; k < MPC_MLP_MAX_LAYERS; ++k) {
+        a.tbase[k] = k < d.L ? pl.g.tbase[k] : 0;
+        a.gboff[k] = k < d.L ? pl.g.gboff[k] : 0;
+        a.gW[k] = k < d.L ? (float *)out->gW[k] : nullptr;
+        a.gb[k] = k < d.L ? (float *)out->gb[k] : nullptr;
+        if (k < d.L) entries += (long)d.w[k + 1] * d.w[k] + d.w[k + 1];
+    }
+    hipLaunchKernelGGL(nn_param_grad_final_kernel, dim3((unsigned)((entries + 255) / 256)), dim3(256), 0, st, a);
+    return check_launch("nn_param_grad_final_kernel");
 }
 
 }  // namespace mpclqr

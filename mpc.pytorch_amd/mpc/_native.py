@@ -111,6 +111,10 @@ class MlpDynamics(ctypes.Structure):          # struct mpc_mlp_dynamics
                 ("widths", _i32 * (MLP_MAX_LAYERS + 1)), ("W", _vp * MLP_MAX_LAYERS), ("b", _vp * MLP_MAX_LAYERS)]
 
 
+class MlpParamGrads(ctypes.Structure):       # struct mpc_mlp_param_grads
+    _fields_ = [("gW", _vp * MLP_MAX_LAYERS), ("gb", _vp * MLP_MAX_LAYERS)]
+
+
 class MlpSpec:
     """What mpc.dynamics.NNDynamics hands to the kernels: its Linear layers' weights and biases (as they are NOW:
     the struct is rebuilt for every call, a training loop changes them between calls), the activation and the
@@ -158,7 +162,19 @@ class MlpSpec:
         for l, w in enumerate(widths):
             e.widths[l] = int(w)
         ns = int(widths[-1])
-        return int(load().mpc_mlp_supported(ctypes.byref(e), ns, int(widths[0]) - ns)) == 3
+        return (int(load().mpc_mlp_supported(ctypes.byref(e), ns, int(widths[0]) - ns)) & 3) == 3
+
+    def param_grad_supported(self):
+        """Bit 2 of mpc_mlp_supported: does mpc_mlp_param_grad (the weight gradient of the linearisation) take this network?
+        The library answers that bit for a complete description only -- activation, ctrl_carry and non-NULL weights."""
+        e = MlpDynamics()
+        e.n_layers, e.activation, e.passthrough = len(self.weights), ACT_CODES[self.activation], int(self.passthrough)
+        e.ctrl_carry = self.ctrl_carry
+        e.widths[0] = self.weights[0].shape[1]
+        for l, (W, b) in enumerate(zip(self.weights, self.biases)):
+            e.widths[l + 1] = W.shape[0]
+            e.W[l], e.b[l] = W.data_ptr() or 16, b.data_ptr() or 16
+        return bool(int(load().mpc_mlp_supported(ctypes.byref(e), self.n_state, self.n_ctrl)) & 4)
 
     def to_struct(self, like):
         e = MlpDynamics()
@@ -189,6 +205,7 @@ EXPORTS = ("mpc_lqr_abi_version", "mpc_lqr_build_info", "mpc_lqr_last_error", "m
            "mpc_pnqp", "mpc_pnqp_lu", "mpc_traj_cost", "mpc_env_traj_cost", "mpc_env_linearize", "mpc_select_best",
            "mpc_env_param_grad_workspace_bytes", "mpc_env_param_grad",
            "mpc_mlp_workspace_bytes", "mpc_mlp_rollout", "mpc_mlp_linearize",
+           "mpc_mlp_param_grad_workspace_bytes", "mpc_mlp_param_grad",
            "mpc_mlp_supported", "mpc_lqr_kkt_fused_supported", "mpc_lqr_kkt_fused_workspace_bytes", "mpc_lqr_kkt_fused",
            "mpc_du_norm_reference")
 
@@ -248,6 +265,9 @@ def load():
     L.mpc_mlp_supported.argtypes = [MP, ctypes.c_int, ctypes.c_int]
     L.mpc_mlp_rollout.argtypes = [PP, OP, MP, _vp, _vp, _vp, UP, _vp, _i64, _vp]
     L.mpc_mlp_linearize.argtypes = [MP, ctypes.c_int, ctypes.c_int, _i64, _vp, _vp, _vp, _vp, _vp, _i64, _vp]
+    L.mpc_mlp_param_grad_workspace_bytes.restype = _i64
+    L.mpc_mlp_param_grad_workspace_bytes.argtypes = [MP, _i64]
+    L.mpc_mlp_param_grad.argtypes = [MP, ctypes.c_int, ctypes.c_int, _i64, _vp, _vp, _vp, _vp, ctypes.POINTER(MlpParamGrads), _vp, _i64, _vp]
     if L.mpc_lqr_abi_version() != ABI_VERSION:
         raise RuntimeError("libmpc_lqr_hip ABI version mismatch")
     _lib = L
@@ -915,6 +935,33 @@ class HipBackend:
                                    ws.data_ptr(), nbytes, _stream(dev)), "mpc_mlp_linearize")
         return F, f
 
+    def mlp_linearize_backward(self, net, x, u, gF, gf):
+        """The backward of `mlp_linearize` with respect to the network's weights and biases: x [N,ns], u [N,nc] (constants) and
+        the cotangents gF [N,ns,ns+nc], gf [N,ns] of (F, f) -> [gW_1, gb_1, ..., gW_L, gb_L], float32 on the device, in
+        nn.Linear's layouts (mpc_mlp_param_grad: MFMA over sixteen points per wavefront, one partial per block, a second
+        launch adds them in a fixed order -- bitwise reproducible)."""
+        dev = _require_device(x, u, gF, gf)
+        L = load()
+        N, ns = x.shape
+        nc = u.shape[1]
+        x = x.detach().to(torch.float32).contiguous(); u = u.detach().to(torch.float32).contiguous()
+        gF = gF.detach().to(torch.float32).contiguous(); gf = gf.detach().to(torch.float32).contiguous()
+        assert gF.numel() == N * ns * (ns + nc) and gf.numel() == N * ns
+        e, _, _, keep_e = net.to_struct(x)
+        nbytes = int(L.mpc_mlp_param_grad_workspace_bytes(ctypes.byref(e), N))
+        if nbytes < 0:
+            raise RuntimeError("mpc_mlp_param_grad does not take this network (mpc_mlp_supported, bit 2)")
+        ws = torch.empty(nbytes, device=dev, dtype=torch.uint8)
+        out, grads = MlpParamGrads(), []
+        for l, (W, b) in enumerate(zip(net.weights, net.biases)):
+            gW = torch.empty(tuple(W.shape), device=dev, dtype=torch.float32)
+            gb = torch.empty(tuple(b.shape), device=dev, dtype=torch.float32)
+            out.gW[l], out.gb[l] = gW.data_ptr(), gb.data_ptr()
+            grads += [gW, gb]
+        _check(L.mpc_mlp_param_grad(ctypes.byref(e), ns, nc, N, x.data_ptr(), u.data_ptr(), gF.data_ptr(), gf.data_ptr(),
+                                    ctypes.byref(out), ws.data_ptr(), nbytes, _stream(dev)), "mpc_mlp_param_grad")
+        return grads
+
     def plan_network_iteration(self, x_init, C, c, net, opts, nominals, scratch=None):
         """One iLQR iteration on an NNDynamics network (mpc/mpc.py:245-306 with dx a module: util.get_traj is the previous
         rollout's own new_x, then MPC.linearize_dynamics(ANALYTIC) :495-512, lqr_backward :52-160, lqr_forward through the
@@ -1085,6 +1132,30 @@ class EnvLinearizeFn(torch.autograd.Function):
         x, u = ctx.saved_tensors
         g = ctx.be.env_linearize_backward(ctx.env, x, u, gF, gf)
         return g.to(device=ctx.like.device, dtype=ctx.like.dtype).view(ctx.like.shape), None, None, None
+
+
+class MlpLinearizeFn(torch.autograd.Function):
+    """(F, f) = linearisation of an NNDynamics network at N points, differentiable in the network's weights and biases:
+    forward = backend().mlp_linearize, backward = backend().mlp_linearize_backward.  `params` are the module's own
+    tensors in the order [W_1, b_1, ..., W_L, b_L] (the ones `net` was built from): each gradient comes back in the dtype
+    and on the device of its parameter.  x and u are constants (MPC.linearize_dynamics hands in detached leaves,
+    mpc/mpc.py:495-497); the backward is not itself differentiable."""
+
+    @staticmethod
+    def forward(ctx, net, x, u, *params):
+        be = backend()
+        F, f = be.mlp_linearize(net, x, u)
+        ctx.be, ctx.net, ctx.like = be, net, [(p.device, p.dtype, p.shape) for p in params]
+        ctx.save_for_backward(x, u)
+        return F, f
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, gF, gf):
+        x, u = ctx.saved_tensors
+        grads = ctx.be.mlp_linearize_backward(ctx.net, x, u, gF, gf)
+        assert len(grads) == len(ctx.like)
+        return (None, None, None) + tuple(g.to(device=d, dtype=t).view(s) for g, (d, t, s) in zip(grads, ctx.like))
 
 
 _backend = None

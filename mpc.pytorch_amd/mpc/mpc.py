@@ -174,7 +174,8 @@ class MPC(Module):
                  lqr_iter=10, grad_method=GradMethods.ANALYTIC, delta_u=None, verbose=0, eps=1e-7,
                  back_eps=1e-7, n_batch=None, linesearch_decay=0.2, max_linesearch_iter=10,
                  exit_unconverged=True, detach_unconverged=True, backprop=True, slew_rate_penalty=None,
-                 prev_ctrl=None, not_improved_lim=5, best_cost_eps=1e-4, reference_du_norm=False):
+                 prev_ctrl=None, not_improved_lim=5, best_cost_eps=1e-4, reference_du_norm=False,
+                 weight_grad_kernel=False):
         super().__init__()
         assert (u_lower is None) == (u_upper is None)
         assert max_linesearch_iter > 0
@@ -203,6 +204,10 @@ class MPC(Module):
         # (:321-334) are the reference's.  Default: each problem's own norm.  Costs one more rollout per iteration
         # and takes the general loop (no pre-bound device-side iterations).
         self.reference_du_norm = bool(reference_du_norm)
+        # OPT-IN: the differentiable linearisation of a trainable NNDynamics as _native.MlpLinearizeFn (mpc_mlp_linearize forward,
+        # mpc_mlp_param_grad backward) instead of the module through torch autograd.  Off by default: measured faster than the
+        # module route at (12, 4, [100]) but slower at (32, 8, [100]) (docs/history/r10.md)
+        self.weight_grad_kernel = bool(weight_grad_kernel)
         self.flag_reducer = None     # set by mpc.shard for lock-step sharded solves
         self.prev_ctrl = prev_ctrl
 
@@ -609,6 +614,31 @@ class MPC(Module):
             return None
         return fn()
 
+    def _param_grad_net(self, dynamics, x):
+        """(MlpSpec, [W_1, b_1, ...]) of `dynamics` when its differentiable linearisation (GradMethods.ANALYTIC, diff=True)
+        runs as _native.MlpLinearizeFn, else None (the module path through torch): the controller was built with
+        `weight_grad_kernel=True`, an NNDynamics the kernels take as it came
+        (`native_net`: no overridden forward, no hooks, stock activations, float32 on the device), not ELU, a network
+        mpc_mlp_param_grad covers (mpc_mlp_supported bit 2), T > 1, a backend that has the backward, and the `fcs` weights and
+        biases the module's only tensors that ask for a gradient."""
+        be = _native.backend()
+        if (not self.weight_grad_kernel or self.T <= 1 or not isinstance(dynamics, Module) or not hasattr(dynamics, "native_net") or not hasattr(dynamics, "fcs")
+                or not hasattr(be, "mlp_linearize_backward") or x.dtype != torch.float32):
+            return None
+        net = dynamics.native_net(x)
+        if net is None or net.activation == "elu" or net.ctrl_carry or not net.param_grad_supported():
+            return None
+        params = [t for layer in dynamics.fcs for t in (layer.weight, layer.bias)]
+        if len(params) != 2 * len(net.weights) or any(a is not b for a, b in zip(params[0::2], net.weights)) \
+                or any(a is not b for a, b in zip(params[1::2], net.biases)):
+            return None
+        for m in dynamics.modules():
+            for v in list(m.parameters(recurse=False)) + list(vars(m).values()):
+                for t in (v if isinstance(v, (list, tuple)) else (v,)):
+                    if torch.is_tensor(t) and t.requires_grad and not any(t is p for p in params):
+                        return None
+        return net, params
+
     def linearize_dynamics(self, x, u, dynamics, diff):
         """F_t = [df/dx | df/du], f_t = f(x_t,u_t) - F_t [x_t;u_t] along the trajectory
         (mpc/mpc.py:490-601).  ANALYTIC uses the module's grad_input over all (T-1)*B points at
@@ -621,6 +651,14 @@ class MPC(Module):
                 # NNDynamics: forward, grad_input and the affine term in one kernel, no [N, hidden, n] intermediates
                 # (elu has no grad_input in the reference, mpc/dynamics.py:113-114: left to the module to refuse)
                 Fl, fl = _native.backend().mlp_linearize(net, x[:-1].reshape(-1, ns), u[:-1].reshape(-1, nc))
+                return Fl.view(T - 1, B, ns, ns + nc), fl.view(T - 1, B, ns)
+            routed = self._param_grad_net(dynamics, x) if diff else None
+            if routed is not None:
+                # a trainable NNDynamics: the linearisation kernel forward, its weight-gradient kernel backward (x, u constants
+                # as below) -- not the module over all points with [N, hidden, n] intermediates and an autograd pass through them
+                with torch.enable_grad():
+                    Fl, fl = _native.MlpLinearizeFn.apply(routed[0], x[:-1].reshape(-1, ns).detach(), u[:-1].reshape(-1, nc).detach(),
+                                                          *routed[1])
                 return Fl.view(T - 1, B, ns, ns + nc), fl.view(T - 1, B, ns)
             # fresh leaves, as the reference (mpc/mpc.py:495-497): with diff=True the graph reaches the
             # dynamics' parameters (through new_x, R, S), not the trajectory itself.
