@@ -38,7 +38,8 @@ enum {
     MPC_E_NULL = -2,       /* a required pointer is NULL                  */
     MPC_E_DTYPE = -3,
     MPC_E_LAUNCH = -4,     /* hipLaunch failed; see mpc_lqr_last_error()  */
-    MPC_E_ARG = -5
+    MPC_E_ARG = -5,
+    MPC_E_UNSUPPORTED = -6 /* a valid request no kernel behind this entry / impl serves (MPC_ENV_CTRL_CARRY off the lane-per-problem kernel) */
 };
 /* per-problem status word bits (status[B]) */
 enum {
@@ -71,10 +72,20 @@ enum {
     MPC_ENV_NONE = 0,
     MPC_ENV_PENDULUM = 1,        /* PendulumDx(simple=True):  params (g, m, l),       n_state 3 */
     MPC_ENV_PENDULUM_FULL = 2,   /* PendulumDx(simple=False): params (g, m, l, d, b), n_state 3 */
-    MPC_ENV_CARTPOLE = 3         /* CartpoleDx: params (gravity, masscart, masspole, length), n_state 5 */
+    MPC_ENV_CARTPOLE = 3,        /* CartpoleDx: params (gravity, masscart, masspole, length), n_state 5 */
+    MPC_ENV_CTRL_CARRY = 0x100   /* OR-ed into `kind`: mpc.dynamics.CtrlPassthroughDynamics around the simulator (the slew-rate
+                                    augmentation, mpc/mpc.py:362-445, mpc/dynamics.py:131-150).  The state is z = (previous control,
+                                    x), n_state + 1 numbers; a step returns (this control, env(x, u)) -- the control RAW, the clamp
+                                    stays inside the simulator -- and the Jacobian [ns+1][ns+2] has the carry row (0 .. 0 1), a zero
+                                    column for the previous control and the simulator's own block inside.
+                                    Honoured by mpc_env_traj_cost and by mpc_lqr_step on the lane-per-problem kernel (impl 4; impl 0
+                                    routes every such call there, at every batch size), with or without `linearize`.  REFUSED
+                                    (MPC_E_UNSUPPORTED, mpc_lqr_impl_supported answers 0) by the row-per-problem kernel (impl 6), the
+                                    generic kernels (impl 1, mpc_lqr_sweep, mpc_lqr_rollout), mpc_env_linearize and
+                                    mpc_env_param_grad: the differentiable ending linearises the simulator itself. */
 };
 typedef struct mpc_env_dynamics {
-    int32_t kind;                 /* MPC_ENV_* */
+    int32_t kind;                 /* MPC_ENV_PENDULUM .. MPC_ENV_CARTPOLE, optionally | MPC_ENV_CTRL_CARRY */
     int32_t linearize;            /* 1: mpc_lqr_step takes the sweep's F_t from the simulator's Jacobian at the nominal
                                      (current_x, current_u), computed in the kernel: MPC.linearize_dynamics
                                      (mpc/mpc.py:490-549) fused into the step; p->F, p->f are ignored (may be NULL).
@@ -279,6 +290,21 @@ int mpc_traj_cost(const mpc_lqr_problem *p, void *x, void *cost, void *stream);
  *     p->F/f are ignored (may be NULL), p->C/c optional as in (6). */
 int mpc_env_traj_cost(const mpc_lqr_problem *p, const mpc_env_dynamics *env, void *x, void *cost,
                       void *stream);
+
+/* (6b') The slew-rate augmentation of a QuadCost / LinDx problem (mpc/mpc.py:362-445) in one launch: with na = ns + 2 nc,
+ *     n = ns + nc and the augmented state z_t = (u_{t-1}, x_t),
+ *         aC [.,.,na,na] = slew_C + pad(C)     slew_C = gamma [[I 0 -I], [0 0 0], [-I 0 I]] on (u_prev, x, u)
+ *         ac [.,.,na]    = [0; c]
+ *         aF [.,.,n,na]  = [[0 0 I], [0 F]]    (T - 1 blocks along t)
+ *         af [.,.,n]     = [0; f]              (not touched when p->f is NULL; af may then be NULL)
+ *     Of `p` only B, T, ns, nc, dtype and (C, c, F, f) with their T / B element strides are read.  The outputs are dense in the
+ *     layout of the INPUT's broadcast pattern: an axis the input strides by 0 has extent 1 in the output (the caller sizes
+ *     the buffers accordingly and `.expand()`s them: a shared [n,n] cost becomes ONE shared [na,na] block), every other
+ *     axis its full extent.  The only arithmetic is slew_C + pad(C) -- bitwise what the torch composition gives; +-gamma I and
+ *     the carry identity are stored.  float32 / float64, any n_state, n_ctrl.  gamma is rounded to the problem's dtype.
+ *     F and aF may both be NULL (a simulator carried by MPC_ENV_CTRL_CARRY has no F, f: only the cost is augmented).
+ *     A NULL C / c / aC / ac, or only one of F / aF, is MPC_E_ARG; B = 0 succeeds and writes nothing. */
+int mpc_slew_augment(const mpc_lqr_problem *p, double gamma, void *aC, void *ac, void *aF, void *af, void *stream);
 
 /* (6c) MPC.linearize_dynamics for a shipped simulator (mpc/mpc.py:490-549):
  *     over N = (T-1)*B points (x [N,ns], u [N,1]):  F [N,ns,ns+1] = d env / d [x;u] (exact),

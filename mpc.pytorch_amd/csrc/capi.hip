@@ -94,9 +94,11 @@ static int check_problem(const mpc_lqr_problem *p, bool need_cost, bool need_nom
 
 static int check_env(const mpc_env_dynamics *e, int ns, int nc)
 {
-    if (e->kind < MPC_ENV_PENDULUM || e->kind > MPC_ENV_CARTPOLE) return fail(MPC_E_ARG, "unknown simulator kind");
+    // MPC_ENV_CTRL_CARRY rides in `kind`: the state is (previous control, x), one more than the simulator's own
+    const int kind = e->kind & ~MPC_ENV_CTRL_CARRY, carry = (e->kind & MPC_ENV_CTRL_CARRY) ? 1 : 0;
+    if (kind < MPC_ENV_PENDULUM || kind > MPC_ENV_CARTPOLE) return fail(MPC_E_ARG, "unknown simulator kind");
     if (!e->params) return fail(MPC_E_NULL, "simulator params is NULL");
-    if (nc != 1 || ns != env_ns(e->kind)) return fail(MPC_E_DIMS, "n_state / n_ctrl do not match the simulator");
+    if (nc != 1 || ns != env_ns(kind) + carry) return fail(MPC_E_DIMS, "n_state / n_ctrl do not match the simulator");
     if (!(e->dt > 0) || !(e->u_max >= 0)) return fail(MPC_E_ARG, "simulator dt / u_max");
     return MPC_OK;
 }
@@ -205,6 +207,10 @@ static int step_impl(const mpc_lqr_problem *p, const mpc_lqr_options *o, const m
             return launch_step_generic<real>(sp, 1, st);
         }
     }
+    // MPC_ENV_CTRL_CARRY: the lane-per-problem kernel carries the control (lqr_tiny_body.h); the row-per-problem and the generic
+    // kernels call the simulator as it is and REFUSE the flag -- never a silent un-augmented answer
+    if (sp.env.carry && (phase_mask != 3 || (impl != 0 && impl != 4)))
+        return fail(MPC_E_UNSUPPORTED, "MPC_ENV_CTRL_CARRY: only mpc_lqr_step on the lane-per-problem kernel (impl 0 or 4) carries the control");
     if (sp.env.kind && sp.env.linearize && !(phase_mask == 3 && tiny_supported(p->ns, p->nc) && (impl == 0 || impl == 4 || impl == 6)))
         return fail(MPC_E_ARG, "in-kernel linearisation needs the lane-per-problem kernel (n_ctrl = 1, n_state <= 6)");
     if (sp.env.kind && (impl == 2 || impl == 3 || impl == 8))
@@ -352,7 +358,7 @@ int mpc_lqr_abi_version(void) { return MPC_LQR_ABI_VERSION; }
 const char *mpc_lqr_build_info(void)
 {
     return "libmpc_lqr_hip gfx950 (CDNA4) | kernels: lqr_step_generic<f32,f64>, lqr_step_mfma16<f32,f64>, lqr_step_dpp16<f32>, lqr_step_dpp16_padded<f32>, "
-           "lqr_step_tiny<f32,f64>, lqr_step_wave1<f32>, lqr_step_mfma40<f32>, lqr_step_mfma40_padded<f32>, nn_rollout<f32>, nn_linearize<f32>, nn_param_grad<f32>, env_linearize, env_param_grad<f32,f64>, kkt_grads, kkt_fused<f32>, kkt_fused_padded<f32>, pnqp, traj_cost, select_best | built " __DATE__ " " __TIME__;
+           "lqr_step_tiny<f32,f64>, lqr_step_wave1<f32>, lqr_step_mfma40<f32>, lqr_step_mfma40_padded<f32>, nn_rollout<f32>, nn_linearize<f32>, nn_param_grad<f32>, env_linearize, env_param_grad<f32,f64>, kkt_grads, kkt_fused<f32>, kkt_fused_padded<f32>, pnqp, traj_cost, select_best, slew_augment<f32,f64> | built " __DATE__ " " __TIME__;
 }
 
 const char *mpc_lqr_last_error(void) { return g_last_error.c_str(); }
@@ -381,6 +387,7 @@ int mpc_lqr_step(const mpc_lqr_problem *p, const mpc_lqr_options *o, const mpc_l
 int mpc_lqr_impl_supported(const mpc_lqr_problem *p, const mpc_lqr_options *o, int impl)
 {
     if (!p || check_problem(p, false, false) != MPC_OK || check_options(p, o) != MPC_OK) return 0;
+    if (o && o->true_dynamics && (o->true_dynamics->kind & MPC_ENV_CTRL_CARRY)) return (impl == 4 && tiny_supported(p->ns, p->nc)) ? 1 : 0;
     if (impl == 1) return generic_lds_bytes(p->ns, p->nc, p->dtype == MPC_F64 ? 8 : 4) <= 160 * 1024;
     if (impl == 4) return tiny_supported(p->ns, p->nc) ? 1 : 0;
     if (impl == 6) return (p->dtype == MPC_F32 && tiny_supported(p->ns, p->nc) && wave1_supported(make_params<float>(p, o, nullptr))) ? 1 : 0;
@@ -603,11 +610,29 @@ int mpc_env_traj_cost(const mpc_lqr_problem *p, const mpc_env_dynamics *env, voi
     return launch_traj_cost<double>(sp, (double *)x, (double *)cost, st);
 }
 
+int mpc_slew_augment(const mpc_lqr_problem *p, double gamma, void *aC, void *ac, void *aF, void *af, void *stream)
+{
+    if (!p) return fail(MPC_E_NULL, "problem is NULL");
+    if (p->B < 0 || p->T < 1 || p->ns < 1 || p->nc < 1) return fail(MPC_E_DIMS, "need B>=0, T>=1, ns>=1, nc>=1");
+    if (p->dtype != MPC_F32 && p->dtype != MPC_F64) return fail(MPC_E_DTYPE, "dtype must be MPC_F32 or MPC_F64");
+    if (p->B == 0) return MPC_OK;
+    if (!p->C || !p->c || !aC || !ac) return fail(MPC_E_ARG, "slew_augment: C / c / aC / ac is NULL");
+    // (F NULL: a simulator behind MPC_ENV_CTRL_CARRY has no F, f -- only the cost is augmented)
+    if (p->T > 1 && ((p->F == nullptr) != (aF == nullptr))) return fail(MPC_E_ARG, "slew_augment: F and aF go together");
+    if (p->T > 1 && p->f && (!af || !p->F)) return fail(MPC_E_ARG, "slew_augment: f given but af / F is NULL");
+    if (p->C_st < 0 || p->C_sb < 0 || p->c_st < 0 || p->c_sb < 0 || p->F_st < 0 || p->F_sb < 0 || p->f_st < 0 || p->f_sb < 0)
+        return fail(MPC_E_ARG, "slew_augment: negative stride");
+    hipStream_t st = (hipStream_t)stream;
+    return p->dtype == MPC_F32 ? launch_slew_augment<float>(p, gamma, (float *)aC, (float *)ac, (float *)aF, (float *)af, st)
+                               : launch_slew_augment<double>(p, gamma, (double *)aC, (double *)ac, (double *)aF, (double *)af, st);
+}
+
 int mpc_env_linearize(const mpc_env_dynamics *env, int dtype, int64_t N, const void *x, const void *u, void *F,
                       void *f, void *stream)
 {
     if (!env) return fail(MPC_E_NULL, "simulator is NULL");
     if (dtype != MPC_F32 && dtype != MPC_F64) return fail(MPC_E_DTYPE, "bad dtype");
+    if (env->kind & MPC_ENV_CTRL_CARRY) return fail(MPC_E_UNSUPPORTED, "MPC_ENV_CTRL_CARRY: linearise the simulator itself (the carry block is constant)");
     if (env->kind < MPC_ENV_PENDULUM || env->kind > MPC_ENV_CARTPOLE) return fail(MPC_E_ARG, "unknown simulator kind");
     int rc = check_env(env, env_ns(env->kind), 1);
     if (rc) return rc;
@@ -632,6 +657,7 @@ int mpc_env_param_grad(const mpc_env_dynamics *env, int dtype, int64_t N, const 
 {
     if (!env) return fail(MPC_E_NULL, "simulator is NULL");
     if (dtype != MPC_F32 && dtype != MPC_F64) return fail(MPC_E_DTYPE, "bad dtype");
+    if (env->kind & MPC_ENV_CTRL_CARRY) return fail(MPC_E_UNSUPPORTED, "MPC_ENV_CTRL_CARRY: linearise the simulator itself (the carry block is constant)");
     if (env->kind < MPC_ENV_PENDULUM || env->kind > MPC_ENV_CARTPOLE) return fail(MPC_E_ARG, "unknown simulator kind");
     int rc = check_env(env, env_ns(env->kind), 1);
     if (rc) return rc;

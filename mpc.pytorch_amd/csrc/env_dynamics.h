@@ -22,6 +22,7 @@ template <typename real> struct EnvDesc {
     int linearize;       // sweep model = Jacobian of the simulator at the nominal, computed in the kernel
     const real *params;  // device pointer: pendulum (g,m,l[,d,b]), cartpole (g,mcart,mpole,l)
     real dt, u_max;
+    int carry = 0;       // MPC_ENV_CTRL_CARRY: the state is (previous control, x), a step returns (this control, env(x, u))
 };
 
 MPC_HD int env_ns(int kind) { return kind == MPC_ENV_CARTPOLE ? 5 : 3; }
@@ -200,6 +201,29 @@ MPC_HD void env_step(const EnvDesc<real> &e, const real *x, real u, real *out, r
         J[0] = -s2 * t_c; J[1] = -s2 * t_s; J[2] = -s2 * t_w; J[3] = -s2 * t_u;
         J[4] = c2 * t_c;  J[5] = c2 * t_s;  J[6] = c2 * t_w;  J[7] = c2 * t_u;
         J[8] = w_c;       J[9] = w_s;       J[10] = 1;        J[11] = w_u;
+    }
+}
+
+// The simulator inside the slew-rate augmentation (mpc/mpc.py:362-445, mpc/dynamics.py:131-150: CtrlPassthroughDynamics):
+// z = (u_prev, x) -> (u, env(x, u)), env_ns + 1 states.  `u` is carried RAW, as the reference concatenates it; the clamp
+// lives inside the simulator.  If J != nullptr also d z+ / d [z;u], row-major [ns+1][ns+2]: the carry row is (0 ... 0 1),
+// the u_prev column is zero, the simulator's own block sits inside these.  A wrapper: env_step is not touched.
+template <typename real, int NSE>      // NSE = env_ns(e.kind), a compile-time constant so that out and J stay in registers
+MPC_HD void env_step_carry(const EnvDesc<real> &e, const real *z, real u, real *out, real *J)
+{
+    constexpr int n = NSE + 1, na = NSE + 2;
+    if (!env_wants_jacobian(J)) {
+        env_step<real>(e, z + 1, u, out + 1, nullptr);
+        out[0] = u;
+        return;
+    }
+    real Je[30];
+    env_step<real>(e, z + 1, u, out + 1, Je);
+    out[0] = u;
+    for (int j = 0; j < na; ++j) J[j] = j == na - 1 ? (real)1 : (real)0;
+    for (int r = 0; r < NSE; ++r) {
+        J[(r + 1) * na] = 0;
+        for (int j = 0; j < n; ++j) J[(r + 1) * na + 1 + j] = Je[r * n + j];
     }
 }
 

@@ -43,6 +43,8 @@ int64_t env_param_grad_workspace_bytes(int64_t N);
 template <typename real> int launch_env_param_grad(const EnvDesc<real> &env, long N, const real *x, const real *u,
                                                    const real *gF, const real *gf, real *gparams, double *ws, hipStream_t st);
 size_t generic_lds_bytes(int ns, int nc, size_t elem);
+// the slew-rate augmentation (aC, ac, aF, af) of p's (C, c, F, f) in one launch (slew_augment.hip)
+template <typename real> int launch_slew_augment(const mpc_lqr_problem *p, double gamma, real *aC, real *ac, real *aF, real *af, hipStream_t st);
 
 // 4-problems-per-wave DPP path for n_state = 12, n_ctrl = 4, f32 (lqr_dpp16.hip)
 bool dpp16_supported(const StepParams<float> &p);

@@ -778,7 +778,11 @@ __global__ void __launch_bounds__(MAX_THREADS) traj_cost_kernel(StepParams<real>
             }
         }
         if (t < T - 1 && p.env.kind) {                                 // mpc/util.py:112-113
-            if (tid == 0) env_step<real>(p.env, s.tau, s.tau[ns], s.xn2, nullptr);
+            if (tid == 0) {
+                if (!p.env.carry) env_step<real>(p.env, s.tau, s.tau[ns], s.xn2, nullptr);
+                else if (p.env.kind == MPC_ENV_CARTPOLE) env_step_carry<real, 5>(p.env, s.tau, s.tau[ns], s.xn2, nullptr);
+                else env_step_carry<real, 3>(p.env, s.tau, s.tau[ns], s.xn2, nullptr);
+            }
         } else if (t < T - 1) {
             const real *ft = p.f ? p.f + (long)t * p.f_st + (long)b * p.f_sb : nullptr;
             for (int i = tid; i < ns; i += nt) {
@@ -1121,7 +1125,7 @@ __global__ void __launch_bounds__(64) env_traj_lane_kernel(StepParams<real> p, r
     const int b = blockIdx.x * 64 + threadIdx.x;
     if (b >= p.B) return;
     const int ns = p.ns, T = p.T, B = p.B;
-    real xi[5], xn[5];
+    real xi[6], xn[6];        // (six: a cart-pole behind MPC_ENV_CTRL_CARRY)
     for (int i = 0; i < ns; ++i) {
         xi[i] = p.x_init[(long)b * ns + i];
         x[(long)b * ns + i] = xi[i];
@@ -1129,7 +1133,9 @@ __global__ void __launch_bounds__(64) env_traj_lane_kernel(StepParams<real> p, r
     real u = T > 1 ? p.cur_u[b] : (real)0;
     for (int t = 0; t < T - 1; ++t) {
         const real un = t + 1 < T - 1 ? p.cur_u[(long)(t + 1) * B + b] : (real)0;     // (next step's control in flight)
-        env_step<real>(p.env, xi, u, xn, nullptr);
+        if (!p.env.carry) env_step<real>(p.env, xi, u, xn, nullptr);
+        else if (p.env.kind == MPC_ENV_CARTPOLE) env_step_carry<real, 5>(p.env, xi, u, xn, nullptr);
+        else env_step_carry<real, 3>(p.env, xi, u, xn, nullptr);
         for (int i = 0; i < ns; ++i) {
             xi[i] = xn[i];
             x[((long)(t + 1) * B + b) * ns + i] = xn[i];
@@ -1140,7 +1146,7 @@ __global__ void __launch_bounds__(64) env_traj_lane_kernel(StepParams<real> p, r
 
 template <typename real> int launch_traj_cost(const StepParams<real> &p, real *x, real *cost, hipStream_t st)
 {
-    if (!cost && x && p.env.kind && p.nc == 1 && p.ns <= 5) {
+    if (!cost && x && p.env.kind && p.nc == 1 && p.ns <= 6) {
         hipLaunchKernelGGL(env_traj_lane_kernel<real>, dim3((unsigned)((p.B + 63) / 64)), dim3(64), 0, st, p, x);
         return check_launch("env_traj_lane_kernel");
     }

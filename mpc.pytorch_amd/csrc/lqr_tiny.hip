@@ -1,5 +1,6 @@
 // lqr_tiny.hip -- gfx950 launch of lqr_tiny_body.h: one lane per problem for n_ctrl = 1,
-// n_state <= 6 (pendulum / cart-pole iLQR, their slew-augmented variants).
+// n_state <= 6 (pendulum / cart-pole iLQR, their slew-augmented variants: at n_state 4 / 6 a simulator is carried behind
+// MPC_ENV_CTRL_CARRY, lqr_tiny_body.h env_carries).
 #include "lqr_common.h"
 #include "lqr_tiny_body.h"
 

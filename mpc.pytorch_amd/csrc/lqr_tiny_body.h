@@ -25,6 +25,11 @@ template <typename real> MPC_HD real clampr(real x, real lo, real hi)
 }
 template <typename real> MPC_HD real absr(real x) { return x < 0 ? -x : x; }
 
+// A simulator at n_state = 4 / 6 can only be the slew-rate augmentation of one of the shipped ones (pendulum 3 + 1, cart-pole
+// 5 + 1: MPC_ENV_CTRL_CARRY, the caller's sizes are held to that by capi.hip's check_env), at 3 / 5 only the simulator itself: the
+// instantiation decides, and the un-augmented kernels are the code they were.
+template <int NS> constexpr bool env_carries() { return NS == 4 || NS == 6; }
+
 // pnqp for n = 1 (mpc/pnqp.py:5-82).  Returns the iteration index the reference returns; x in/out,
 // Hfree = the (regularised) free-set Hessian the returned x belongs to, is_free its free flag.
 template <typename real>
@@ -139,8 +144,9 @@ MPC_HD void sweep_problem(const StepParams<real> &p, int b, real *Kw, bool write
         if (t < T - 1) {                               // Q = C + F'VF, q = c_back + F'v (:65-70)
             real F[NS][N];
             if (p.env.kind && p.env.linearize) {       // F_t = d simulator / d [x;u] at the nominal (mpc/mpc.py:490-549)
-                real nxt[NS > 5 ? NS : 5], J[NS * N > 30 ? NS * N : 30];   // (sized for either simulator)
-                env_step<real>(p.env, tau, tau[NS], nxt, J);
+                real nxt[env_carries<NS>() ? 6 : (NS > 5 ? NS : 5)], J[env_carries<NS>() ? 42 : (NS * N > 30 ? NS * N : 30)];   // (sized for either simulator)
+                if constexpr (env_carries<NS>()) env_step_carry<real, NS - 1>(p.env, tau, tau[NS], nxt, J);
+                else env_step<real>(p.env, tau, tau[NS], nxt, J);
                 for (int m = 0; m < NS; ++m)
                     for (int j = 0; j < N; ++j) F[m][j] = J[m * N + j];
             } else {
@@ -299,9 +305,10 @@ MPC_HD void rollout_pass(const StepParams<real> &p, int b, const real *Kw, real 
             ca += (double)((real)0.5 * tau[i] * s + now.c[i] * tau[i]);
         }
         if (t < T - 1) {
-            real xn[NS > 5 ? NS : 5];
+            real xn[env_carries<NS>() ? 6 : (NS > 5 ? NS : 5)];
             if (p.env.kind) {                                               // :223-225
-                env_step<real>(p.env, x, un, xn, nullptr);
+                if constexpr (env_carries<NS>()) env_step_carry<real, NS - 1>(p.env, x, un, xn, nullptr);
+                else env_step<real>(p.env, x, un, xn, nullptr);
             } else {                                                        // :216-222
                 const real *Ft = p.F + (long)t * p.F_st + (long)b * p.F_sb;
                 const real *ft = p.f ? p.f + (long)t * p.f_st + (long)b * p.f_sb : nullptr;

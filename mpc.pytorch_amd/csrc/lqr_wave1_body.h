@@ -67,6 +67,7 @@ MPC_HD Layout layout(const StepParams<float> &p)
 MPC_HD bool shape_supported(const StepParams<float> &p)
 {
     if (!(p.nc == 1 && p.ns >= 1 && p.ns <= 6 && p.T >= 1 && p.max_ls >= 1 && p.max_ls <= 16)) return false;
+    if (p.env.carry) return false;          // MPC_ENV_CTRL_CARRY: the lane-per-problem kernel only (this one calls env_step as it is)
     if ((long)p.T * 49 * 16 > 160 * 1024) return false;                   // (before the sum below could overflow)
     return (long)layout(p).total * 16 <= 150 * 1024;                      // four problems per wavefront
 }

@@ -47,6 +47,7 @@ class Options(ctypes.Structure):
 
 
 ENV_PENDULUM, ENV_PENDULUM_FULL, ENV_CARTPOLE = 1, 2, 3
+ENV_CTRL_CARRY = 0x100               # MPC_ENV_CTRL_CARRY, OR-ed into mpc_env_dynamics.kind (see EnvSpec.augmented)
 OPT_NOMINAL_ON_DYNAMICS = 1          # mpc_lqr_options.flags
 OPT_SWEEP_ONLY = 2
 OPT_C_SYMMETRIC = 4                  # the caller vouches for C = C' (no symmetry test, no gated re-solve)
@@ -56,17 +57,24 @@ class EnvSpec:
     """What a shipped simulator module hands to the kernels: kind (ENV_*), its parameter tensor,
     the integration step and the control clamp (mpc/env_dx/pendulum.py:23-37, cartpole.py:36-49)."""
 
-    def __init__(self, kind, params, dt, u_max, linearize=False):
+    def __init__(self, kind, params, dt, u_max, linearize=False, carry=False):
         self.kind, self.params, self.dt, self.u_max = int(kind), params, float(dt), float(u_max)
         self.linearize = bool(linearize)     # the step kernel linearises the simulator itself (F, f not passed)
-        self.n_state = 5 if self.kind == ENV_CARTPOLE else 3
+        self.carry = bool(carry)             # CtrlPassthroughDynamics around the simulator (see `augmented`)
+        self.n_state = (5 if self.kind == ENV_CARTPOLE else 3) + int(self.carry)
         self.n_ctrl = 1
         self.n_params = {ENV_PENDULUM: 3, ENV_PENDULUM_FULL: 5}.get(self.kind, 4)
+
+    def augmented(self):
+        """The same simulator as the dynamics of the slew-rate augmentation (mpc/dynamics.py:131-150): state (previous
+        control, x), a step returns (this control, env(x, u)).  MPC_ENV_CTRL_CARRY: mpc_env_traj_cost and the lane-per-problem
+        step carry the control; every other entry refuses the flag."""
+        return EnvSpec(self.kind, self.params, self.dt, self.u_max, linearize=self.linearize, carry=True)
 
     def to_struct(self, like):
         prm = _device_copy_of(self.params, like.device, like.dtype)
         e = EnvDynamics()
-        e.kind, e.params, e.dt, e.u_max = self.kind, prm.data_ptr(), self.dt, self.u_max
+        e.kind, e.params, e.dt, e.u_max = self.kind | (ENV_CTRL_CARRY if self.carry else 0), prm.data_ptr(), self.dt, self.u_max
         e.linearize = int(self.linearize)
         return e, prm
 
@@ -207,7 +215,7 @@ EXPORTS = ("mpc_lqr_abi_version", "mpc_lqr_build_info", "mpc_lqr_last_error", "m
            "mpc_mlp_workspace_bytes", "mpc_mlp_rollout", "mpc_mlp_linearize",
            "mpc_mlp_param_grad_workspace_bytes", "mpc_mlp_param_grad",
            "mpc_mlp_supported", "mpc_lqr_kkt_fused_supported", "mpc_lqr_kkt_fused_workspace_bytes", "mpc_lqr_kkt_fused",
-           "mpc_du_norm_reference")
+           "mpc_du_norm_reference", "mpc_slew_augment")
 
 _lib = None
 
@@ -254,6 +262,7 @@ def load():
     L.mpc_pnqp_lu.argtypes = [ctypes.c_int] * 3 + [_vp] * 5 + [ctypes.c_int] + [_vp] * 8
     L.mpc_traj_cost.argtypes = [PP, _vp, _vp, _vp]
     L.mpc_env_traj_cost.argtypes = [PP, ctypes.POINTER(EnvDynamics), _vp, _vp, _vp]
+    L.mpc_slew_augment.argtypes = [PP, _f64, _vp, _vp, _vp, _vp, _vp]
     L.mpc_env_linearize.argtypes = [ctypes.POINTER(EnvDynamics), ctypes.c_int, _i64, _vp, _vp, _vp, _vp, _vp]
     L.mpc_env_param_grad_workspace_bytes.restype = _i64
     L.mpc_env_param_grad_workspace_bytes.argtypes = [_i64]
@@ -828,6 +837,41 @@ class HipBackend:
         _check(L.mpc_env_traj_cost(ctypes.byref(p), ctypes.byref(e), _ptr(x), _ptr(cost), _stream(dev)),
                "mpc_env_traj_cost")
         return x, cost
+
+    def slew_augment(self, C, c, F, f, n_state, n_ctrl, gamma, prefill=None):
+        """The slew-rate augmentation of (C [T,B,n,n], c [T,B,n], F [T-1,B,ns,n] or None when T = 1, f or None) in one launch
+        (mpc_slew_augment): -> (aC [T,B,na,na], ac [T,B,na], aF [T-1,B,n,na] or None, af or None), na = ns + 2 nc.  An axis the
+        input broadcasts (stride 0) is allocated once and `.expand()`ed in the output, too.  F None (a simulator carried by the
+        kernels): only the cost is augmented.  prefill: a value the outputs hold before the launch (tests: NaN)."""
+        dev = _require_device(C, c, F)
+        self._check_same(C, c, F, f)
+        T, B, n = C.shape[0], C.shape[1], C.shape[2]
+        ns, nc = int(n_state), int(n_ctrl)
+        assert n == ns + nc
+        na = n + nc
+        kw = dict(device=dev, dtype=C.dtype)
+        p = Problem()
+        p.B, p.T, p.ns, p.nc, p.dtype = B, T, ns, nc, _dtype_code(C)
+        keep = []
+
+        def bind(t, inner, name, lead, block):
+            tc, st, sb = _block_strided(t.detach(), inner)
+            keep.append(tc)
+            setattr(p, name, tc.data_ptr()); setattr(p, name + "_st", st); setattr(p, name + "_sb", sb)
+            out = torch.empty((lead if st else min(lead, 1), B if sb else 1) + block, **kw)
+            if prefill is not None:
+                out.fill_(prefill)
+            return out, out.expand((lead, B) + block)
+        aC, aCv = bind(C, 2, "C", T, (na, na))
+        ac, acv = bind(c, 1, "c", T, (na,))
+        aF = aFv = af = afv = None
+        if T > 1 and F is not None:
+            aF, aFv = bind(F, 2, "F", T - 1, (n, na))
+            if f is not None and f.numel() > 0:
+                af, afv = bind(f, 1, "f", T - 1, (n,))
+        _check(load().mpc_slew_augment(ctypes.byref(p), float(gamma), _ptr(aC), _ptr(ac), _ptr(aF), _ptr(af), _stream(dev)),
+               "mpc_slew_augment")
+        return aCv, acv, aFv, afv
 
     def env_linearize(self, env, x, u, out_F=None, out_f=None):
         """x [N,ns], u [N,1] -> F [N,ns,ns+1], f [N,ns] (closed-form Jacobian of the simulator)."""

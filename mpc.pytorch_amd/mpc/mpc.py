@@ -274,8 +274,13 @@ class MPC(Module):
             net = dx.native_net(x_init)
             if net is not None and net.activation == "elu":      # (no grad_input in the reference: the module refuses, mpc/dynamics.py:113-114)
                 net = None
+        # a slew-rate penalty on a QuadCost with LinDx or a shipped simulator: the same device-side loop on the augmented
+        # problem, which does not depend on the iterate and is built once (round 11; _iterate_general rebuilt it per iteration)
+        slew = self._slew_plan(cost, dx, be, x_init)
         if fast or sim is not None:
             best = self._iterate_planned(be, x_init, u, cost, dx, sim, n_batch)
+        elif slew is not None:
+            best = self._iterate_slew(be, x_init, u, cost, dx, slew, n_batch)
         elif net is not None:
             best = self._iterate_network(be, x_init, u, cost, dx, net, n_batch)
         else:
@@ -373,6 +378,49 @@ class MPC(Module):
                     sym_plans = (be.plan_step(xi, cost.C, cost.c, F, f, xa, ua, so, out_x=xb, out_u=ub),
                                  be.plan_step(xi, cost.C, cost.c, F, f, xb, ub, so, out_x=xa, out_u=ua))
         return self._drive(be, launch, (pa.outputs, pb.outputs) if variant is not None else None, r, xa, ua, n_batch, stream, on_symmetric)
+
+    def _slew_plan(self, cost, dx, be, x_init):
+        """Does this slew-rate solve run on the device-side loop (`_iterate_slew`)?  None = no: `_iterate_general`, as before
+        round 11.  Else what the dynamics are there: "lin" (LinDx) or the simulator's EnvSpec behind MPC_ENV_CTRL_CARRY.
+        All of: a QuadCost, a penalty, T > 1, each problem's own du norm (not `reference_du_norm` with B > 1), and either LinDx
+        or a shipped simulator under ANALYTIC / AUTO_DIFF on a backend whose lane-per-problem kernel carries the control
+        (`impl_supported`; FINITE_DIFF keeps the reference's central differences, module costs are not augmented by the
+        reference either)."""
+        if (not isinstance(cost, QuadCost) or self.slew_rate_penalty is None or self.T <= 1
+                or (self.reference_du_norm and x_init.size(0) > 1)):
+            return None
+        if isinstance(dx, LinDx):
+            return "lin"
+        if (hasattr(dx, "native_env") and self.n_ctrl == 1 and self.grad_method in (GradMethods.ANALYTIC, GradMethods.AUTO_DIFF)
+                and hasattr(be, "impl_supported") and x_init.dtype in (torch.float32, torch.float64)):
+            env = dx.native_env().augmented()
+            if env.n_state == self.n_state + 1 and be.impl_supported(
+                    env.n_state, 1, x_init.dtype, _native.IMPL_TINY, StepOptions(true_dynamics=env)):
+                return env
+        return None
+
+    def _iterate_slew(self, be, x_init, u, cost, dx, plan, n_batch):
+        """The loop of `_iterate_planned` on the slew-rate augmentation (mpc/mpc.py:362-445): state z_t = (u_{t-1}, x_t),
+        0.5 gamma |u_t - u_{t-1}|^2 inside the stage cost.  (aC, ac, aF, af) are constant over the solve and built ONCE
+        (mpc_slew_augment where the backend has it, else the torch composition); the augmented rollout of a step IS the next
+        augmented nominal, so nothing is re-packed between iterations.  A simulator is carried through the kernels by
+        MPC_ENV_CTRL_CARRY (its F, f never exist).  `costs` include the penalty, as the reference's (its line search prices the
+        augmented QuadCost); the first n_ctrl state columns are stripped from the best iterate."""
+        nc = self.n_ctrl
+        C, c = util.detach_maybe(cost.C), util.detach_maybe(cost.c)
+        lin = isinstance(dx, LinDx)
+        F = util.detach_maybe(dx.F) if lin else None
+        f = util.detach_maybe(dx.f) if lin else None
+        if hasattr(be, "slew_augment") and C.is_cuda:
+            aC, ac, aF, af = be.slew_augment(C, c, F, f, self.n_state, nc, self.slew_rate_penalty)
+        else:
+            _, aC, ac, aF, af = self._slew_compose(C, c, F, f)
+        prev_u = self._slew_prev_u(n_batch, dict(dtype=C.dtype, device=C.device))
+        ax_init = torch.cat((prev_u[0], util.detach_maybe(x_init)), 1)
+        best = self._iterate_planned(be, ax_init, u, QuadCost(aC, ac), LinDx(aF, af) if lin else None,
+                                     None if lin else plan, n_batch)
+        best["x"] = best["x"][:, :, nc:].contiguous()
+        return best
 
     def _drive(self, be, launch, outputs, r, xa, ua, n_batch, stream, on_symmetric):
         """The loop of mpc/mpc.py:245-306 around pre-bound iterations: launch(i) enqueues iteration i and returns its output
@@ -545,27 +593,10 @@ class MPC(Module):
         from .dynamics import CtrlPassthroughDynamics
         T, ns, nc = self.T, self.n_state, self.n_ctrl
         B = C.size(1)
-        n, na = ns + nc, ns + 2 * nc
+        n = ns + nc
         kw = dict(dtype=C.dtype, device=C.device)
-        gI = self.slew_rate_penalty * torch.eye(nc, **kw)
-        slew_C = torch.zeros(T, B, na, na, **kw)
-        slew_C[:, :, :nc, :nc] = gI
-        slew_C[:, :, -nc:, :nc] = -gI
-        slew_C[:, :, :nc, -nc:] = -gI
-        slew_C[:, :, -nc:, -nc:] = gI
-        aC = slew_C + torch.nn.functional.pad(C, (nc, 0, nc, 0))
-        ac = torch.cat((torch.zeros(T, B, nc, **kw), c), 2)
-        carry = torch.cat((torch.zeros(nc, n, **kw), torch.eye(nc, **kw)), 1)       # u_t -> next state's u_{t-1}
-        aF = torch.cat((carry.expand(T - 1, B, nc, na),
-                        torch.cat((torch.zeros(T - 1, B, ns, nc, **kw), F), 3)), 2)
-        af = None if f is None or f.numel() == 0 else torch.cat((torch.zeros(T - 1, B, nc, **kw), f), 2)
-        if self.prev_ctrl is not None:
-            prev_u = self.prev_ctrl.detach().to(**kw)
-            while prev_u.ndimension() < 3:
-                prev_u = prev_u.unsqueeze(0)
-        else:
-            prev_u = torch.zeros(1, B, nc, **kw)
-        prev_u = prev_u.expand(1, B, nc)
+        slew_C, aC, ac, aF, af = self._slew_compose(C, c, F, f)
+        prev_u = self._slew_prev_u(B, kw)
         ax = torch.cat((torch.cat((prev_u, util.detach_maybe(u)[:-1])), x), 2)
         ax_init = torch.cat((prev_u[0], x_init), 1)
         a_dyn = None if isinstance(dynamics, LinDx) else CtrlPassthroughDynamics(dynamics)
@@ -579,6 +610,39 @@ class MPC(Module):
         empty = torch.empty(0, **kw)
         out = step(ax_init, aC, ac, aF, af if af is not None else empty)
         return (out[0][:, :, nc:],) + tuple(out[1:])
+
+    def _slew_compose(self, C, c, F, f):
+        """(slew_C, aC, aC's linear term ac, aF, af) of the slew-rate augmentation from [T,B,...] tensors, in torch: autograd
+        reaches C, c, F, f through the padding ops.  F None (a simulator carried by the kernels): aF = af = None."""
+        T, ns, nc = self.T, self.n_state, self.n_ctrl
+        B = C.size(1)
+        n, na = ns + nc, ns + 2 * nc
+        kw = dict(dtype=C.dtype, device=C.device)
+        gI = self.slew_rate_penalty * torch.eye(nc, **kw)
+        slew_C = torch.zeros(T, B, na, na, **kw)
+        slew_C[:, :, :nc, :nc] = gI
+        slew_C[:, :, -nc:, :nc] = -gI
+        slew_C[:, :, :nc, -nc:] = -gI
+        slew_C[:, :, -nc:, -nc:] = gI
+        aC = slew_C + torch.nn.functional.pad(C, (nc, 0, nc, 0))
+        ac = torch.cat((torch.zeros(T, B, nc, **kw), c), 2)
+        if F is None:
+            return slew_C, aC, ac, None, None
+        carry = torch.cat((torch.zeros(nc, n, **kw), torch.eye(nc, **kw)), 1)       # u_t -> next state's u_{t-1}
+        aF = torch.cat((carry.expand(T - 1, B, nc, na),
+                        torch.cat((torch.zeros(T - 1, B, ns, nc, **kw), F), 3)), 2)
+        af = None if f is None or f.numel() == 0 else torch.cat((torch.zeros(T - 1, B, nc, **kw), f), 2)
+        return slew_C, aC, ac, aF, af
+
+    def _slew_prev_u(self, B, kw):
+        """`prev_ctrl` as [1,B,n_ctrl] (every rank up to three broadcasts from the left; None = zeros)."""
+        if self.prev_ctrl is not None:
+            prev_u = self.prev_ctrl.detach().to(**kw)
+            while prev_u.ndimension() < 3:
+                prev_u = prev_u.unsqueeze(0)
+        else:
+            prev_u = torch.zeros(1, B, self.n_ctrl, **kw)
+        return prev_u.expand(1, B, self.n_ctrl)
 
     # ------------------------------------------------------------------------------------------
     def approximate_cost(self, x, u, Cf, diff=True):
