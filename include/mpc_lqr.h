@@ -342,7 +342,8 @@ typedef struct mpc_mlp_dynamics {
                                                  is (previous control, x), a step returns (this control, net(x, u)).  The
                                                  weights then describe the augmented map: zero columns for the previous control
                                                  in W[0], zero rows for it in the last layer; the first ctrl_carry entries of the
-                                                 next state are the control itself and take no passthrough.  Rollout only. */
+                                                 next state are the control itself and take no passthrough.  Rollout only:
+                                                 the augmented linearisation is mpc_mlp_linearize_carry on the network itself. */
     int32_t widths[MPC_MLP_MAX_LAYERS + 1];   /* widths[0] = n_state + n_ctrl, widths[n_layers] = n_state */
     const void *W[MPC_MLP_MAX_LAYERS];
     const void *b[MPC_MLP_MAX_LAYERS];
@@ -377,6 +378,20 @@ int mpc_mlp_rollout(const mpc_lqr_problem *p, const mpc_lqr_options *o, const mp
  *      mpc/dynamics.py:82-128) at N points x [N,ns], u [N,nc]: F [N,ns,ns+nc], f [N,ns] = net(x,u) - F [x;u]. */
 int mpc_mlp_linearize(const mpc_mlp_dynamics *net, int n_state, int n_ctrl, int64_t N, const void *x, const void *u,
                       void *F, void *f, void *workspace, int64_t workspace_bytes, void *stream);
+
+/*      The same linearisation written straight into the layout of the slew-rate augmentation (mpc/mpc.py:362-445,
+ *      mpc/dynamics.py:131-150: state z = (u_prev, x), z' = (u, net(x, u))), na = n_state + n_ctrl.  `net` is the network
+ *      ITSELF (ctrl_carry == 0, widths [n_state + n_ctrl, ..., n_state]; ctrl_carry != 0 is MPC_E_ARG) -- a (12, 4, [100])
+ *      network stays on the register-resident kernel, which the augmented weights (20 inputs, padded to 32) would leave.
+ *      z [N,na]: x is read from columns n_ctrl.. with row stride na; u [N,n_ctrl].
+ *          aF [N,na,na+n_ctrl]: rows i < n_ctrl are (j == na + i); row n_ctrl + i is (0 .. 0 | F[i][:]), n_ctrl zeros first
+ *          af [N,na]          : n_ctrl zeros, then f
+ *      with (F, f) BITWISE those of mpc_mlp_linearize(net, x = z[:, n_ctrl:], u): the same kernels with the addresses as
+ *      launch parameters.  Every element of aF, af is written exactly once by the one launch (no memset).
+ *      The envelope is mpc_mlp_linearize's plus n_state + n_ctrl <= 32 (MPC_E_DIMS); N = 0 succeeds; NULL / workspace codes
+ *      as there.  mpc_mlp_linearize itself keeps refusing ctrl_carry.  (ABI 9, additive) */
+int mpc_mlp_linearize_carry(const mpc_mlp_dynamics *net, int n_state, int n_ctrl, int64_t N, const void *z, const void *u,
+                            void *aF, void *af, void *workspace, int64_t workspace_bytes, void *stream);
 
 /*      The backward of mpc_mlp_linearize with respect to the network's weights and biases -- what makes a solve through a
  *      trainable NNDynamics trainable on the device (GradMethods.ANALYTIC with diff=True, mpc/mpc.py:625-635).  With x, u

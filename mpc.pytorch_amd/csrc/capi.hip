@@ -729,6 +729,17 @@ int mpc_mlp_linearize(const mpc_mlp_dynamics *net, int n_state, int n_ctrl, int6
                                workspace, workspace_bytes, (hipStream_t)stream);
 }
 
+int mpc_mlp_linearize_carry(const mpc_mlp_dynamics *net, int n_state, int n_ctrl, int64_t N, const void *z, const void *u,
+                            void *aF, void *af, void *workspace, int64_t workspace_bytes, void *stream)
+{
+    if (n_state < 1 || n_ctrl < 1 || N < 0) return fail(MPC_E_DIMS, "need n_state>=1, n_ctrl>=1, N>=0");
+    if (n_state + n_ctrl > 32) return fail(MPC_E_DIMS, "mlp_linearize_carry: n_state + n_ctrl <= 32 (the augmented state of the step kernels)");
+    if (N == 0) return MPC_OK;
+    if (!z || !u || !aF || !af) return fail(MPC_E_NULL, "mlp_linearize_carry: NULL argument");
+    return launch_nn_linearize_carry(net, (long)N, n_state, n_ctrl, (const float *)z, (const float *)u, (float *)aF, (float *)af,
+                                     workspace, workspace_bytes, (hipStream_t)stream);
+}
+
 int64_t mpc_mlp_param_grad_workspace_bytes(const mpc_mlp_dynamics *net, int64_t N) { return nn_param_grad_workspace_bytes(net, N); }
 
 int mpc_mlp_param_grad(const mpc_mlp_dynamics *net, int n_state, int n_ctrl, int64_t N, const void *x, const void *u,

@@ -121,6 +121,9 @@ int nn_budget(const mpc_mlp_dynamics *net, int ns, int nc);     // bit 0: the ro
 int launch_nn_rollout(const StepParams<float> &p, const mpc_mlp_dynamics *net, void *workspace, int64_t bytes, hipStream_t st);
 int launch_nn_linearize(const mpc_mlp_dynamics *net, long N, int ns, int nc, const float *x, const float *u, float *F,
                         float *f, void *workspace, int64_t bytes, hipStream_t st);
+// ... into the slew-rate augmentation's layout: z [N,nc+ns] = (u_prev, x), aF [N,na,na+nc], af [N,na], na = ns + nc (same kernels)
+int launch_nn_linearize_carry(const mpc_mlp_dynamics *net, long N, int ns, int nc, const float *z, const float *u, float *aF,
+                              float *af, void *workspace, int64_t bytes, hipStream_t st);
 // ... and the linearisation's weight gradient (nn_param_grad.h); nn_budget bit 2 says whether it takes the network
 int64_t nn_param_grad_workspace_bytes(const mpc_mlp_dynamics *net, int64_t N);     // -1: outside the kernel
 int launch_nn_param_grad(const mpc_mlp_dynamics *net, long N, int ns, int nc, const float *x, const float *u, const float *gF,

@@ -335,6 +335,40 @@ __global__ void __launch_bounds__(256) nn_wide_rollout_kernel(StepParams<float> 
     rollout_tiles<WL, 2>(p, m, TS, ZS, wave_floats);
 }
 
+// Where a linearisation reads x and writes (F, f), in floats -- launch parameters, so that the layout of the slew-rate
+// augmentation (mpc_mlp_linearize_carry: state (u_prev, x), aF = [[0 0 I], [0 F]], af = [0; f]) runs the arithmetic of the dense one
+// (mpc_mlp_linearize) instruction for instruction; only addresses differ.
+struct LinLayout {
+    int xs, xo;         // x of point p: x + p xs + xo
+    int Fp, Fr, Fo;     // F[i][j] of point p: F + p Fp + Fo + i Fr + j
+    int fs, fo;         // f[i] of point p: f + p fs + fo
+    int carry;          // 0: dense.  n_ctrl: the augmented layout -- the constant blocks are written too (below), and a network row's
+                        // store also zeroes the `carry` floats in front of it (the u_prev columns: Fo = carry Fr + carry)
+};
+inline LinLayout dense_layout(int ns, int nc) { return LinLayout{ns, 0, ns * (ns + nc), ns + nc, 0, ns, 0, 0}; }
+inline LinLayout carry_layout(int ns, int nc)
+{
+    const int na = ns + nc, W = na + nc;
+    return LinLayout{na, nc, na * W, W, nc * W + nc, na, nc, nc};
+}
+
+// The constant blocks of the augmented layout, by each wavefront for its own sixteen points: a point's carry rows are ONE contiguous run
+// of carry (na + carry) floats at the head of its matrix, element (i, j) = (j == na + i); af starts with `carry` zeros.
+__device__ __forceinline__ void write_carry_blocks(const LinLayout &lay, long p0, long N, int ns, float *F, float *f, int lane)
+{
+    const int nc = lay.carry, W = lay.Fr, na = ns + nc, run = nc * W;
+    const int np = (int)(N - p0 < 16 ? N - p0 : 16);
+    for (int e = lane; e < run; e += 64) {
+        const int i = e / W, j = e - i * W;
+        const float v = j == na + i ? 1.f : 0.f;
+        for (int pp = 0; pp < np; ++pp) F[(p0 + pp) * lay.Fp + e] = v;
+    }
+    for (int e = lane; e < np * nc; e += 64) {
+        const int pp = e / nc, i = e - pp * nc;
+        f[(p0 + pp) * lay.fs + i] = 0.f;
+    }
+}
+
 // ---------------------------------------------------------------------------------------------------------------
 // F = d net / d [x;u], f = net(x, u) - F [x;u] at N points (mpc/mpc.py:495-512 + mpc/dynamics.py:82-128), sixteen
 // points per wavefront: one forward pass for all sixteen, then the chain of one point at a time.  A product
@@ -344,7 +378,7 @@ __global__ void __launch_bounds__(256) nn_wide_rollout_kernel(StepParams<float> 
 // ST: row tiles of the output layer (n_state <= 16 ST).
 template <bool WL, int ST>
 __device__ __forceinline__ void linearize_tiles(MlpDesc m, long N, int ns, int nc, const float *x, const float *u,
-                                                float *F, float *f, int TS, int ZS, int GT, int wave_floats)
+                                                float *F, float *f, LinLayout lay, int TS, int ZS, int GT, int wave_floats)
 {
     extern __shared__ __attribute__((aligned(16))) float lds[];
     const float *wts = stage_weights<WL>(m, lds);
@@ -356,11 +390,12 @@ __device__ __forceinline__ void linearize_tiles(MlpDesc m, long N, int ns, int n
     if (p0 >= N) return;
     const long pt = (p0 + r < N) ? p0 + r : N - 1;
     const int n = ns + nc, NTJ = m.wp[0] >> 4;
+    if (lay.carry) write_carry_blocks(lay, p0, N, ns, F, f, lane);
     for (int f0 = 4 * q; f0 < m.wp[0]; f0 += 16) {
 #pragma unroll
         for (int v = 0; v < 4; ++v) {
             const int fe = f0 + v;
-            tauS[r * TS + fe] = fe < ns ? x[pt * ns + fe] : (fe < n ? u[pt * nc + (fe - ns)] : 0.f);
+            tauS[r * TS + fe] = fe < ns ? x[pt * lay.xs + lay.xo + fe] : (fe < n ? u[pt * nc + (fe - ns)] : 0.f);
         }
     }
     wave_sync();
@@ -412,6 +447,7 @@ __device__ __forceinline__ void linearize_tiles(MlpDesc m, long N, int ns, int n
         for (int s = 0; s < ST; ++s)
 #pragma unroll
             for (int v = 0; v < 4; ++v) fs[s][v] = 0.f;
+        float *Fb = F + (p0 + pp) * lay.Fp + lay.Fo;
         {
             const int l = Lh, nin_t = m.wp[l] >> 4, ld = m.wp[l] + 4;
             const float *W = wts + m.woff[l];
@@ -451,7 +487,10 @@ __device__ __forceinline__ void linearize_tiles(MlpDesc m, long N, int ns, int n
                     for (int v = 0; v < 4; ++v) {
                         const int i = 16 * s + 4 * q + v;
                         if (m.pass && i == j && j < ns) J[s][v] += 1.f;                     // mpc/dynamics.py:118-125
-                        if (i < ns && j < n) F[((p0 + pp) * ns + i) * n + j] = J[s][v];
+                        if (i < ns && j < n) {
+                            Fb[i * lay.Fr + j] = J[s][v];
+                            if (j < lay.carry) Fb[i * lay.Fr + j - lay.carry] = 0.f;        // (the u_prev columns of this row)
+                        }
                         fs[s][v] = fmaf(J[s][v], tj_tau, fs[s][v]);
                     }
             }
@@ -473,7 +512,7 @@ __device__ __forceinline__ void linearize_tiles(MlpDesc m, long N, int ns, int n
 #pragma unroll
                 for (int v = 0; v < 4; ++v) {
                     const int i = 16 * s + 4 * q + v;
-                    if (i < ns) f[(p0 + pp) * ns + i] = out.t[s][v] - fs[s][v];               // mpc/mpc.py:508-509
+                    if (i < ns) f[(p0 + pp) * lay.fs + lay.fo + i] = out.t[s][v] - fs[s][v];   // mpc/mpc.py:508-509
                 }
         }
     }
@@ -481,16 +520,16 @@ __device__ __forceinline__ void linearize_tiles(MlpDesc m, long N, int ns, int n
 
 template <bool WL>
 __global__ void __launch_bounds__(512) nn_linearize_kernel(MlpDesc m, long N, int ns, int nc, const float *x, const float *u,
-                                                           float *F, float *f, int TS, int ZS, int GT, int wave_floats)
+                                                           float *F, float *f, LinLayout lay, int TS, int ZS, int GT, int wave_floats)
 {
-    linearize_tiles<WL, 1>(m, N, ns, nc, x, u, F, f, TS, ZS, GT, wave_floats);
+    linearize_tiles<WL, 1>(m, N, ns, nc, x, u, F, f, lay, TS, ZS, GT, wave_floats);
 }
 // 16 < n_state <= 32: two row tiles of the output layer, of F and of f
 template <bool WL>
 __global__ void __launch_bounds__(512) nn_wide_linearize_kernel(MlpDesc m, long N, int ns, int nc, const float *x, const float *u,
-                                                                float *F, float *f, int TS, int ZS, int GT, int wave_floats)
+                                                                float *F, float *f, LinLayout lay, int TS, int ZS, int GT, int wave_floats)
 {
-    linearize_tiles<WL, 2>(m, N, ns, nc, x, u, F, f, TS, ZS, GT, wave_floats);
+    linearize_tiles<WL, 2>(m, N, ns, nc, x, u, F, f, lay, TS, ZS, GT, wave_floats);
 }
 
 // ===============================================================================================================
@@ -862,7 +901,7 @@ __global__ void __launch_bounds__(64) nn_rollout_fast_kernel(StepParams<float> p
 // f = net - F tau needs no reduction either: net - F tau = W_2 (z - s .* (W_1 tau)) + b_2, one more pass of layer 2.
 template <int HT, int PP> struct JacPoints {
     static __device__ __forceinline__ void run(const NetRegs<HT> &R, const f32x4 (&w1d)[HT], const f32x4 (&s)[HT], int pass,
-                                               long p0, long N, int ns, int n, int q, int r, float *F)
+                                               long p0, long N, int ns, int n, int q, int r, float *F, const LinLayout &lay)
     {
         if (p0 + PP < N) {
             // all B operands of the point first, then the MFMAs as one block: an MFMA issued right behind the vector
@@ -883,28 +922,33 @@ template <int HT, int PP> struct JacPoints {
             }
             __builtin_amdgcn_sched_barrier(0);
             const f32x4 J = (a0 + a1) + (a2 + a3);
+            float *Fb = F + (p0 + PP) * lay.Fp + lay.Fo;
 #pragma unroll
             for (int v = 0; v < 4; ++v) {
                 const int i = 4 * q + v;
-                if (i < ns && r < n) F[((p0 + PP) * ns + i) * n + r] = J[v] + ((pass && i == r) ? 1.f : 0.f);   // mpc/dynamics.py:118-125
+                if (i < ns && r < n) {
+                    Fb[i * lay.Fr + r] = J[v] + ((pass && i == r) ? 1.f : 0.f);             // mpc/dynamics.py:118-125
+                    if (r < lay.carry) Fb[i * lay.Fr + r - lay.carry] = 0.f;               // (the u_prev columns of this row)
+                }
             }
         }
-        JacPoints<HT, PP + 1>::run(R, w1d, s, pass, p0, N, ns, n, q, r, F);
+        JacPoints<HT, PP + 1>::run(R, w1d, s, pass, p0, N, ns, n, q, r, F, lay);
     }
 };
 template <int HT> struct JacPoints<HT, 16> {
     static __device__ __forceinline__ void run(const NetRegs<HT> &, const f32x4 (&)[HT], const f32x4 (&)[HT], int, long, long, int, int,
-                                               int, int, float *) {}
+                                               int, int, float *, const LinLayout &) {}
 };
 
 template <int HT, int ACT>
 __global__ void __launch_bounds__(64) nn_linearize_fast_kernel(MlpDesc m, long N, int ns, int nc, const float *x, const float *u,
-                                                               float *F, float *f)
+                                                               float *F, float *f, LinLayout lay)
 {
     const int lane = threadIdx.x, r = lane & 15, q = lane >> 4;
     const long p0 = (long)blockIdx.x * 16;
     const long pt = (p0 + r < N) ? p0 + r : N - 1;
     const int n = ns + nc;
+    if (lay.carry) write_carry_blocks(lay, p0, N, ns, F, f, lane);       // (first: nothing of the network is in registers yet)
     NetRegs<HT> R;
     load_net<HT>(R, m, q, r);
     f32x4 w1d[HT];                      // W_1 in accumulator layout: rows (hidden units) 16 to + 4q + v, column r
@@ -917,7 +961,7 @@ __global__ void __launch_bounds__(64) nn_linearize_fast_kernel(MlpDesc m, long N
 #pragma unroll
     for (int v = 0; v < 4; ++v) {
         const int fe = 4 * q + v;
-        const float tx = load_if(x, pt * ns + fe, fe < ns), tu = load_if(u, pt * nc + (fe - ns), fe >= ns && fe < n);
+        const float tx = load_if(x, pt * lay.xs + lay.xo + fe, fe < ns), tu = load_if(u, pt * nc + (fe - ns), fe >= ns && fe < n);
         tq[v] = fe < ns ? tx : tu;
     }
     f32x4 z[HT], s[HT];
@@ -933,9 +977,9 @@ __global__ void __launch_bounds__(64) nn_linearize_fast_kernel(MlpDesc m, long N
     if (p0 + r < N) {
 #pragma unroll
         for (int v = 0; v < 4; ++v)
-            if (4 * q + v < ns) f[pt * ns + 4 * q + v] = fv[v];                              // mpc/mpc.py:508-509
+            if (4 * q + v < ns) f[pt * lay.fs + lay.fo + 4 * q + v] = fv[v];                 // mpc/mpc.py:508-509
     }
-    JacPoints<HT, 0>::run(R, w1d, s, m.pass, p0, N, ns, n, q, r, F);
+    JacPoints<HT, 0>::run(R, w1d, s, m.pass, p0, N, ns, n, q, r, F, lay);
 }
 
 inline int check_launch(const char *what)
@@ -1105,11 +1149,11 @@ int launch_nn_rollout(const StepParams<float> &p, const mpc_mlp_dynamics *net, v
     return check_launch("nn_rollout_kernel");
 }
 
-int launch_nn_linearize(const mpc_mlp_dynamics *net, long N, int ns, int nc, const float *x, const float *u, float *F,
-                        float *f, void *workspace, int64_t bytes, hipStream_t st)
+// both linearisation entries: the same kernels, the layout (dense / the slew-rate augmentation's) a launch parameter
+static int launch_linearize(const mpc_mlp_dynamics *net, long N, int ns, int nc, const float *x, const float *u, float *F,
+                            float *f, const LinLayout &lay, void *workspace, int64_t bytes, hipStream_t st)
 {
     MlpDesc d;
-    if (net && net->ctrl_carry) { set_last_error("mlp_linearize: ctrl_carry describes a rollout only (linearise the network itself)"); return MPC_E_ARG; }
     int rc = mlp_prepare(net, ns, nc, workspace, bytes, d, st);
     if (rc) return rc;
     if (d.L == 2 && d.wp[0] == 16 && d.wp[1] <= 128) {
@@ -1117,9 +1161,9 @@ int launch_nn_linearize(const mpc_mlp_dynamics *net, long N, int ns, int nc, con
         const int ht = d.wp[1] >> 4;
 #define MPC_NN_LIN(HT_)                                                                                                             \
         do {                                                                                                                        \
-            if (d.act == MPC_ACT_SIGMOID) hipLaunchKernelGGL((nn_linearize_fast_kernel<HT_, MPC_ACT_SIGMOID>), dim3(g), dim3(64), 0, st, d, N, ns, nc, x, u, F, f); \
-            else if (d.act == MPC_ACT_RELU) hipLaunchKernelGGL((nn_linearize_fast_kernel<HT_, MPC_ACT_RELU>), dim3(g), dim3(64), 0, st, d, N, ns, nc, x, u, F, f);   \
-            else hipLaunchKernelGGL((nn_linearize_fast_kernel<HT_, MPC_ACT_ELU>), dim3(g), dim3(64), 0, st, d, N, ns, nc, x, u, F, f);                              \
+            if (d.act == MPC_ACT_SIGMOID) hipLaunchKernelGGL((nn_linearize_fast_kernel<HT_, MPC_ACT_SIGMOID>), dim3(g), dim3(64), 0, st, d, N, ns, nc, x, u, F, f, lay); \
+            else if (d.act == MPC_ACT_RELU) hipLaunchKernelGGL((nn_linearize_fast_kernel<HT_, MPC_ACT_RELU>), dim3(g), dim3(64), 0, st, d, N, ns, nc, x, u, F, f, lay);   \
+            else hipLaunchKernelGGL((nn_linearize_fast_kernel<HT_, MPC_ACT_ELU>), dim3(g), dim3(64), 0, st, d, N, ns, nc, x, u, F, f, lay);                              \
         } while (0)
         if (ht <= 2) MPC_NN_LIN(2);
         else if (ht <= 4) MPC_NN_LIN(4);
@@ -1143,19 +1187,33 @@ int launch_nn_linearize(const mpc_mlp_dynamics *net, long N, int ns, int nc, con
     if (ns > 16) {
         if (wl) {
             allow_lds(&nn_wide_linearize_kernel<true>, lds);
-            hipLaunchKernelGGL(nn_wide_linearize_kernel<true>, dim3(grid), dim3(64 * nw), lds, st, d, N, ns, nc, x, u, F, f, TS, ZS, GT, wave_floats);
+            hipLaunchKernelGGL(nn_wide_linearize_kernel<true>, dim3(grid), dim3(64 * nw), lds, st, d, N, ns, nc, x, u, F, f, lay, TS, ZS, GT, wave_floats);
         } else {
             allow_lds(&nn_wide_linearize_kernel<false>, lds);
-            hipLaunchKernelGGL(nn_wide_linearize_kernel<false>, dim3(grid), dim3(64 * nw), lds, st, d, N, ns, nc, x, u, F, f, TS, ZS, GT, wave_floats);
+            hipLaunchKernelGGL(nn_wide_linearize_kernel<false>, dim3(grid), dim3(64 * nw), lds, st, d, N, ns, nc, x, u, F, f, lay, TS, ZS, GT, wave_floats);
         }
     } else if (wl) {
         allow_lds(&nn_linearize_kernel<true>, lds);
-        hipLaunchKernelGGL(nn_linearize_kernel<true>, dim3(grid), dim3(64 * nw), lds, st, d, N, ns, nc, x, u, F, f, TS, ZS, GT, wave_floats);
+        hipLaunchKernelGGL(nn_linearize_kernel<true>, dim3(grid), dim3(64 * nw), lds, st, d, N, ns, nc, x, u, F, f, lay, TS, ZS, GT, wave_floats);
     } else {
         allow_lds(&nn_linearize_kernel<false>, lds);
-        hipLaunchKernelGGL(nn_linearize_kernel<false>, dim3(grid), dim3(64 * nw), lds, st, d, N, ns, nc, x, u, F, f, TS, ZS, GT, wave_floats);
+        hipLaunchKernelGGL(nn_linearize_kernel<false>, dim3(grid), dim3(64 * nw), lds, st, d, N, ns, nc, x, u, F, f, lay, TS, ZS, GT, wave_floats);
     }
     return check_launch("nn_linearize_kernel");
+}
+
+int launch_nn_linearize(const mpc_mlp_dynamics *net, long N, int ns, int nc, const float *x, const float *u, float *F,
+                        float *f, void *workspace, int64_t bytes, hipStream_t st)
+{
+    if (net && net->ctrl_carry) { set_last_error("mlp_linearize: ctrl_carry describes a rollout only (linearise the network itself)"); return MPC_E_ARG; }
+    return launch_linearize(net, N, ns, nc, x, u, F, f, dense_layout(ns, nc), workspace, bytes, st);
+}
+
+int launch_nn_linearize_carry(const mpc_mlp_dynamics *net, long N, int ns, int nc, const float *z, const float *u, float *aF,
+                              float *af, void *workspace, int64_t bytes, hipStream_t st)
+{
+    if (net && net->ctrl_carry) { set_last_error("mlp_linearize_carry: pass the network itself (ctrl_carry = 0), not its augmentation"); return MPC_E_ARG; }
+    return launch_linearize(net, N, ns, nc, z, u, aF, af, carry_layout(ns, nc), workspace, bytes, st);
 }
 
 // workspace of launch_nn_param_grad: the packed network, then one partial per block.  -1: the network is outside the kernel.

@@ -128,10 +128,11 @@ class MlpSpec:
     the struct is rebuilt for every call, a training loop changes them between calls), the activation and the
     passthrough flag (mpc/dynamics.py:15-36)."""
 
-    def __init__(self, weights, biases, activation, passthrough, ctrl_carry=0):
+    def __init__(self, weights, biases, activation, passthrough, ctrl_carry=0, inner=None):
         self.weights, self.biases = list(weights), list(biases)
         self.activation, self.passthrough = activation, bool(passthrough)
         self.ctrl_carry = int(ctrl_carry)      # CtrlPassthroughDynamics around the network (see `augmented`)
+        self.inner = inner                     # ... and the spec of the network itself (mpc_mlp_linearize_carry takes that one)
         self.n_state = self.weights[-1].shape[0]
         self.n_ctrl = self.weights[0].shape[1] - self.n_state
 
@@ -148,29 +149,31 @@ class MlpSpec:
         else:
             W[-1] = torch.cat((W[-1].new_zeros(nc, W[-1].shape[1]), W[-1]), 0)
         b[-1] = torch.cat((b[-1].new_zeros(nc), b[-1]), 0)
-        return MlpSpec(W, b, self.activation, self.passthrough, ctrl_carry=nc)
+        return MlpSpec(W, b, self.activation, self.passthrough, ctrl_carry=nc, inner=self)
 
     @staticmethod
-    def supported(weights, activation, like):
+    def supported(weights, activation, like, bits=3):
         """fp32 on the device of `like`, at most four layers, n_state <= 32, and layer widths whose staging areas fit the
         160 KiB of LDS the kernels work in -- the library's own test (mpc_mlp_supported: both the rollout and the
-        linearisation kernel must take the network, e.g. NNDynamics(4, 1, [1024]) does not and keeps the module path)."""
+        linearisation kernel must take the network, e.g. NNDynamics(4, 1, [1024]) does not and keeps the module path;
+        `bits=1`: the rollout kernels alone, for a spec that is only ever rolled out -- `augmented()`)."""
         if not (like.is_cuda and like.dtype == torch.float32 and 1 <= len(weights) <= MLP_MAX_LAYERS
                 and activation in ACT_CODES and weights[-1].shape[0] <= 32
                 and all(W.shape[0] <= 4096 for W in weights)
                 and all(W.is_cuda and W.dtype == torch.float32 for W in weights)):
             return False
-        return MlpSpec.widths_supported([weights[0].shape[1]] + [W.shape[0] for W in weights])
+        return MlpSpec.widths_supported([weights[0].shape[1]] + [W.shape[0] for W in weights], bits)
 
     @staticmethod
-    def widths_supported(widths):
-        """mpc_mlp_supported for a network of these layer widths ([n_state + n_ctrl, hidden..., n_state])."""
+    def widths_supported(widths, bits=3):
+        """mpc_mlp_supported for a network of these layer widths ([n_state + n_ctrl, hidden..., n_state]): every bit of `bits`
+        (1 = rollout, 2 = linearisation) must be set."""
         e = MlpDynamics()
         e.n_layers = len(widths) - 1
         for l, w in enumerate(widths):
             e.widths[l] = int(w)
         ns = int(widths[-1])
-        return (int(load().mpc_mlp_supported(ctypes.byref(e), ns, int(widths[0]) - ns)) & 3) == 3
+        return (int(load().mpc_mlp_supported(ctypes.byref(e), ns, int(widths[0]) - ns)) & bits) == bits
 
     def param_grad_supported(self):
         """Bit 2 of mpc_mlp_supported: does mpc_mlp_param_grad (the weight gradient of the linearisation) take this network?
@@ -212,7 +215,7 @@ EXPORTS = ("mpc_lqr_abi_version", "mpc_lqr_build_info", "mpc_lqr_last_error", "m
            "mpc_lqr_step", "mpc_lqr_impl_supported", "mpc_lqr_qp_record", "mpc_lqr_sweep", "mpc_lqr_rollout", "mpc_lqr_kkt_grads", "mpc_lqr_kkt_prepare",
            "mpc_pnqp", "mpc_pnqp_lu", "mpc_traj_cost", "mpc_env_traj_cost", "mpc_env_linearize", "mpc_select_best",
            "mpc_env_param_grad_workspace_bytes", "mpc_env_param_grad",
-           "mpc_mlp_workspace_bytes", "mpc_mlp_rollout", "mpc_mlp_linearize",
+           "mpc_mlp_workspace_bytes", "mpc_mlp_rollout", "mpc_mlp_linearize", "mpc_mlp_linearize_carry",
            "mpc_mlp_param_grad_workspace_bytes", "mpc_mlp_param_grad",
            "mpc_mlp_supported", "mpc_lqr_kkt_fused_supported", "mpc_lqr_kkt_fused_workspace_bytes", "mpc_lqr_kkt_fused",
            "mpc_du_norm_reference", "mpc_slew_augment")
@@ -274,6 +277,7 @@ def load():
     L.mpc_mlp_supported.argtypes = [MP, ctypes.c_int, ctypes.c_int]
     L.mpc_mlp_rollout.argtypes = [PP, OP, MP, _vp, _vp, _vp, UP, _vp, _i64, _vp]
     L.mpc_mlp_linearize.argtypes = [MP, ctypes.c_int, ctypes.c_int, _i64, _vp, _vp, _vp, _vp, _vp, _i64, _vp]
+    L.mpc_mlp_linearize_carry.argtypes = [MP, ctypes.c_int, ctypes.c_int, _i64, _vp, _vp, _vp, _vp, _vp, _i64, _vp]
     L.mpc_mlp_param_grad_workspace_bytes.restype = _i64
     L.mpc_mlp_param_grad_workspace_bytes.argtypes = [MP, _i64]
     L.mpc_mlp_param_grad.argtypes = [MP, ctypes.c_int, ctypes.c_int, _i64, _vp, _vp, _vp, _vp, ctypes.POINTER(MlpParamGrads), _vp, _i64, _vp]
@@ -979,6 +983,25 @@ class HipBackend:
                                    ws.data_ptr(), nbytes, _stream(dev)), "mpc_mlp_linearize")
         return F, f
 
+    def mlp_linearize_carry(self, net, z, u, out_F=None, out_f=None):
+        """`mlp_linearize` of the network itself (`net`: no ctrl_carry) at the augmented points z = (u_prev, x) [N,nc+ns],
+        u [N,nc], written straight into the layout of the slew-rate augmentation (mpc/mpc.py:362-445, mpc/dynamics.py:131-150),
+        na = ns + nc: aF [N,na,na+nc] = [[0 0 I], [0 F]], af [N,na] = [0; f] -- every element by the one launch."""
+        dev = _require_device(z, u)
+        L = load()
+        N, na = z.shape
+        nc = u.shape[1]
+        ns = na - nc
+        kw = dict(device=dev, dtype=z.dtype)
+        z = z.detach().contiguous(); u = u.detach().contiguous()
+        F = torch.empty(N, na, na + nc, **kw) if out_F is None else out_F
+        f = torch.empty(N, na, **kw) if out_f is None else out_f
+        assert F.is_contiguous() and f.is_contiguous() and F.numel() == N * na * (na + nc) and f.numel() == N * na
+        e, ws, nbytes, keep_e = net.to_struct(z)
+        _check(L.mpc_mlp_linearize_carry(ctypes.byref(e), ns, nc, N, z.data_ptr(), u.data_ptr(), F.data_ptr(), f.data_ptr(),
+                                         ws.data_ptr(), nbytes, _stream(dev)), "mpc_mlp_linearize_carry")
+        return F, f
+
     def mlp_linearize_backward(self, net, x, u, gF, gf):
         """The backward of `mlp_linearize` with respect to the network's weights and biases: x [N,ns], u [N,nc] (constants) and
         the cotangents gF [N,ns,ns+nc], gf [N,ns] of (F, f) -> [gW_1, gb_1, ..., gW_L, gb_L], float32 on the device, in
@@ -1013,7 +1036,10 @@ class HipBackend:
         (MPC_OPT_SWEEP_ONLY, the fused kernel of the shape), mpc_mlp_rollout -- no allocation, no struct rebuilt, no torch op.
         nominals = ((xa, ua), (xb, ub)): iteration k reads nominals[k % 2] and writes nominals[1 - k % 2] (contiguous buffers).
         -> (run(k, stream=None) -> outputs dict of that parity, (outputs_0, outputs_1), vouch_c()): vouch_c() re-binds the two
-        sweeps with MPC_OPT_C_SYMMETRIC once the first sweep has reported C symmetric."""
+        sweeps with MPC_OPT_C_SYMMETRIC once the first sweep has reported C symmetric.
+        A `net` with `ctrl_carry` (MlpSpec.augmented(): the slew-rate augmentation, x_init / C / c / nominals at n_state + n_ctrl
+        states) linearises with mpc_mlp_linearize_carry on `net.inner`, the network itself, with a packed-weights workspace of
+        its own; sweep and rollout are the same calls on the augmented sizes and the augmented spec."""
         dev = _require_device(x_init, C, c, nominals[0][0], nominals[0][1])
         L = load()
         T, B, n = C.shape[0], C.shape[1], C.shape[2]
@@ -1024,6 +1050,14 @@ class HipBackend:
         F, f = torch.empty(T - 1, B, ns, n, **kw), torch.empty(T - 1, B, ns, **kw)
         K, k = torch.empty(T, B, nc, ns, **kw), torch.empty(T, B, nc, **kw)
         e, mws, mbytes, keep_e = net.to_struct(C)
+        if net.ctrl_carry:
+            if net.inner is None or net.ctrl_carry != nc:
+                raise ValueError("plan_network_iteration: a ctrl_carry spec comes from MlpSpec.augmented()")
+            le, lws, lbytes, keep_l = net.inner.to_struct(C)
+            lin_fn, lin_ns = L.mpc_mlp_linearize_carry, ns - nc
+        else:
+            le, lws, lbytes, keep_l = e, mws, mbytes, None
+            lin_fn, lin_ns = L.mpc_mlp_linearize, ns
         import copy
         so = copy.copy(opts)
         so.sweep_only, so.true_dynamics = True, None
@@ -1031,7 +1065,7 @@ class HipBackend:
         ro.sweep_only, ro.true_dynamics = False, None
         ro_struct, keep_ro = ro.to_struct(T, B, nc, C)
         fl, it = torch.empty(2, 5, B, **kw), torch.zeros(2, 2, B, device=dev, dtype=torch.int32)
-        sweeps, rolls, outs, keeps = [], [], [], [F, f, K, k, keep_e, keep_ro, fl, it]
+        sweeps, rolls, outs, keeps = [], [], [], [F, f, K, k, keep_e, keep_l, keep_ro, fl, it]
         for j in (0, 1):
             cx, cu = nominals[j]
             ox, ou = nominals[1 - j]
@@ -1064,21 +1098,22 @@ class HipBackend:
                 sweeps[j][1], sweeps[j][2] = st_, sout
             keeps.append(keep_s)
         bind_sweeps(so)
-        step_fn, lin_fn, roll_fn = L.mpc_lqr_step, L.mpc_mlp_linearize, L.mpc_mlp_rollout
+        step_fn, roll_fn = L.mpc_lqr_step, L.mpc_mlp_rollout
         ep, rop, wsp, mwsp = ctypes.byref(e), ctypes.byref(ro_struct), ws.data_ptr(), mws.data_ptr()
+        lep, lwsp = ctypes.byref(le), lws.data_ptr()
         Fp, fp, Kp, kp = F.data_ptr(), f.data_ptr(), K.data_ptr(), k.data_ptr()
 
         def run(j, stream=None):
             st = torch.cuda.current_stream(dev).cuda_stream if stream is None else stream
             sp, so_, sout, _ = sweeps[j]
             rp, rout, _, cxp, cup = rolls[j]
-            rc = lin_fn(ep, ns, nc, N, cxp, cup, Fp, fp, mwsp, mbytes, st)
+            rc = lin_fn(lep, lin_ns, nc, N, cxp, cup, Fp, fp, lwsp, lbytes, st)
             if rc == 0:
                 rc = step_fn(ctypes.byref(sp), ctypes.byref(so_), ctypes.byref(sout), wsp, nbytes, IMPL_AUTO, st)
             if rc == 0:
                 rc = roll_fn(ctypes.byref(rp), rop, ep, Kp, kp, outs[j]["old_costs"].data_ptr(), ctypes.byref(rout), mwsp, mbytes, st)
             if rc != 0:
-                _check(rc, "network iteration (mpc_mlp_linearize / mpc_lqr_step / mpc_mlp_rollout)")
+                _check(rc, "network iteration (mpc_mlp_linearize[_carry] / mpc_lqr_step / mpc_mlp_rollout)")
             return outs[j]
 
         def vouch_c():

@@ -175,7 +175,7 @@ class MPC(Module):
                  back_eps=1e-7, n_batch=None, linesearch_decay=0.2, max_linesearch_iter=10,
                  exit_unconverged=True, detach_unconverged=True, backprop=True, slew_rate_penalty=None,
                  prev_ctrl=None, not_improved_lim=5, best_cost_eps=1e-4, reference_du_norm=False,
-                 weight_grad_kernel=False):
+                 weight_grad_kernel=False, planned_network_slew=False):
         super().__init__()
         assert (u_lower is None) == (u_upper is None)
         assert max_linesearch_iter > 0
@@ -208,6 +208,12 @@ class MPC(Module):
         # mpc_mlp_param_grad backward) instead of the module through torch autograd.  Off by default: measured faster than the
         # module route at (12, 4, [100]) but slower at (32, 8, [100]) (docs/history/r10.md)
         self.weight_grad_kernel = bool(weight_grad_kernel)
+        # OPT-IN: a slew-rate penalty around an NNDynamics on the pre-bound device loop (`_iterate_slew` -> `_iterate_network` on the
+        # augmented problem, mpc_mlp_linearize_carry) instead of `_iterate_general`.  Off by default whatever it measures:
+        # tests/test_gpu_nn.py::test_slew_rate_penalty_on_the_network_kernels and tests/test_gpu_nn_wide.py::
+        # test_slew_rate_penalty_on_a_wide_network pin the general route by spying on HipBackend.mlp_rollout, a method a pre-bound
+        # iteration never goes through (it calls mpc_mlp_rollout itself), and existing tests are the yardstick of every change
+        self.planned_network_slew = bool(planned_network_slew)
         self.flag_reducer = None     # set by mpc.shard for lock-step sharded solves
         self.prev_ctrl = prev_ctrl
 
@@ -274,8 +280,9 @@ class MPC(Module):
             net = dx.native_net(x_init)
             if net is not None and net.activation == "elu":      # (no grad_input in the reference: the module refuses, mpc/dynamics.py:113-114)
                 net = None
-        # a slew-rate penalty on a QuadCost with LinDx or a shipped simulator: the same device-side loop on the augmented
-        # problem, which does not depend on the iterate and is built once (round 11; _iterate_general rebuilt it per iteration)
+        # a slew-rate penalty on a QuadCost with LinDx or a shipped simulator (or, with `planned_network_slew`, an NNDynamics):
+        # the same device-side loop on the augmented problem, which does not depend on the iterate and is built once (round 11;
+        # _iterate_general rebuilt it per iteration)
         slew = self._slew_plan(cost, dx, be, x_init)
         if fast or sim is not None:
             best = self._iterate_planned(be, x_init, u, cost, dx, sim, n_batch)
@@ -381,11 +388,14 @@ class MPC(Module):
 
     def _slew_plan(self, cost, dx, be, x_init):
         """Does this slew-rate solve run on the device-side loop (`_iterate_slew`)?  None = no: `_iterate_general`, as before
-        round 11.  Else what the dynamics are there: "lin" (LinDx) or the simulator's EnvSpec behind MPC_ENV_CTRL_CARRY.
+        round 11.  Else what the dynamics are there: "lin" (LinDx), the simulator's EnvSpec behind MPC_ENV_CTRL_CARRY, or the
+        augmented MlpSpec of an NNDynamics (`ctrl_carry`).
         All of: a QuadCost, a penalty, T > 1, each problem's own du norm (not `reference_du_norm` with B > 1), and either LinDx
         or a shipped simulator under ANALYTIC / AUTO_DIFF on a backend whose lane-per-problem kernel carries the control
         (`impl_supported`; FINITE_DIFF keeps the reference's central differences, module costs are not augmented by the
-        reference either)."""
+        reference either) or -- `planned_network_slew` only -- an NNDynamics the kernels take (`native_net`, not elu) under
+        ANALYTIC with n_state + n_ctrl <= 32 on a backend with `plan_network_iteration`, whose rollout kernels take the
+        augmented widths (`MlpSpec.augmented()` does not ask the LDS budget again: mpc_mlp_supported's rollout bit does here)."""
         if (not isinstance(cost, QuadCost) or self.slew_rate_penalty is None or self.T <= 1
                 or (self.reference_du_norm and x_init.size(0) > 1)):
             return None
@@ -397,6 +407,14 @@ class MPC(Module):
             if env.n_state == self.n_state + 1 and be.impl_supported(
                     env.n_state, 1, x_init.dtype, _native.IMPL_TINY, StepOptions(true_dynamics=env)):
                 return env
+        if (self.planned_network_slew and self.grad_method == GradMethods.ANALYTIC and hasattr(dx, "native_net")
+                and hasattr(be, "plan_network_iteration") and self.n_state + self.n_ctrl <= 32):
+            net = dx.native_net(x_init)
+            if net is not None and net.activation != "elu" and net.n_state == self.n_state and net.n_ctrl == self.n_ctrl:
+                aug = net.augmented()
+                # (bit 0 only: the augmented network is rolled out, never linearised -- that is `net` itself, which native_net vouched for)
+                if _native.MlpSpec.supported(aug.weights, aug.activation, x_init, bits=1):
+                    return aug
         return None
 
     def _iterate_slew(self, be, x_init, u, cost, dx, plan, n_batch):
@@ -404,11 +422,13 @@ class MPC(Module):
         0.5 gamma |u_t - u_{t-1}|^2 inside the stage cost.  (aC, ac, aF, af) are constant over the solve and built ONCE
         (mpc_slew_augment where the backend has it, else the torch composition); the augmented rollout of a step IS the next
         augmented nominal, so nothing is re-packed between iterations.  A simulator is carried through the kernels by
-        MPC_ENV_CTRL_CARRY (its F, f never exist).  `costs` include the penalty, as the reference's (its line search prices the
+        MPC_ENV_CTRL_CARRY (its F, f never exist); an NNDynamics (`plan` = its augmented MlpSpec) runs `_iterate_network` on the
+        augmented problem, whose linearisation kernel writes (aF, af) at every nominal.  `costs` include the penalty, as the reference's (its line search prices the
         augmented QuadCost); the first n_ctrl state columns are stripped from the best iterate."""
         nc = self.n_ctrl
         C, c = util.detach_maybe(cost.C), util.detach_maybe(cost.c)
         lin = isinstance(dx, LinDx)
+        network = isinstance(plan, _native.MlpSpec)
         F = util.detach_maybe(dx.F) if lin else None
         f = util.detach_maybe(dx.f) if lin else None
         if hasattr(be, "slew_augment") and C.is_cuda:
@@ -417,8 +437,13 @@ class MPC(Module):
             _, aC, ac, aF, af = self._slew_compose(C, c, F, f)
         prev_u = self._slew_prev_u(n_batch, dict(dtype=C.dtype, device=C.device))
         ax_init = torch.cat((prev_u[0], util.detach_maybe(x_init)), 1)
-        best = self._iterate_planned(be, ax_init, u, QuadCost(aC, ac), LinDx(aF, af) if lin else None,
-                                     None if lin else plan, n_batch)
+        if network:
+            from .dynamics import CtrlPassthroughDynamics
+            # (the module serves the first get_traj only; every later nominal is a rollout of the kernels)
+            best = self._iterate_network(be, ax_init, u, QuadCost(aC, ac), CtrlPassthroughDynamics(dx), plan, n_batch)
+        else:
+            best = self._iterate_planned(be, ax_init, u, QuadCost(aC, ac), LinDx(aF, af) if lin else None,
+                                         None if lin else plan, n_batch)
         best["x"] = best["x"][:, :, nc:].contiguous()
         return best
 
@@ -479,7 +504,12 @@ class MPC(Module):
         ua = util.detach_maybe(u).contiguous()
         if self.u_init is not None and ua.untyped_storage().data_ptr() == self.u_init.untyped_storage().data_ptr():
             ua = ua.clone()               # the iterations WRITE into the nominal buffers: never the caller's u_init
-        xa = util.get_traj(T, ua, x_init=xi, dynamics=dx).contiguous()
+        if hasattr(be, "mlp_traj_cost"):
+            # util.get_traj's own call for such a module, with the spec already in hand (`dx.native_net` would build it again --
+            # for the slew-rate augmentation a second set of concatenated weights)
+            xa = be.mlp_traj_cost(xi, ua.to(xi.dtype), net)[0].contiguous()
+        else:
+            xa = util.get_traj(T, ua, x_init=xi, dynamics=dx).contiguous()
         xb, ub = torch.empty_like(xa), torch.empty_like(ua)
         run, outs, vouch_c = be.plan_network_iteration(xi, cost.C, cost.c, net, self._step_options(), ((xa, ua), (xb, ub)))
         stream = torch.cuda.current_stream(xa.device).cuda_stream if xa.is_cuda else None

@@ -7,11 +7,15 @@ Rows:
   lin_box    the same with u in [-1, 1]
   pendulum   PendulumDx, T = 20, B = 1024, 10 iterations, the module's own bounds and line search
   cartpole   CartpoleDx, T = 25, B = 4096, 10 iterations, the module's own bounds and line search
+  nn         NNDynamics(12, 4, [100]), T = 50, B = 4096, float32, 5 iterations, gamma = 1, unbounded: `planned_network_slew=True`
+             (the pre-bound network loop on the augmented problem, mpc_mlp_linearize_carry) against the flag off (`_iterate_general`)
+  nn_box     the same with u in [-1, 1]
+  nn_wide    NNDynamics(20, 4, [32]), T = 64, B = 1024, unbounded (the two-tile kernels)
 
 The two routes alternate in one process after a warm-up solve of each; a solve is timed on the host clock from the call to a
 device synchronise behind it (MPC.forward reads its convergence flags back, so host time is part of a solve).  The record
 holds every repeat, the median and the spread (min, max).
-usage: python tools/slew_bench.py [--rows lin,lin_box,pendulum,cartpole] [--rounds 7] [--rounds-off 3]"""
+usage: python tools/slew_bench.py [--rows lin,lin_box,pendulum,cartpole,nn,nn_box,nn_wide] [--rounds 7] [--rounds-off 3]"""
 import argparse
 import json
 import os
@@ -67,6 +71,29 @@ def sim_row(kind, dev):
     return make, (x0, cost, dx), dict(kind=kind, T=T, B=B, lqr_iter=10, dtype="float32")
 
 
+def nn_row(row, dev):
+    from mpc import mpc
+    from mpc.dynamics import NNDynamics
+    from mpc.mpc import QuadCost
+    ns, nc, hidden, T, B = (20, 4, [32], 64, 1024) if row == "nn_wide" else (12, 4, [100], 50, 4096)
+    n = ns + nc
+    torch.manual_seed(3)
+    dyn = NNDynamics(ns, nc, hidden, activation="sigmoid").to(dev)
+    g = torch.Generator().manual_seed(4)
+    r = lambda *s: torch.randn(*s, generator=g, dtype=torch.float32)
+    L = r(T, B, n, n)
+    C = (L @ L.transpose(2, 3) / n + torch.eye(n)).to(dev)
+    c = r(T, B, n).to(dev)
+    x0 = r(B, ns).to(dev)
+    kw = dict(u_lower=-1.0, u_upper=1.0) if row == "nn_box" else {}
+
+    def make(flag=True):
+        return mpc.MPC(ns, nc, T, lqr_iter=5, verbose=-1, exit_unconverged=False, detach_unconverged=False, backprop=False,
+                       slew_rate_penalty=1.0, eps=0.0, grad_method=mpc.GradMethods.ANALYTIC, planned_network_slew=flag, **kw)
+    return make, (x0, QuadCost(C, c), dyn), dict(n_state=ns, n_ctrl=nc, hidden=hidden, T=T, B=B, lqr_iter=5, dtype="float32",
+                                                   box=row == "nn_box")
+
+
 def solve_ms(ctrl, args):
     torch.cuda.synchronize()
     t0 = time.perf_counter()
@@ -87,14 +114,19 @@ def main():
     dev = "cuda:0"
     res = {"device": torch.cuda.get_device_name(0), "rows": {}}
     for row in a.rows.split(","):
-        make, args, meta = (lin_row(row == "lin_box", dev) if row.startswith("lin") else sim_row(row, dev))
-        on, off = make(), make()
-        off._slew_plan = lambda *x, **k: None
+        if row.startswith("nn"):
+            make, args, meta = nn_row(row, dev)
+            on, off = make(True), make(False)          # (the route is opt-in: off is the constructor's default)
+            assert off._slew_plan(off._expand_cost(args[1], meta["B"]), args[2], _native.backend(), args[0]) is None
+        else:
+            make, args, meta = (lin_row(row == "lin_box", dev) if row.startswith("lin") else sim_row(row, dev))
+            on, off = make(), make()
+            off._slew_plan = lambda *x, **k: None
         assert on._slew_plan(on._expand_cost(args[1], meta["B"]), args[2], _native.backend(), args[0]) is not None, \
             "the predicate must fire on the new route"
         _, o_on = solve_ms(on, args)           # warm-up of either route at this shape
         _, o_off = solve_ms(off, args)
-        rounds_off = a.rounds if row.startswith("lin") else a.rounds_off
+        rounds_off = a.rounds if row.startswith(("lin", "nn")) else a.rounds_off
         w_on, w_off = [], []
         for i in range(a.rounds):              # the routes alternate
             w_on.append(solve_ms(on, args)[0])
