@@ -680,16 +680,7 @@ int mpc_env_param_grad(const mpc_env_dynamics *env, int dtype, int64_t N, const 
                                          (double *)gparams, (double *)workspace, st);
 }
 
-int64_t mpc_mlp_workspace_bytes(const mpc_mlp_dynamics *net)
-{
-    if (!net || net->n_layers < 1 || net->n_layers > MPC_MLP_MAX_LAYERS) return 0;
-    int64_t fl = 0;
-    for (int l = 0; l < net->n_layers; ++l) {
-        const int64_t in = (net->widths[l] + 15) & ~15, out = (net->widths[l + 1] + 15) & ~15;
-        fl += out * (in + 4) + out;          // rows padded by 16 bytes (LDS banks), see nn_dynamics.hip
-    }
-    return fl * 4 + 256;
-}
+int64_t mpc_mlp_workspace_bytes(const mpc_mlp_dynamics *net) { return nn_workspace_bytes(net); }
 
 int mpc_mlp_supported(const mpc_mlp_dynamics *net, int n_state, int n_ctrl) { return nn_budget(net, n_state, n_ctrl); }
 

@@ -25,6 +25,7 @@
 //
 // Weights are re-packed once per call into zero-padded [out_pad][in_pad] blocks (multiples of 16) in the workspace.
 #include <string>
+#include <type_traits>
 
 #include "lqr_common.h"
 
@@ -992,47 +993,22 @@ inline int check_launch(const char *what)
     return MPC_OK;
 }
 
+
+// ---- the host side: ONE layout, ONE validation, ONE plan per entry point, read by the budget query and by the launchers alike
 int pad16(int v) { return (v + 15) & ~15; }
 
-// validates the network, lays the packed block out in the workspace and launches the packing kernel
-int mlp_prepare(const mpc_mlp_dynamics *net, int ns, int nc, void *workspace, int64_t bytes, MlpDesc &d, hipStream_t st)
+// widths -> padded widths, offsets into the packed block, its size (returned in 64 bits: nothing has validated the widths yet)
+int64_t mlp_layout(const int *widths, int L, MlpDesc &d)
 {
-    if (!net) { set_last_error("network is NULL"); return MPC_E_NULL; }
-    if (net->n_layers < 1 || net->n_layers > MPC_MLP_MAX_LAYERS) { set_last_error("network: 1..4 Linear layers"); return MPC_E_ARG; }
-    if (net->activation < MPC_ACT_SIGMOID || net->activation > MPC_ACT_ELU) { set_last_error("network: unknown activation"); return MPC_E_ARG; }
-    if (net->widths[0] != ns + nc || net->widths[net->n_layers] != ns) { set_last_error("network: widths[0] must be n_state + n_ctrl, widths[L] n_state"); return MPC_E_DIMS; }
-    if (ns > 32) { set_last_error("network kernels: n_state <= 32"); return MPC_E_DIMS; }
-    for (int l = 0; l <= net->n_layers; ++l)
-        if (net->widths[l] < 1 || net->widths[l] > 4096) { set_last_error("network: layer width out of range"); return MPC_E_DIMS; }
-    if (mpc_mlp_workspace_bytes(net) > bytes || !workspace || ((uintptr_t)workspace & 15)) {
-        set_last_error("network: workspace too small or not 16-byte aligned (see mpc_mlp_workspace_bytes)");
-        return MPC_E_ARG;
+    int64_t off = 0;
+    d.L = L;
+    for (int l = 0; l <= L; ++l) d.wp[l] = pad16(d.w[l] = widths[l]);
+    for (int l = 0; l < L; ++l) {
+        d.woff[l] = (int)off; off += (int64_t)d.wp[l + 1] * (d.wp[l] + 4);     // rows padded by 16 bytes (LDS banks), see MlpDesc
+        d.boff[l] = (int)off; off += d.wp[l + 1];
     }
-    PackArgs a;
-    d.L = net->n_layers;
-    d.act = net->activation;
-    d.pass = net->passthrough ? 1 : 0;
-    d.carry = net->ctrl_carry;
-    if (d.carry != 0 && d.carry != nc) { set_last_error("network: ctrl_carry must be 0 or n_ctrl"); return MPC_E_ARG; }
-    if (d.carry >= ns) { set_last_error("network: ctrl_carry needs n_state (augmented) > n_ctrl"); return MPC_E_DIMS; }
-    for (int l = 0; l <= d.L; ++l) {
-        d.w[l] = net->widths[l];
-        d.wp[l] = pad16(net->widths[l]);
-    }
-    int off = 0;
-    for (int l = 0; l < d.L; ++l) {
-        if (!net->W[l] || !net->b[l]) { set_last_error("network: weight / bias pointer is NULL"); return MPC_E_NULL; }
-        a.W[l] = (const float *)net->W[l];
-        a.b[l] = (const float *)net->b[l];
-        d.woff[l] = off; off += d.wp[l + 1] * (d.wp[l] + 4);
-        d.boff[l] = off; off += d.wp[l + 1];
-    }
-    d.total = off;
-    d.packed = (const float *)workspace;
-    a.d = d;
-    a.dst = (float *)workspace;
-    hipLaunchKernelGGL(mlp_pack_kernel, dim3(64), dim3(256), 0, st, a);
-    return check_launch("mlp_pack_kernel");
+    d.total = (int)off;
+    return off;
 }
 
 int max_hidden_pad(const MlpDesc &d)
@@ -1042,50 +1018,155 @@ int max_hidden_pad(const MlpDesc &d)
     return h;
 }
 
+// The checks of a description in the order every caller reports them.  NULL, layer count and widths[0] / widths[L] always run,
+// the rest by group: a probe by widths alone has no activation, the weight gradient answers a network past the width range
+// with its own message, only mlp_prepare has a workspace, a ctrl_carry to honour and pointers to read.
+struct MlpCheck { int code; const char *msg; };
+enum : unsigned { CK_ACT = 1, CK_RANGE = 2, CK_BIND = 4 };
+
+MlpCheck mlp_check(const mpc_mlp_dynamics *net, int ns, int nc, unsigned what, const void *workspace = nullptr, int64_t bytes = 0)
+{
+    if (!net) return {MPC_E_NULL, "network is NULL"};
+    const int L = net->n_layers;
+    if (L < 1 || L > MPC_MLP_MAX_LAYERS) return {MPC_E_ARG, "network: 1..4 Linear layers"};
+    if ((what & CK_ACT) && (net->activation < MPC_ACT_SIGMOID || net->activation > MPC_ACT_ELU)) return {MPC_E_ARG, "network: unknown activation"};
+    if (net->widths[0] != ns + nc || net->widths[L] != ns) return {MPC_E_DIMS, "network: widths[0] must be n_state + n_ctrl, widths[L] n_state"};
+    if ((what & CK_RANGE) && ns > 32) return {MPC_E_DIMS, "network kernels: n_state <= 32"};
+    for (int l = 0; l <= L && (what & CK_RANGE); ++l)
+        if (net->widths[l] < 1 || net->widths[l] > 4096) return {MPC_E_DIMS, "network: layer width out of range"};
+    if (!(what & CK_BIND)) return {MPC_OK, nullptr};
+    if (nn_workspace_bytes(net) > bytes || !workspace || ((uintptr_t)workspace & 15))
+        return {MPC_E_ARG, "network: workspace too small or not 16-byte aligned (see mpc_mlp_workspace_bytes)"};
+    if (net->ctrl_carry != 0 && net->ctrl_carry != nc) return {MPC_E_ARG, "network: ctrl_carry must be 0 or n_ctrl"};
+    if (net->ctrl_carry >= ns) return {MPC_E_DIMS, "network: ctrl_carry needs n_state (augmented) > n_ctrl"};
+    for (int l = 0; l < L; ++l)
+        if (!net->W[l] || !net->b[l]) return {MPC_E_NULL, "network: weight / bias pointer is NULL"};
+    return {MPC_OK, nullptr};
+}
+
+int refuse(const MlpCheck &c) { set_last_error(c.msg); return c.code; }
+
+// validates the network, lays the packed block out in the workspace and launches the packing kernel
+int mlp_prepare(const mpc_mlp_dynamics *net, int ns, int nc, void *workspace, int64_t bytes, MlpDesc &d, hipStream_t st)
+{
+    const MlpCheck c = mlp_check(net, ns, nc, CK_ACT | CK_RANGE | CK_BIND, workspace, bytes);
+    if (c.code) return refuse(c);
+    PackArgs a;
+    mlp_layout(net->widths, net->n_layers, d);
+    d.act = net->activation;
+    d.pass = net->passthrough ? 1 : 0;
+    d.carry = net->ctrl_carry;
+    d.packed = (const float *)workspace;
+    for (int l = 0; l < d.L; ++l) a.W[l] = (const float *)net->W[l], a.b[l] = (const float *)net->b[l];
+    a.d = d;
+    a.dst = (float *)workspace;
+    hipLaunchKernelGGL(mlp_pack_kernel, dim3(64), dim3(256), 0, st, a);
+    return check_launch("mlp_pack_kernel");
+}
+
 // LDS budget of a workgroup: the packed network (when it is staged) + one staging area per wavefront
 constexpr size_t LDS_MAX = 160 * 1024, WEIGHTS_IN_LDS_MAX = 96 * 1024;
 
-template <typename K> void allow_lds(K kernel, size_t lds)
+// What a launch of the rollout / the linearisation does with a network, `groups` of sixteen problems each
+struct NnPlan {
+    bool fits;                         // false: too wide.  Independent of `groups`: nw shrinks to 1 before a launch is refused
+    bool fast, wide, wl;               // the register-resident kernels (no staging) / two state tiles (n_state > 16) / weights in LDS
+    int ht;                            // fast: the compile-time hidden-tile bucket, 2, 4, 7 or 8
+    int TS, ZS, GT, wave_floats, nw;   // the general kernels: staging strides, floats per wavefront, wavefronts per workgroup
+    size_t lds;
+    unsigned grid;
+};
+
+NnPlan nn_plan(const MlpDesc &d, bool jacobian, bool entry_allows_fast, long groups)
+{
+    NnPlan pl = {};
+    pl.wide = d.w[d.L] > 16;
+    // one hidden layer of <= 128 units, n <= 16: the network lives in registers, one wavefront per workgroup
+    pl.fast = entry_allows_fast && d.L == 2 && d.wp[0] == 16 && d.wp[1] <= 128;
+    if (pl.fast) {
+        const int ht = d.wp[1] >> 4;
+        pl.ht = ht <= 2 ? 2 : (ht <= 4 ? 4 : (ht <= 7 ? 7 : 8));
+        pl.nw = 1;
+        pl.grid = (unsigned)groups;
+        pl.fits = true;
+        return pl;
+    }
+    const int NTJ = d.wp[0] >> 4;
+    pl.TS = d.wp[0] + 4;
+    pl.ZS = max_hidden_pad(d) + 4;
+    pl.GT = 1;
+    for (int l = 1; l < d.L; ++l) pl.GT = (d.wp[l] >> 4) * NTJ > pl.GT ? (d.wp[l] >> 4) * NTJ : pl.GT;
+    pl.wave_floats = jacobian ? 16 * pl.TS + (d.L > 1 ? d.L - 1 : 1) * 16 * pl.ZS + 2 * pl.GT * 64 * 4 : 2 * 16 * pl.TS + 2 * 16 * pl.ZS;
+    const size_t wbytes = (size_t)d.total * 4, per_wave = (size_t)pl.wave_floats * 4;
+    pl.wl = wbytes <= WEIGHTS_IN_LDS_MAX && wbytes + per_wave <= LDS_MAX;
+    pl.fits = pl.wl || per_wave <= LDS_MAX;
+    // few groups -> one wavefront per workgroup so that every CU gets one
+    pl.nw = jacobian && groups >= 4096 ? 8 : (groups >= 2048 ? 4 : (groups >= 1024 ? 2 : 1));
+    while (pl.nw > 1 && (pl.wl ? wbytes : 0) + pl.nw * per_wave > LDS_MAX) pl.nw >>= 1;
+    pl.lds = (pl.wl ? wbytes : 0) + pl.nw * per_wave;
+    pl.grid = (unsigned)((groups + pl.nw - 1) / pl.nw);
+    return pl;
+}
+
+// rows16: rows readable 16 bytes at a time; the register-resident rollout needs that and n_ctrl <= 4.  A probe that cannot know
+// passes false and gets the general kernel's budget, which always holds a network this small (19 KiB a wavefront): the same answer.
+NnPlan plan_rollout(const MlpDesc &d, int ns, int nc, bool rows16, long groups) { return nn_plan(d, false, nc <= 4 && rows16, groups); }
+NnPlan plan_linearize(const MlpDesc &d, long groups) { return nn_plan(d, true, true, groups); }
+
+const MlpCheck TOO_WIDE = {MPC_E_DIMS, "network: layers too wide for the LDS-resident kernel"};
+
+// runtime value -> template argument: f is a generic lambda and receives a std::integral_constant
+template <int V> using Int = std::integral_constant<int, V>;
+template <bool V> using Bool = std::integral_constant<bool, V>;
+template <typename F> void with_ht(int b, F &&f) { b == 2 ? f(Int<2>{}) : (b == 4 ? f(Int<4>{}) : (b == 7 ? f(Int<7>{}) : f(Int<8>{}))); }
+template <typename F> void with_act(int a, F &&f)
+{
+    a == MPC_ACT_SIGMOID ? f(Int<MPC_ACT_SIGMOID>{}) : (a == MPC_ACT_RELU ? f(Int<MPC_ACT_RELU>{}) : f(Int<MPC_ACT_ELU>{}));
+}
+template <typename F> void with_bools(bool a, bool b, F &&f)
+{
+    a ? (b ? f(Bool<true>{}, Bool<true>{}) : f(Bool<true>{}, Bool<false>{})) : (b ? f(Bool<false>{}, Bool<true>{}) : f(Bool<false>{}, Bool<false>{}));
+}
+
+// a kernel with dynamic LDS: past 64 KiB the runtime wants to be told
+template <typename K, typename... A> void launch_staged(K kernel, unsigned grid, int nw, size_t lds, hipStream_t st, A... args)
 {
     if (lds > 64 * 1024)
         (void)hipFuncSetAttribute(reinterpret_cast<const void *>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+    hipLaunchKernelGGL(kernel, dim3(grid), dim3(64 * nw), lds, st, args...);
 }
 
 #include "nn_param_grad.h"
 
 }  // namespace
 
-// Does the general (LDS-staged) kernel of either entry point fit a network of these layer widths?  The same two budget
-// tests the launchers below apply -- exported as mpc_mlp_supported so that a caller can ask BEFORE it routes a module here
-// (a 1024-unit layer is a legal NNDynamics, it just keeps the host-driven path).  bit 0: rollout, bit 1: linearisation,
-// bit 2: the linearisation's weight gradient (nn_param_grad.h: sigmoid / relu, no ctrl_carry, at most PG_MAX_TILES tiles of gW,
-// one point's matrices in LDS).
+// the packed network + slack for alignment; for any description with a legal layer count (nothing else is looked at)
+int64_t nn_workspace_bytes(const mpc_mlp_dynamics *net)
+{
+    if (!net || net->n_layers < 1 || net->n_layers > MPC_MLP_MAX_LAYERS) return 0;
+    MlpDesc d;
+    return mlp_layout(net->widths, net->n_layers, d) * 4 + 256;
+}
+
+// Do the kernels take this network?  The plans the launchers below execute, at one group -- exported as mpc_mlp_supported so
+// that a caller can ask BEFORE it routes a module here (a 1024-unit layer is a legal NNDynamics, it keeps the host-driven path).
+// bit 0: rollout, bit 1: linearisation, bit 2: its weight gradient (nn_param_grad.h: sigmoid / relu, no ctrl_carry, at most
+// PG_MAX_TILES tiles of gW, one point's matrices in LDS) -- answered for a complete description only (W, b non-NULL): a probe
+// by widths alone, all that bits 0 and 1 need, keeps its answer.  Silent; d is laid out past validation, pl is valid with bit 2.
+static int nn_describe(const mpc_mlp_dynamics *net, int ns, int nc, MlpDesc &d, PgPlan &pl)
+{
+    if (ns < 1 || nc < 1 || mlp_check(net, ns, nc, CK_RANGE).code) return 0;
+    mlp_layout(net->widths, net->n_layers, d);
+    bool grad = (net->activation == MPC_ACT_SIGMOID || net->activation == MPC_ACT_RELU) && net->ctrl_carry == 0;
+    for (int l = 0; l < d.L; ++l) grad = grad && net->W[l] && net->b[l];
+    return (plan_rollout(d, ns, nc, false, 1).fits ? 1 : 0) | (plan_linearize(d, 1).fits ? 2 : 0) | (grad && pg_plan(d, ns, nc, pl) ? 4 : 0);
+}
+
 int nn_budget(const mpc_mlp_dynamics *net, int ns, int nc)
 {
-    if (!net || net->n_layers < 1 || net->n_layers > MPC_MLP_MAX_LAYERS || ns < 1 || ns > 32 || nc < 1) return 0;
-    if (net->widths[0] != ns + nc || net->widths[net->n_layers] != ns) return 0;
-    int wp[MPC_MLP_MAX_LAYERS + 1], total = 0, hid = 16;
-    for (int l = 0; l <= net->n_layers; ++l) {
-        if (net->widths[l] < 1 || net->widths[l] > 4096) return 0;
-        wp[l] = pad16(net->widths[l]);
-    }
-    for (int l = 0; l < net->n_layers; ++l) total += wp[l + 1] * (wp[l] + 4) + wp[l + 1];
-    for (int l = 1; l < net->n_layers; ++l) hid = wp[l] > hid ? wp[l] : hid;
-    const int TS = wp[0] + 4, ZS = hid + 4, NTJ = wp[0] >> 4, L = net->n_layers;
-    int GT = 1;
-    for (int l = 1; l < L; ++l) GT = (wp[l] >> 4) * NTJ > GT ? (wp[l] >> 4) * NTJ : GT;
-    const size_t wbytes = (size_t)total * 4;
-    const size_t roll = (size_t)(2 * 16 * TS + 2 * 16 * ZS) * 4;
-    const size_t lin = (size_t)(16 * TS + (L > 1 ? L - 1 : 1) * 16 * ZS + 2 * GT * 64 * 4) * 4;
-    auto fits = [&](size_t per_wave) { return (wbytes <= WEIGHTS_IN_LDS_MAX && wbytes + per_wave <= LDS_MAX) || per_wave <= LDS_MAX; };
-    const bool fast = L == 2 && wp[0] == 16 && wp[1] <= 128;          // the register-resident kernels: no staging at all
-    // bit 2 is answered for a complete description only (weights and biases non-NULL): a probe by widths alone, which is all
-    // that bits 0 and 1 need and what callers older than this bit compare with == 3, keeps its answer
+    MlpDesc d;
     PgPlan pl;
-    bool grad = (net->activation == MPC_ACT_SIGMOID || net->activation == MPC_ACT_RELU) && net->ctrl_carry == 0;
-    for (int l = 0; l < L; ++l) grad = grad && net->W[l] && net->b[l];
-    grad = grad && pg_plan(net->widths, L, ns, nc, pl);
-    return ((fast || fits(roll)) ? 1 : 0) | ((fast || fits(lin)) ? 2 : 0) | (grad ? 4 : 0);
+    return nn_describe(net, ns, nc, d, pl);
 }
 
 int launch_nn_rollout(const StepParams<float> &p, const mpc_mlp_dynamics *net, void *workspace, int64_t bytes, hipStream_t st)
@@ -1094,58 +1175,24 @@ int launch_nn_rollout(const StepParams<float> &p, const mpc_mlp_dynamics *net, v
     int rc = mlp_prepare(net, p.ns, p.nc, workspace, bytes, d, st);
     if (rc) return rc;
     const bool rows16 = (p.ns & 3) == 0 && ((p.ns + p.nc) & 3) == 0 && (!p.C || ((p.C_st & 3) == 0 && (p.C_sb & 3) == 0));
-    if (d.L == 2 && d.wp[0] == 16 && d.wp[1] <= 128 && p.nc <= 4 && rows16) {
-        // one hidden layer of <= 128 units, n <= 16: the register-resident kernel
-        const unsigned g = (unsigned)(((long)p.B + 15) / 16);
-        const int ht = d.wp[1] >> 4;
-        const int mode = p.K ? 2 : (p.C ? 1 : 0);
-#define MPC_NN_LAUNCH_A(HT_, ACT_)                                                                                                \
-        do {                                                                                                                       \
-            if (mode == 2) hipLaunchKernelGGL((nn_rollout_fast_kernel<HT_, true, true, ACT_>), dim3(g), dim3(64), 0, st, p, d);      \
-            else if (mode == 1) hipLaunchKernelGGL((nn_rollout_fast_kernel<HT_, false, true, ACT_>), dim3(g), dim3(64), 0, st, p, d); \
-            else hipLaunchKernelGGL((nn_rollout_fast_kernel<HT_, false, false, ACT_>), dim3(g), dim3(64), 0, st, p, d);              \
-        } while (0)
-#define MPC_NN_LAUNCH(HT_)                                                                  \
-        do {                                                                                 \
-            if (d.act == MPC_ACT_SIGMOID) MPC_NN_LAUNCH_A(HT_, MPC_ACT_SIGMOID);             \
-            else if (d.act == MPC_ACT_RELU) MPC_NN_LAUNCH_A(HT_, MPC_ACT_RELU);              \
-            else MPC_NN_LAUNCH_A(HT_, MPC_ACT_ELU);                                          \
-        } while (0)
-        if (ht <= 2) MPC_NN_LAUNCH(2);
-        else if (ht <= 4) MPC_NN_LAUNCH(4);
-        else if (ht <= 7) MPC_NN_LAUNCH(7);
-        else MPC_NN_LAUNCH(8);
-#undef MPC_NN_LAUNCH_A
-#undef MPC_NN_LAUNCH
+    const NnPlan pl = plan_rollout(d, p.ns, p.nc, rows16, ((long)p.B + 15) / 16);
+    if (!pl.fits) return refuse(TOO_WIDE);
+    if (pl.fast) {
+        with_ht(pl.ht, [&](auto HT) {
+            with_act(d.act, [&](auto ACT) {
+                constexpr int H = decltype(HT)::value, A = decltype(ACT)::value;
+                auto kernel = p.K ? nn_rollout_fast_kernel<H, true, true, A>
+                                  : (p.C ? nn_rollout_fast_kernel<H, false, true, A> : nn_rollout_fast_kernel<H, false, false, A>);
+                hipLaunchKernelGGL(kernel, dim3(pl.grid), dim3(64), 0, st, p, d);
+            });
+        });
         return check_launch("nn_rollout_fast_kernel");
     }
-    const int TS = d.wp[0] + 4, ZS = max_hidden_pad(d) + 4;
-    const int wave_floats = 2 * 16 * TS + 2 * 16 * ZS;
-    const size_t wbytes = (size_t)d.total * 4, per_wave = (size_t)wave_floats * 4;
-    const bool wl = wbytes <= WEIGHTS_IN_LDS_MAX && wbytes + per_wave <= LDS_MAX;
-    if (!wl && per_wave > LDS_MAX) { set_last_error("network: layers too wide for the LDS-resident kernel"); return MPC_E_DIMS; }
-    // sixteen problems per wavefront; few groups -> one wavefront per workgroup so that every CU gets one
-    const long groups = ((long)p.B + 15) / 16;
-    int nw = groups >= 2048 ? 4 : (groups >= 1024 ? 2 : 1);
-    while (nw > 1 && (wl ? wbytes : 0) + nw * per_wave > LDS_MAX) nw >>= 1;
-    const size_t lds = (wl ? wbytes : 0) + nw * per_wave;
-    const unsigned grid = (unsigned)((groups + nw - 1) / nw);
-    if (p.ns > 16) {
-        // two state tiles (the extra one lives in registers: same staging, same grid)
-        if (wl) {
-            allow_lds(&nn_wide_rollout_kernel<true>, lds);
-            hipLaunchKernelGGL(nn_wide_rollout_kernel<true>, dim3(grid), dim3(64 * nw), lds, st, p, d, TS, ZS, wave_floats);
-        } else {
-            allow_lds(&nn_wide_rollout_kernel<false>, lds);
-            hipLaunchKernelGGL(nn_wide_rollout_kernel<false>, dim3(grid), dim3(64 * nw), lds, st, p, d, TS, ZS, wave_floats);
-        }
-    } else if (wl) {
-        allow_lds(&nn_rollout_kernel<true>, lds);
-        hipLaunchKernelGGL(nn_rollout_kernel<true>, dim3(grid), dim3(64 * nw), lds, st, p, d, TS, ZS, wave_floats);
-    } else {
-        allow_lds(&nn_rollout_kernel<false>, lds);
-        hipLaunchKernelGGL(nn_rollout_kernel<false>, dim3(grid), dim3(64 * nw), lds, st, p, d, TS, ZS, wave_floats);
-    }
+    with_bools(pl.wl, pl.wide, [&](auto WL, auto WIDE) {
+        constexpr bool S = decltype(WL)::value;
+        launch_staged(decltype(WIDE)::value ? nn_wide_rollout_kernel<S> : nn_rollout_kernel<S>, pl.grid, pl.nw, pl.lds, st, p, d, pl.TS, pl.ZS,
+                      pl.wave_floats);
+    });
     return check_launch("nn_rollout_kernel");
 }
 
@@ -1156,63 +1203,36 @@ static int launch_linearize(const mpc_mlp_dynamics *net, long N, int ns, int nc,
     MlpDesc d;
     int rc = mlp_prepare(net, ns, nc, workspace, bytes, d, st);
     if (rc) return rc;
-    if (d.L == 2 && d.wp[0] == 16 && d.wp[1] <= 128) {
-        const unsigned g = (unsigned)((N + 15) / 16);
-        const int ht = d.wp[1] >> 4;
-#define MPC_NN_LIN(HT_)                                                                                                             \
-        do {                                                                                                                        \
-            if (d.act == MPC_ACT_SIGMOID) hipLaunchKernelGGL((nn_linearize_fast_kernel<HT_, MPC_ACT_SIGMOID>), dim3(g), dim3(64), 0, st, d, N, ns, nc, x, u, F, f, lay); \
-            else if (d.act == MPC_ACT_RELU) hipLaunchKernelGGL((nn_linearize_fast_kernel<HT_, MPC_ACT_RELU>), dim3(g), dim3(64), 0, st, d, N, ns, nc, x, u, F, f, lay);   \
-            else hipLaunchKernelGGL((nn_linearize_fast_kernel<HT_, MPC_ACT_ELU>), dim3(g), dim3(64), 0, st, d, N, ns, nc, x, u, F, f, lay);                              \
-        } while (0)
-        if (ht <= 2) MPC_NN_LIN(2);
-        else if (ht <= 4) MPC_NN_LIN(4);
-        else if (ht <= 7) MPC_NN_LIN(7);
-        else MPC_NN_LIN(8);
-#undef MPC_NN_LIN
+    const NnPlan pl = plan_linearize(d, (N + 15) / 16);
+    if (!pl.fits) return refuse(TOO_WIDE);
+    if (pl.fast) {
+        with_ht(pl.ht, [&](auto HT) {
+            with_act(d.act, [&](auto ACT) {
+                hipLaunchKernelGGL((nn_linearize_fast_kernel<decltype(HT)::value, decltype(ACT)::value>), dim3(pl.grid), dim3(64), 0, st, d, N,
+                                   ns, nc, x, u, F, f, lay);
+            });
+        });
         return check_launch("nn_linearize_fast_kernel");
     }
-    const int TS = d.wp[0] + 4, ZS = max_hidden_pad(d) + 4, NTJ = d.wp[0] >> 4;
-    int GT = 1;
-    for (int l = 1; l < d.L; ++l) GT = (d.wp[l] >> 4) * NTJ > GT ? (d.wp[l] >> 4) * NTJ : GT;
-    const int wave_floats = 16 * TS + (d.L > 1 ? d.L - 1 : 1) * 16 * ZS + 2 * GT * 64 * 4;
-    const size_t wbytes = (size_t)d.total * 4, per_wave = (size_t)wave_floats * 4;
-    const bool wl = wbytes <= WEIGHTS_IN_LDS_MAX && wbytes + per_wave <= LDS_MAX;
-    if (!wl && per_wave > LDS_MAX) { set_last_error("network: layers too wide for the LDS-resident kernel"); return MPC_E_DIMS; }
-    const long groups = (N + 15) / 16;
-    int nw = groups >= 4096 ? 8 : (groups >= 2048 ? 4 : (groups >= 1024 ? 2 : 1));
-    while (nw > 1 && (wl ? wbytes : 0) + nw * per_wave > LDS_MAX) nw >>= 1;
-    const size_t lds = (wl ? wbytes : 0) + nw * per_wave;
-    const unsigned grid = (unsigned)((groups + nw - 1) / nw);
-    if (ns > 16) {
-        if (wl) {
-            allow_lds(&nn_wide_linearize_kernel<true>, lds);
-            hipLaunchKernelGGL(nn_wide_linearize_kernel<true>, dim3(grid), dim3(64 * nw), lds, st, d, N, ns, nc, x, u, F, f, lay, TS, ZS, GT, wave_floats);
-        } else {
-            allow_lds(&nn_wide_linearize_kernel<false>, lds);
-            hipLaunchKernelGGL(nn_wide_linearize_kernel<false>, dim3(grid), dim3(64 * nw), lds, st, d, N, ns, nc, x, u, F, f, lay, TS, ZS, GT, wave_floats);
-        }
-    } else if (wl) {
-        allow_lds(&nn_linearize_kernel<true>, lds);
-        hipLaunchKernelGGL(nn_linearize_kernel<true>, dim3(grid), dim3(64 * nw), lds, st, d, N, ns, nc, x, u, F, f, lay, TS, ZS, GT, wave_floats);
-    } else {
-        allow_lds(&nn_linearize_kernel<false>, lds);
-        hipLaunchKernelGGL(nn_linearize_kernel<false>, dim3(grid), dim3(64 * nw), lds, st, d, N, ns, nc, x, u, F, f, lay, TS, ZS, GT, wave_floats);
-    }
+    with_bools(pl.wl, pl.wide, [&](auto WL, auto WIDE) {
+        constexpr bool S = decltype(WL)::value;
+        launch_staged(decltype(WIDE)::value ? nn_wide_linearize_kernel<S> : nn_linearize_kernel<S>, pl.grid, pl.nw, pl.lds, st, d, N, ns, nc,
+                      x, u, F, f, lay, pl.TS, pl.ZS, pl.GT, pl.wave_floats);
+    });
     return check_launch("nn_linearize_kernel");
 }
 
 int launch_nn_linearize(const mpc_mlp_dynamics *net, long N, int ns, int nc, const float *x, const float *u, float *F,
                         float *f, void *workspace, int64_t bytes, hipStream_t st)
 {
-    if (net && net->ctrl_carry) { set_last_error("mlp_linearize: ctrl_carry describes a rollout only (linearise the network itself)"); return MPC_E_ARG; }
+    if (net && net->ctrl_carry) return refuse({MPC_E_ARG, "mlp_linearize: ctrl_carry describes a rollout only (linearise the network itself)"});
     return launch_linearize(net, N, ns, nc, x, u, F, f, dense_layout(ns, nc), workspace, bytes, st);
 }
 
 int launch_nn_linearize_carry(const mpc_mlp_dynamics *net, long N, int ns, int nc, const float *z, const float *u, float *aF,
                               float *af, void *workspace, int64_t bytes, hipStream_t st)
 {
-    if (net && net->ctrl_carry) { set_last_error("mlp_linearize_carry: pass the network itself (ctrl_carry = 0), not its augmentation"); return MPC_E_ARG; }
+    if (net && net->ctrl_carry) return refuse({MPC_E_ARG, "mlp_linearize_carry: pass the network itself (ctrl_carry = 0), not its augmentation"});
     return launch_linearize(net, N, ns, nc, z, u, aF, af, carry_layout(ns, nc), workspace, bytes, st);
 }
 
@@ -1221,61 +1241,46 @@ int64_t nn_param_grad_workspace_bytes(const mpc_mlp_dynamics *net, int64_t N)
 {
     if (!net || net->n_layers < 1 || net->n_layers > MPC_MLP_MAX_LAYERS) return -1;
     const int ns = net->widths[net->n_layers], nc = net->widths[0] - ns;
-    if (!(nn_budget(net, ns, nc) & 4)) return -1;
+    MlpDesc d;
     PgPlan pl;
-    pg_plan(net->widths, net->n_layers, ns, nc, pl);
-    const int64_t packed = (mpc_mlp_workspace_bytes(net) + 255) & ~(int64_t)255;
-    const int blocks = pg_blocks(N < 0 ? 0 : (long)N, pl.nw);
-    return packed + (int64_t)(blocks > 0 ? blocks : 1) * pl.g.psize * 4;
+    if (!(nn_describe(net, ns, nc, d, pl) & 4)) return -1;
+    return pg_workspace_bytes(pl, N < 0 ? 0 : (long)N);
 }
 
 int launch_nn_param_grad(const mpc_mlp_dynamics *net, long N, int ns, int nc, const float *x, const float *u, const float *gF,
                          const float *gf, const mpc_mlp_param_grads *out, void *workspace, int64_t bytes, hipStream_t st)
 {
-    if (!net) { set_last_error("network is NULL"); return MPC_E_NULL; }
-    if (net->ctrl_carry) { set_last_error("mlp_param_grad: ctrl_carry describes a rollout only (differentiate the network itself)"); return MPC_E_DIMS; }
-    if (net->activation == MPC_ACT_ELU) { set_last_error("mlp_param_grad: sigmoid and relu only (an ELU network keeps the module path)"); return MPC_E_DIMS; }
-    if (net->n_layers < 1 || net->n_layers > MPC_MLP_MAX_LAYERS) { set_last_error("network: 1..4 Linear layers"); return MPC_E_ARG; }
-    if (net->activation < MPC_ACT_SIGMOID || net->activation > MPC_ACT_ELU) { set_last_error("network: unknown activation"); return MPC_E_ARG; }
-    if (net->widths[0] != ns + nc || net->widths[net->n_layers] != ns) { set_last_error("network: widths[0] must be n_state + n_ctrl, widths[L] n_state"); return MPC_E_DIMS; }
-    const int64_t need = nn_param_grad_workspace_bytes(net, N);
-    if (need < 0) { set_last_error("mlp_param_grad: the network is outside the kernel (see mpc_mlp_supported, bit 2)"); return MPC_E_DIMS; }
-    if (bytes < need) { set_last_error("mlp_param_grad: workspace too small (see mpc_mlp_param_grad_workspace_bytes)"); return MPC_E_DIMS; }
+    // this entry's own refusals come before anything else, as MPC_E_DIMS (the module path keeps such a network)
+    if (net && net->ctrl_carry) return refuse({MPC_E_DIMS, "mlp_param_grad: ctrl_carry describes a rollout only (differentiate the network itself)"});
+    if (net && net->activation == MPC_ACT_ELU) return refuse({MPC_E_DIMS, "mlp_param_grad: sigmoid and relu only (an ELU network keeps the module path)"});
+    const MlpCheck c = mlp_check(net, ns, nc, CK_ACT);
+    if (c.code) return refuse(c);
     MlpDesc d;
+    PgPlan pl;
+    if (!(nn_describe(net, ns, nc, d, pl) & 4)) return refuse({MPC_E_DIMS, "mlp_param_grad: the network is outside the kernel (see mpc_mlp_supported, bit 2)"});
+    if (bytes < pg_workspace_bytes(pl, N)) return refuse({MPC_E_DIMS, "mlp_param_grad: workspace too small (see mpc_mlp_param_grad_workspace_bytes)"});
     int rc = mlp_prepare(net, ns, nc, workspace, bytes, d, st);
     if (rc) return rc;
-    PgPlan pl;
-    pg_plan(net->widths, d.L, ns, nc, pl);
-    const int64_t packed = (mpc_mlp_workspace_bytes(net) + 255) & ~(int64_t)255;
-    float *partials = reinterpret_cast<float *>(static_cast<char *>(workspace) + packed);
+    float *partials = reinterpret_cast<float *>(static_cast<char *>(workspace) + pl.packed_bytes);
     const int blocks = pg_blocks(N, pl.nw);
     if (blocks > 0) {
-#define MPC_NN_PG(WL_, MAXT_)                                                                                                       \
-        do {                                                                                                                        \
-            allow_lds(&nn_param_grad_kernel<WL_, MAXT_>, pl.lds);                                                                   \
-            hipLaunchKernelGGL((nn_param_grad_kernel<WL_, MAXT_>), dim3(blocks), dim3(64 * pl.nw), pl.lds, st, d, pl.g, N, ns, nc, x, u, \
-                               gF, gf, partials, pl.TS, pl.ZS, pl.wave_floats);                                                     \
-        } while (0)
-        if (pl.g.ntiles <= 16) { if (pl.wl) MPC_NN_PG(true, 16); else MPC_NN_PG(false, 16); }
-        else { if (pl.wl) MPC_NN_PG(true, PG_MAX_TILES); else MPC_NN_PG(false, PG_MAX_TILES); }
-#undef MPC_NN_PG
+        with_bools(pl.wl, pl.g.ntiles > 16, [&](auto WL, auto MANY) {
+            launch_staged(nn_param_grad_kernel<decltype(WL)::value, decltype(MANY)::value ? PG_MAX_TILES : 16>, (unsigned)blocks, pl.nw, pl.lds,
+                          st, d, pl.g, N, ns, nc, x, u, gF, gf, partials, pl.TS, pl.ZS, pl.wave_floats);
+        });
         rc = check_launch("nn_param_grad_kernel");
         if (rc) return rc;
     }
-    PgFinalArgs a;
-    a.L = d.L;
-    a.ntiles = pl.g.ntiles;
-    a.psize = pl.g.psize;
-    a.nparts = blocks;
+    PgFinalArgs a = {d.L, pl.g.ntiles, pl.g.psize, blocks};          // (layers past L: zeros and NULL)
     a.partials = partials;
     long entries = 0;
     for (int l = 0; l <= d.L; ++l) { a.w[l] = d.w[l]; a.wp[l] = d.wp[l]; }
-    for (int k = 0; k < MPC_MLP_MAX_LAYERS; ++k) {
-        a.tbase[k] = k < d.L ? pl.g.tbase[k] : 0;
-        a.gboff[k] = k < d.L ? pl.g.gboff[k] : 0;
-        a.gW[k] = k < d.L ? (float *)out->gW[k] : nullptr;
-        a.gb[k] = k < d.L ? (float *)out->gb[k] : nullptr;
-        if (k < d.L) entries += (long)d.w[k + 1] * d.w[k] + d.w[k + 1];
+    for (int k = 0; k < d.L; ++k) {
+        a.tbase[k] = pl.g.tbase[k];
+        a.gboff[k] = pl.g.gboff[k];
+        a.gW[k] = (float *)out->gW[k];
+        a.gb[k] = (float *)out->gb[k];
+        entries += (long)d.w[k + 1] * d.w[k] + d.w[k + 1];
     }
     hipLaunchKernelGGL(nn_param_grad_final_kernel, dim3((unsigned)((entries + 255) / 256)), dim3(256), 0, st, a);
     return check_launch("nn_param_grad_final_kernel");

@@ -294,14 +294,12 @@ struct PgPlan {
     int TS, ZS, wave_floats, nw;
     bool wl;
     size_t lds;
+    int64_t packed_bytes;              // the packed network's share of the workspace (the partials follow, 256-byte aligned)
 };
 
-bool pg_plan(const int *w, int L, int ns, int nc, PgPlan &pl)
+bool pg_plan(const MlpDesc &d, int ns, int nc, PgPlan &pl)
 {
-    int wp[MPC_MLP_MAX_LAYERS + 1], total = 0, hid = 16;
-    for (int l = 0; l <= L; ++l) wp[l] = pad16(w[l]);
-    for (int l = 0; l < L; ++l) total += wp[l + 1] * (wp[l] + 4) + wp[l + 1];
-    for (int l = 1; l < L; ++l) hid = wp[l] > hid ? wp[l] : hid;
+    const int *wp = d.wp, L = d.L;
     PgDesc &g = pl.g;
     g.NC = pad16(ns + nc + 1);
     g.JS = g.NC + 4;
@@ -329,9 +327,9 @@ bool pg_plan(const int *w, int L, int ns, int nc, PgPlan &pl)
     g.psize = nt * 256 + gb;
     g.mat_floats = off;
     pl.TS = wp[0] + 4;
-    pl.ZS = hid + 4;
+    pl.ZS = max_hidden_pad(d) + 4;
     pl.wave_floats = 16 * pl.TS + (L > 1 ? L - 1 : 1) * 16 * pl.ZS + off + gb;
-    const size_t wbytes = (size_t)total * 4, per_wave = (size_t)(pl.wave_floats + 256) * 4;       // (+ the wave's row of `red`)
+    const size_t wbytes = (size_t)d.total * 4, per_wave = (size_t)(pl.wave_floats + 256) * 4;       // (+ the wave's row of `red`)
     const int nw_g = (int)(LDS_MAX / per_wave);
     const int nw_l = wbytes <= WEIGHTS_IN_LDS_MAX && wbytes < LDS_MAX ? (int)((LDS_MAX - wbytes) / per_wave) : 0;
     if (nw_g < 1) return false;
@@ -339,6 +337,7 @@ bool pg_plan(const int *w, int L, int ns, int nc, PgPlan &pl)
     pl.wl = nw_l >= 1 && cap(nw_l) >= cap(nw_g) - 1 && 2 * cap(nw_l) >= cap(nw_g);      // staged weights unless they cost half the waves
     pl.nw = cap(pl.wl ? nw_l : nw_g);
     pl.lds = (pl.wl ? wbytes : 0) + pl.nw * per_wave;
+    pl.packed_bytes = ((int64_t)d.total * 4 + 256 + 255) & ~(int64_t)255;
     return true;
 }
 
@@ -346,4 +345,11 @@ int pg_blocks(long N, int nw)
 {
     const long groups = (N + 15) / 16, b = (groups + nw - 1) / nw;
     return (int)(b > PG_MAX_BLOCKS ? PG_MAX_BLOCKS : b);
+}
+
+// the packed network, then one partial per block (at least one: an empty call still has a workspace)
+int64_t pg_workspace_bytes(const PgPlan &pl, long N)
+{
+    const int blocks = pg_blocks(N, pl.nw);
+    return pl.packed_bytes + (int64_t)(blocks > 0 ? blocks : 1) * pl.g.psize * 4;
 }

@@ -168,37 +168,35 @@ class MlpSpec:
     def widths_supported(widths, bits=3):
         """mpc_mlp_supported for a network of these layer widths ([n_state + n_ctrl, hidden..., n_state]): every bit of `bits`
         (1 = rollout, 2 = linearisation) must be set."""
+        ns = int(widths[-1])
+        return (int(load().mpc_mlp_supported(ctypes.byref(MlpSpec._describe(widths)), ns, int(widths[0]) - ns)) & bits) == bits
+
+    @staticmethod
+    def _describe(widths, activation=0, passthrough=0, ctrl_carry=0, pointers=()):
+        """struct mpc_mlp_dynamics for these layer widths.  `pointers`: the (W, b) addresses layer by layer of a complete
+        description; a probe by widths alone leaves them NULL."""
         e = MlpDynamics()
-        e.n_layers = len(widths) - 1
+        e.n_layers, e.activation, e.passthrough, e.ctrl_carry = len(widths) - 1, activation, passthrough, ctrl_carry
         for l, w in enumerate(widths):
             e.widths[l] = int(w)
-        ns = int(widths[-1])
-        return (int(load().mpc_mlp_supported(ctypes.byref(e), ns, int(widths[0]) - ns)) & bits) == bits
+        for l, (W, b) in enumerate(pointers):
+            e.W[l], e.b[l] = W, b
+        return e
+
+    def _complete(self, pointers):
+        return MlpSpec._describe([self.weights[0].shape[1]] + [W.shape[0] for W in self.weights], ACT_CODES[self.activation],
+                                 int(self.passthrough), self.ctrl_carry, pointers)
 
     def param_grad_supported(self):
         """Bit 2 of mpc_mlp_supported: does mpc_mlp_param_grad (the weight gradient of the linearisation) take this network?
         The library answers that bit for a complete description only -- activation, ctrl_carry and non-NULL weights."""
-        e = MlpDynamics()
-        e.n_layers, e.activation, e.passthrough = len(self.weights), ACT_CODES[self.activation], int(self.passthrough)
-        e.ctrl_carry = self.ctrl_carry
-        e.widths[0] = self.weights[0].shape[1]
-        for l, (W, b) in enumerate(zip(self.weights, self.biases)):
-            e.widths[l + 1] = W.shape[0]
-            e.W[l], e.b[l] = W.data_ptr() or 16, b.data_ptr() or 16
+        e = self._complete([(W.data_ptr() or 16, b.data_ptr() or 16) for W, b in zip(self.weights, self.biases)])
         return bool(int(load().mpc_mlp_supported(ctypes.byref(e), self.n_state, self.n_ctrl)) & 4)
 
     def to_struct(self, like):
-        e = MlpDynamics()
-        keep = []
-        e.n_layers, e.activation, e.passthrough = len(self.weights), ACT_CODES[self.activation], int(self.passthrough)
-        e.ctrl_carry = self.ctrl_carry
-        e.widths[0] = self.weights[0].shape[1]
-        for l, (W, b) in enumerate(zip(self.weights, self.biases)):
-            W = W.detach().to(device=like.device, dtype=torch.float32).contiguous()
-            b = b.detach().to(device=like.device, dtype=torch.float32).contiguous()
-            keep += [W, b]
-            e.widths[l + 1] = W.shape[0]
-            e.W[l], e.b[l] = W.data_ptr(), b.data_ptr()
+        keep = [t.detach().to(device=like.device, dtype=torch.float32).contiguous()
+                for Wb in zip(self.weights, self.biases) for t in Wb]          # W_1, b_1, W_2, ...: the struct holds raw pointers
+        e = self._complete([(W.data_ptr(), b.data_ptr()) for W, b in zip(keep[0::2], keep[1::2])])
         nbytes = int(load().mpc_mlp_workspace_bytes(ctypes.byref(e)))
         ws = torch.empty(nbytes, device=like.device, dtype=torch.uint8)
         keep.append(ws)
@@ -414,15 +412,18 @@ class HipBackend:
     # -- helpers -------------------------------------------------------------------------------
     @staticmethod
     def _problem(x_init, C, c, F, f, cur_x, cur_u):
-        T, B, n = C.shape[0], C.shape[1], C.shape[2]
+        """struct mpc_lqr_problem + the tensors its raw pointers need alive.  C None: a problem without a cost (a plain
+        rollout), its sizes and dtype then come from the controls cur_u [T,B,nc]; cur_x None: no nominal state."""
         ns = x_init.shape[1]
-        nc = n - ns
+        like = cur_u if C is None else C
+        T, B, nc = like.shape[0], like.shape[1], like.shape[2] - (0 if C is None else ns)
         keep = []
         p = Problem()
-        p.B, p.T, p.ns, p.nc, p.dtype = B, T, ns, nc, _dtype_code(C)
+        p.B, p.T, p.ns, p.nc, p.dtype = B, T, ns, nc, _dtype_code(like)
         xi = x_init.detach().contiguous(); keep.append(xi); p.x_init = xi.data_ptr()
-        Cc, p.C_st, p.C_sb = _block_strided(C.detach(), 2); keep.append(Cc); p.C = Cc.data_ptr()
-        cc, p.c_st, p.c_sb = _block_strided(c.detach(), 1); keep.append(cc); p.c = cc.data_ptr()
+        if C is not None:
+            Cc, p.C_st, p.C_sb = _block_strided(C.detach(), 2); keep.append(Cc); p.C = Cc.data_ptr()
+            cc, p.c_st, p.c_sb = _block_strided(c.detach(), 1); keep.append(cc); p.c = cc.data_ptr()
         if T > 1 and F is not None:
             Fc, p.F_st, p.F_sb = _block_strided(F.detach(), 2); keep.append(Fc); p.F = Fc.data_ptr()
         if f is not None and f.numel() > 0:
@@ -432,6 +433,14 @@ class HipBackend:
         if cur_u is not None:
             cu = cur_u.detach().contiguous(); keep.append(cu); p.cur_u = cu.data_ptr()
         return p, keep
+
+    @staticmethod
+    def _bind_outputs(res, names=None, out=None):
+        """struct mpc_lqr_outputs over the tensors of `res` (all of them, or `names`); the caller keeps `res` alive."""
+        out = Outputs() if out is None else out
+        for k in (res if names is None else names):
+            setattr(out, k, res[k].data_ptr())
+        return out
 
     @staticmethod
     def _check_same(C, *others):
@@ -477,10 +486,7 @@ class HipBackend:
                    alphas=torch.empty(B, **kw),
                    qp_iters=torch.zeros(B, device=dev, dtype=torch.int32),
                    status=torch.zeros(B, device=dev, dtype=torch.int32))
-        out = Outputs()
-        for k in ("new_x", "new_u", "costs", "old_costs", "full_du_norm", "alpha_du_norm", "alphas",
-                  "qp_iters", "status"):
-            setattr(out, k, res[k].data_ptr())
+        out = self._bind_outputs(res)
         split = rollout_problem is not None
         ws = None
         if want_gains or split:
@@ -523,9 +529,7 @@ class HipBackend:
                    new_u=torch.empty(T, B, nc, **kw) if out_u is None else out_u)
         res.update(self._per_problem_outputs(B, dev, C.dtype))
         assert res["new_x"].is_contiguous() and res["new_u"].is_contiguous()
-        out = Outputs()
-        for k in res:
-            setattr(out, k, res[k].data_ptr())
+        out = self._bind_outputs(res)
         nbytes = int(L.mpc_lqr_workspace_bytes(ctypes.byref(p)))
         ws = torch.empty(nbytes, device=dev, dtype=torch.uint8) if workspace is None else workspace
         assert ws.numel() >= nbytes
@@ -591,8 +595,7 @@ class HipBackend:
             assert out_x.is_contiguous() and out_u.is_contiguous() and tuple(out_x.shape) == (T, B, ns) and tuple(out_u.shape) == (T, B, nc)
             res["new_x"], res["new_u"] = out_x, out_u
             res.update(self._per_problem_outputs(B, dev, out_x.dtype))
-            for k in res:
-                setattr(out, k, res[k].data_ptr())
+            self._bind_outputs(res, out=out)
         o = o0
         if opts is not None:
             o, keep_o = opts.to_struct(T, B, nc, res["new_x"])
@@ -613,9 +616,7 @@ class HipBackend:
         res = dict(K=torch.empty(T, B, nc, ns, **kw), k=torch.empty(T, B, nc, **kw),
                    old_costs=torch.empty(B, **kw), qp_iters=torch.zeros(B, device=dev, dtype=torch.int32),
                    status=torch.zeros(B, device=dev, dtype=torch.int32))
-        out = Outputs()
-        for k in res:
-            setattr(out, k, res[k].data_ptr())
+        out = self._bind_outputs(res)
         # mpc_lqr_step with MPC_OPT_SWEEP_ONLY: the fused kernel of the shape stops after its sweep (the 12/4 kernel is
         # ten times the generic sweep behind mpc_lqr_sweep); other shapes take the generic sweep through the same call
         o.flags |= OPT_SWEEP_ONLY
@@ -641,9 +642,7 @@ class HipBackend:
         res = dict(new_x=torch.empty(T, B, ns, **kw), new_u=torch.empty(T, B, nc, **kw), costs=torch.empty(B, **kw),
                    full_du_norm=torch.empty(B, **kw), alpha_du_norm=torch.empty(B, **kw), alphas=torch.empty(B, **kw),
                    status=torch.zeros(B, device=dev, dtype=torch.int32))
-        out = Outputs()
-        for key in res:
-            setattr(out, key, res[key].data_ptr())
+        out = self._bind_outputs(res)
         Kc, kc = K.contiguous(), k.contiguous()
         out.K, out.k = Kc.data_ptr(), kc.data_ptr()
         oc = None if old_costs is None else old_costs.contiguous()
@@ -803,18 +802,7 @@ class HipBackend:
         ns = x_init.shape[1]
         kw = dict(device=dev, dtype=u.dtype)
         want_cost = C is not None
-        if want_cost:
-            p, keep = self._problem(x_init, C, c, F, f, None, u)
-        else:
-            p = Problem()
-            p.B, p.T, p.ns, p.nc, p.dtype = B, T, ns, nc, _dtype_code(u)
-            keep = []
-            xi = x_init.detach().contiguous(); keep.append(xi); p.x_init = xi.data_ptr()
-            if T > 1:
-                Fc, p.F_st, p.F_sb = _block_strided(F.detach(), 2); keep.append(Fc); p.F = Fc.data_ptr()
-            if f is not None and f.numel() > 0:
-                fc, p.f_st, p.f_sb = _block_strided(f.detach(), 1); keep.append(fc); p.f = fc.data_ptr()
-            cu = u.detach().contiguous(); keep.append(cu); p.cur_u = cu.data_ptr()
+        p, keep = self._problem(x_init, C, c, F, f, None, u)
         x = torch.empty(T, B, ns, **kw) if want_x else None
         cost = torch.empty(B, **kw) if want_cost else None
         _check(L.mpc_traj_cost(ctypes.byref(p), _ptr(x), _ptr(cost), _stream(dev)), "mpc_traj_cost")
@@ -827,14 +815,7 @@ class HipBackend:
         T, B, nc = u.shape
         ns = x_init.shape[1]
         kw = dict(device=dev, dtype=u.dtype)
-        p = Problem()
-        p.B, p.T, p.ns, p.nc, p.dtype = B, T, ns, nc, _dtype_code(u)
-        xi = x_init.detach().contiguous(); p.x_init = xi.data_ptr()
-        cu = u.detach().contiguous(); p.cur_u = cu.data_ptr()
-        keep = [xi, cu]
-        if C is not None:
-            Cc, p.C_st, p.C_sb = _block_strided(C.detach(), 2); keep.append(Cc); p.C = Cc.data_ptr()
-            cc, p.c_st, p.c_sb = _block_strided(c.detach(), 1); keep.append(cc); p.c = cc.data_ptr()
+        p, keep = self._problem(x_init, C, c, None, None, None, u)
         e, prm = env.to_struct(u)
         x = torch.empty(T, B, ns, **kw) if want_x else None
         cost = torch.empty(B, **kw) if C is not None else None
@@ -932,9 +913,7 @@ class HipBackend:
                    costs=torch.empty(B, **kw), old_costs=torch.empty(B, **kw),
                    full_du_norm=torch.empty(B, **kw), alpha_du_norm=torch.empty(B, **kw),
                    alphas=torch.empty(B, **kw), status=torch.zeros(B, device=dev, dtype=torch.int32))
-        out = Outputs()
-        for name in res:
-            setattr(out, name, res[name].data_ptr())
+        out = self._bind_outputs(res)
         Kc, kc, oc = K.detach().contiguous(), k.detach().contiguous(), old_costs.detach().contiguous()
         _check(L.mpc_mlp_rollout(ctypes.byref(p), ctypes.byref(o), ctypes.byref(e), Kc.data_ptr(), kc.data_ptr(),
                                  oc.data_ptr(), ctypes.byref(out), ws.data_ptr(), nbytes, _stream(dev)),
@@ -949,14 +928,7 @@ class HipBackend:
         T, B, nc = u.shape
         ns = x_init.shape[1]
         kw = dict(device=dev, dtype=u.dtype)
-        p = Problem()
-        p.B, p.T, p.ns, p.nc, p.dtype = B, T, ns, nc, _dtype_code(u)
-        xi = x_init.detach().contiguous(); p.x_init = xi.data_ptr()
-        cu = u.detach().contiguous(); p.cur_u = cu.data_ptr()
-        keep = [xi, cu]
-        if C is not None:
-            Cc, p.C_st, p.C_sb = _block_strided(C.detach(), 2); keep.append(Cc); p.C = Cc.data_ptr()
-            cc, p.c_st, p.c_sb = _block_strided(c.detach(), 1); keep.append(cc); p.c = cc.data_ptr()
+        p, keep = self._problem(x_init, C, c, None, None, None, u)
         e, ws, nbytes, keep_e = net.to_struct(u)
         x = torch.empty(T, B, ns, **kw)
         cost = torch.empty(B, **kw) if C is not None else None
@@ -969,37 +941,28 @@ class HipBackend:
     def mlp_linearize(self, net, x, u, out_F=None, out_f=None):
         """x [N,ns], u [N,nc] -> F [N,ns,ns+nc], f [N,ns]: NNDynamics.grad_input + the affine term of
         MPC.linearize_dynamics (mpc/dynamics.py:82-128, mpc/mpc.py:495-512), no [N, hidden, n] intermediates."""
-        dev = _require_device(x, u)
-        L = load()
-        N, ns = x.shape
-        nc = u.shape[1]
-        kw = dict(device=dev, dtype=x.dtype)
-        x = x.detach().contiguous(); u = u.detach().contiguous()
-        F = torch.empty(N, ns, ns + nc, **kw) if out_F is None else out_F
-        f = torch.empty(N, ns, **kw) if out_f is None else out_f
-        assert F.is_contiguous() and f.is_contiguous() and F.numel() == N * ns * (ns + nc) and f.numel() == N * ns
-        e, ws, nbytes, keep_e = net.to_struct(x)
-        _check(L.mpc_mlp_linearize(ctypes.byref(e), ns, nc, N, x.data_ptr(), u.data_ptr(), F.data_ptr(), f.data_ptr(),
-                                   ws.data_ptr(), nbytes, _stream(dev)), "mpc_mlp_linearize")
-        return F, f
+        return self._mlp_linearize("mpc_mlp_linearize", False, net, x, u, out_F, out_f)
 
     def mlp_linearize_carry(self, net, z, u, out_F=None, out_f=None):
         """`mlp_linearize` of the network itself (`net`: no ctrl_carry) at the augmented points z = (u_prev, x) [N,nc+ns],
         u [N,nc], written straight into the layout of the slew-rate augmentation (mpc/mpc.py:362-445, mpc/dynamics.py:131-150),
         na = ns + nc: aF [N,na,na+nc] = [[0 0 I], [0 F]], af [N,na] = [0; f] -- every element by the one launch."""
-        dev = _require_device(z, u)
-        L = load()
-        N, na = z.shape
+        return self._mlp_linearize("mpc_mlp_linearize_carry", True, net, z, u, out_F, out_f)
+
+    def _mlp_linearize(self, entry, carry, net, x, u, out_F, out_f):
+        """Both linearisations: points x [N,rows], F [N,rows,rows+nc], f [N,rows]; the rows are the network's states, or with
+        `carry` the augmented ones (the previous control in front: n_state = rows - nc)."""
+        dev = _require_device(x, u)
+        N, rows = x.shape
         nc = u.shape[1]
-        ns = na - nc
-        kw = dict(device=dev, dtype=z.dtype)
-        z = z.detach().contiguous(); u = u.detach().contiguous()
-        F = torch.empty(N, na, na + nc, **kw) if out_F is None else out_F
-        f = torch.empty(N, na, **kw) if out_f is None else out_f
-        assert F.is_contiguous() and f.is_contiguous() and F.numel() == N * na * (na + nc) and f.numel() == N * na
-        e, ws, nbytes, keep_e = net.to_struct(z)
-        _check(L.mpc_mlp_linearize_carry(ctypes.byref(e), ns, nc, N, z.data_ptr(), u.data_ptr(), F.data_ptr(), f.data_ptr(),
-                                         ws.data_ptr(), nbytes, _stream(dev)), "mpc_mlp_linearize_carry")
+        kw = dict(device=dev, dtype=x.dtype)
+        x = x.detach().contiguous(); u = u.detach().contiguous()
+        F = torch.empty(N, rows, rows + nc, **kw) if out_F is None else out_F
+        f = torch.empty(N, rows, **kw) if out_f is None else out_f
+        assert F.is_contiguous() and f.is_contiguous() and F.numel() == N * rows * (rows + nc) and f.numel() == N * rows
+        e, ws, nbytes, keep_e = net.to_struct(x)
+        _check(getattr(load(), entry)(ctypes.byref(e), rows - nc if carry else rows, nc, N, x.data_ptr(), u.data_ptr(), F.data_ptr(),
+                                      f.data_ptr(), ws.data_ptr(), nbytes, _stream(dev)), entry)
         return F, f
 
     def mlp_linearize_backward(self, net, x, u, gF, gf):
@@ -1079,9 +1042,7 @@ class HipBackend:
             sweeps.append([sp, None, None, keep_p])
             # the rollout through the network: new_x, new_u, costs, full_du_norm, alphas
             rp, keep_r = self._problem(x_init, C, c, None, None, cx, cu)
-            rout = Outputs()
-            for name in ("new_x", "new_u", "costs", "full_du_norm", "alpha_du_norm", "alphas"):
-                setattr(rout, name, res[name].data_ptr())
+            rout = self._bind_outputs(res, ("new_x", "new_u", "costs", "full_du_norm", "alpha_du_norm", "alphas"))
             # (the rollout's status words would overwrite the sweep's: it reports none the driver reads -- left unbound)
             rolls.append((rp, rout, keep_r, cx.data_ptr(), cu.data_ptr()))
             outs.append(res)
