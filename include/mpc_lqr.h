@@ -268,6 +268,31 @@ int mpc_lqr_kkt_fused(const mpc_lqr_problem *p, const mpc_lqr_options *o, const 
                       void *dC, void *dc, void *dF, void *df, void *dx_init, void *dx_out, void *du_out, int32_t *status,
                       void *workspace, int64_t workspace_bytes, void *stream);
 
+/* (4d) The closed-form part (4) for a cost and a linear model that the whole batch SHARES -- C [T,n,n] or [n,n], c, F, f
+ *     likewise, handed to the kernels as stride-0 views: the gradient of a shared tensor is the SUM over the batch of (4)'s
+ *     per-problem blocks, and this entry writes those sums without ever writing the blocks:
+ *         sum_dC [T,n,n]     = -0.5 (D'X + X'D)     X = tau*_t [B,n],        D = dtau_t [B,n]
+ *         sum_dc [T,n]       = -sum_b dtau_t
+ *         sum_dF [T-1,ns,n]  = -(dL'X + L'D)        L = lambda_{t+1} [B,ns], dL = dlambda_{t+1} [B,ns]
+ *         sum_df [T-1,ns]    = -sum_b dlambda_{t+1}
+ *     contiguous; each of the four may be NULL = not wanted.  p, dx, du, dl_dx, dl_du and dx_init [B,ns] (per problem) exactly
+ *     as in (4); p's strides are honoured as there (the sums are the same whether or not the inputs are in fact shared).
+ *     Three launches: the costate recursion of (4)'s wavefront-per-problem kernels into a compact [T-1,B,2 ns] area of the
+ *     workspace; a GEMM per timestep over the batch on v_mfma_f32_16x16x4_f32, chunks of 32 problems staged through LDS, one
+ *     partial per (timestep, run of chunks); the partials added in a fixed order, dC symmetrised, signs applied.  No atomics:
+ *     the result is bitwise reproducible and depends on the prior contents of neither the outputs nor the workspace.  At
+ *     most MPC_KKT_SHARED_MAX_PARTIALS partials per timestep; their number is a function of (T, B) alone.
+ *     Covered: float32, n_state + n_ctrl <= 64, any T >= 1 (T = 1: no sum_dF / sum_df, F may be NULL), any B >= 1.  Anything
+ *     else is MPC_E_DIMS with a message, decided before anything touches the device (the caller then sums (4)'s outputs).
+ *     workspace: mpc_lqr_kkt_shared_workspace_bytes(p) bytes, 16-byte aligned (shorter: MPC_E_DIMS, misaligned: MPC_E_ARG, NULL:
+ *     MPC_E_NULL).  B = 0 succeeds and writes nothing.  mpc_lqr_kkt_shared_supported: sizes and dtype only.  (ABI 9, additive) */
+#define MPC_KKT_SHARED_MAX_PARTIALS 32
+int mpc_lqr_kkt_shared_supported(const mpc_lqr_problem *p);
+int64_t mpc_lqr_kkt_shared_workspace_bytes(const mpc_lqr_problem *p);
+int mpc_lqr_kkt_grads_shared(const mpc_lqr_problem *p, const void *dx, const void *du, const void *dl_dx, const void *dl_du,
+                             void *sum_dC, void *sum_dc, void *sum_dF, void *sum_df, void *dx_init, void *workspace,
+                             int64_t workspace_bytes, void *stream);
+
 /* (5) Standalone batched pnqp, mpc/pnqp.py:5-82.  H [B,n,n], q/lo/hi/x0/x [B,n];
  *     x0 NULL = cold start (:14-19).  If_out [B,n] uint8 (1 = free), iters [B],
  *     Hfree [B,n,n] receives H_ (free-set Hessian + 1e-11 I, :44-48) or NULL. */

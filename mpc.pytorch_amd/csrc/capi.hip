@@ -358,7 +358,7 @@ int mpc_lqr_abi_version(void) { return MPC_LQR_ABI_VERSION; }
 const char *mpc_lqr_build_info(void)
 {
     return "libmpc_lqr_hip gfx950 (CDNA4) | kernels: lqr_step_generic<f32,f64>, lqr_step_mfma16<f32,f64>, lqr_step_dpp16<f32>, lqr_step_dpp16_padded<f32>, "
-           "lqr_step_tiny<f32,f64>, lqr_step_wave1<f32>, lqr_step_mfma40<f32>, lqr_step_mfma40_padded<f32>, nn_rollout<f32>, nn_linearize<f32>, nn_param_grad<f32>, env_linearize, env_param_grad<f32,f64>, kkt_grads, kkt_fused<f32>, kkt_fused_padded<f32>, pnqp, traj_cost, select_best, slew_augment<f32,f64> | built " __DATE__ " " __TIME__;
+           "lqr_step_tiny<f32,f64>, lqr_step_wave1<f32>, lqr_step_mfma40<f32>, lqr_step_mfma40_padded<f32>, nn_rollout<f32>, nn_linearize<f32>, nn_param_grad<f32>, env_linearize, env_param_grad<f32,f64>, kkt_grads, kkt_grads_shared<f32>, kkt_fused<f32>, kkt_fused_padded<f32>, pnqp, traj_cost, select_best, slew_augment<f32,f64> | built " __DATE__ " " __TIME__;
 }
 
 const char *mpc_lqr_last_error(void) { return g_last_error.c_str(); }
@@ -510,6 +510,38 @@ int mpc_lqr_kkt_grads(const mpc_lqr_problem *p, const void *dx, const void *du, 
     return launch_kkt_grads<double>(sp, (const double *)dx, (const double *)du, (const double *)dl_dx,
                                     (const double *)dl_du, (double *)dC, (double *)dc, (double *)dF, (double *)df,
                                     (double *)dx_init, st);
+}
+
+int mpc_lqr_kkt_shared_supported(const mpc_lqr_problem *p)
+{
+    if (!p || p->B < 0 || p->T < 1 || p->ns < 1 || p->nc < 1) return 0;
+    return (p->dtype == MPC_F32 && p->ns + p->nc <= 64) ? 1 : 0;
+}
+
+int64_t mpc_lqr_kkt_shared_workspace_bytes(const mpc_lqr_problem *p)
+{
+    if (!mpc_lqr_kkt_shared_supported(p)) return 0;
+    return kkt_shared_workspace_bytes(p->T, p->B, p->ns, p->nc);
+}
+
+int mpc_lqr_kkt_grads_shared(const mpc_lqr_problem *p, const void *dx, const void *du, const void *dl_dx, const void *dl_du,
+                             void *sum_dC, void *sum_dc, void *sum_dF, void *sum_df, void *dx_init, void *workspace,
+                             int64_t workspace_bytes, void *stream)
+{
+    int rc = check_problem(p, true, true);
+    if (rc) return rc;
+    if (!mpc_lqr_kkt_shared_supported(p))
+        return fail(MPC_E_DIMS, "mpc_lqr_kkt_grads_shared: needs float32 and n_state + n_ctrl <= 64 (otherwise: mpc_lqr_kkt_grads and a sum over the batch)");
+    if (p->B == 0) return MPC_OK;
+    if (!dx || !du || !dl_dx || !dl_du || !dx_init) return fail(MPC_E_NULL, "kkt_grads_shared: NULL argument");
+    if (!workspace) return fail(MPC_E_NULL, "kkt_grads_shared: the workspace is NULL");
+    if (workspace_bytes < mpc_lqr_kkt_shared_workspace_bytes(p))
+        return fail(MPC_E_DIMS, "workspace too small (see mpc_lqr_kkt_shared_workspace_bytes)");
+    if ((uintptr_t)workspace % 16) return fail(MPC_E_ARG, "kkt_grads_shared: the workspace must be 16-byte aligned");
+    StepParams<float> sp = make_params<float>(p, nullptr, nullptr);
+    return launch_kkt_shared(sp, (const float *)dx, (const float *)du, (const float *)dl_dx, (float *)sum_dC, (float *)sum_dc,
+                             p->T > 1 ? (float *)sum_dF : nullptr, p->T > 1 ? (float *)sum_df : nullptr, (float *)dx_init, workspace,
+                             (hipStream_t)stream);
 }
 
 int mpc_lqr_kkt_fused_supported(const mpc_lqr_problem *p, const mpc_lqr_options *o)

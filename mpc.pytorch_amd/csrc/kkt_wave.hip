@@ -5,7 +5,9 @@
 //                        lane i owns state i; C and F are read column-wise ((C tau)[i] = sum_j C[j][i] tau[j]
 //                        by symmetry, (Fx' lam)[i] = sum_m F[m][i] lam[m]): conflict-free LDS reads of blocks
 //                        that arrive by LDS-DMA one step ahead; tau[j] / lam[m] reach the lanes as readlanes.
-//                        lam_{t+1}, dlam_{t+1} are parked in the first 2 n_state words of the dF_t block.
+//                        lam_{t+1}, dlam_{t+1} are parked in the first 2 n_state words of the dF_t block -- block t of the
+//                        parking area starts park_stride words after block t - 1: n_state n for the dF blocks themselves,
+//                        2 n_state for the compact [T-1,B,2 n_state] area of the batch-summed route (kkt_shared.hip).
 //   kkt_outer_kernel     dC_t, dc_t, dF_t (:346-353, :387-400): independent over (t, b), one wavefront each,
 //                        16 bytes per lane, every output byte written exactly once and fully coalesced
 //                        (the block first picks its two costates out of its own dF_t block).
@@ -71,7 +73,7 @@ __device__ __forceinline__ void wait_newer(int n)
 // word by word.  Rounds 3-5 sent such shapes (13/4, 20/5 ...) to the generic kernel: 0.45 of their 1.0 ms backward.
 template <int NSLOT, bool AL>
 __global__ void __launch_bounds__(64) kkt_costate_kernel(StepParams<float> p, const float *dx, const float *du,
-                                                         const float *dl_dx, float *dF, float *df, float *dx_init)
+                                                         const float *dl_dx, float *dF, long park_stride, float *df, float *dx_init)
 {
     extern __shared__ __attribute__((aligned(16))) char kkt_lds[];
     const int b = blockIdx.x, lane = threadIdx.x;
@@ -181,7 +183,7 @@ __global__ void __launch_bounds__(64) kkt_costate_kernel(StepParams<float> p, co
             }
         }
         if (t < T - 1 && st) {
-            float *park = dF + tb * (long)(ns * n);
+            float *park = dF + tb * park_stride;
             park[lane] = lam;
             park[ns + lane] = dlam;
             if (df) df[tb * ns + lane] = -dlam;                                   // :397-400
@@ -385,19 +387,19 @@ bool kkt_wave_supported(const StepParams<float> &p, const float *, const float *
 }
 
 template <int NSLOT, bool AL>
-static void launch_costate(const StepParams<float> &p, size_t lds, const float *dx, const float *du, const float *dl_dx, float *dF, float *df,
-                           float *dx_init, hipStream_t st)
+static void launch_costate(const StepParams<float> &p, size_t lds, const float *dx, const float *du, const float *dl_dx, float *dF,
+                           long park_stride, float *df, float *dx_init, hipStream_t st)
 {
     if (lds > 64 * 1024)
         (void)hipFuncSetAttribute(reinterpret_cast<const void *>(&kkt_costate_kernel<NSLOT, AL>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    hipLaunchKernelGGL((kkt_costate_kernel<NSLOT, AL>), dim3(p.B), dim3(64), lds, st, p, dx, du, dl_dx, dF, df, dx_init);
+    hipLaunchKernelGGL((kkt_costate_kernel<NSLOT, AL>), dim3(p.B), dim3(64), lds, st, p, dx, du, dl_dx, dF, park_stride, df, dx_init);
 }
 
-int launch_kkt_wave(const StepParams<float> &p, const float *dx, const float *du, const float *dl_dx, float *dC,
-                    float *dc, float *dF, float *df, float *dx_init, hipStream_t st)
+// the costate recursion alone: lam_{t+1}, dlam_{t+1} into block t of `park` (blocks park_stride words apart), df (or NULL), dx_init
+static void launch_costates_any(const StepParams<float> &p, bool al, const float *dx, const float *du, const float *dl_dx, float *park,
+                                long park_stride, float *df, float *dx_init, hipStream_t st)
 {
     const int n = p.ns + p.nc;
-    const bool al = kkt_wave_aligned(p, dx, du, dl_dx, dC, dF);
     // three slots (the DMA two timesteps ahead) while four wavefronts of them fit a CU's 160 KiB, else two
     // (the general instantiation: a stage is up to 4x the instructions -- three slots only while two stages stay under vmcnt's 63)
     const size_t slot = (size_t)(n * n + p.ns * n) * 4 + 1024;
@@ -405,17 +407,40 @@ int launch_kkt_wave(const StepParams<float> &p, const float *dx, const float *du
     const bool deep = 3 * slot * 4 <= 160 * 1024 && (al || nd4 <= 63);
     const size_t lds = (deep ? 3 : 2) * slot;
     if (deep) {
-        if (al) launch_costate<3, true>(p, lds, dx, du, dl_dx, dF, df, dx_init, st);
-        else launch_costate<3, false>(p, lds, dx, du, dl_dx, dF, df, dx_init, st);
+        if (al) launch_costate<3, true>(p, lds, dx, du, dl_dx, park, park_stride, df, dx_init, st);
+        else launch_costate<3, false>(p, lds, dx, du, dl_dx, park, park_stride, df, dx_init, st);
     } else {
-        if (al) launch_costate<2, true>(p, lds, dx, du, dl_dx, dF, df, dx_init, st);
-        else launch_costate<2, false>(p, lds, dx, du, dl_dx, dF, df, dx_init, st);
+        if (al) launch_costate<2, true>(p, lds, dx, du, dl_dx, park, park_stride, df, dx_init, st);
+        else launch_costate<2, false>(p, lds, dx, du, dl_dx, park, park_stride, df, dx_init, st);
     }
+}
+
+int launch_kkt_wave(const StepParams<float> &p, const float *dx, const float *du, const float *dl_dx, float *dC,
+                    float *dc, float *dF, float *df, float *dx_init, hipStream_t st)
+{
+    const int n = p.ns + p.nc;
+    const bool al = kkt_wave_aligned(p, dx, du, dl_dx, dC, dF);
+    launch_costates_any(p, al, dx, du, dl_dx, dF, (long)p.ns * n, df, dx_init, st);
     if (al) hipLaunchKernelGGL(kkt_outer_kernel<true>, dim3((unsigned)((long)p.T * p.B)), dim3(64), 0, st, p, dx, du, dC, dc, dF);
     else hipLaunchKernelGGL(kkt_outer_kernel<false>, dim3((unsigned)((long)p.T * p.B)), dim3(64), 0, st, p, dx, du, dC, dc, dF);
     hipError_t e = hipGetLastError();
     if (e != hipSuccess) {
         set_last_error((std::string("kkt_wave kernels: ") + hipGetErrorString(e)).c_str());
+        return MPC_E_LAUNCH;
+    }
+    return MPC_OK;
+}
+
+// the recursion for the batch-summed route (kkt_shared.hip): the costates of timestep t + 1 go to park[(t B + b) 2 n_state ..],
+// a 16-byte aligned area of (T - 1) B 2 n_state floats; no df (the route sums dlam itself)
+int launch_kkt_costates(const StepParams<float> &p, const float *dx, const float *du, const float *dl_dx, float *park, float *dx_init,
+                        hipStream_t st)
+{
+    const bool al = kkt_wave_aligned(p, dx, du, dl_dx, park, park);
+    launch_costates_any(p, al, dx, du, dl_dx, park, 2l * p.ns, nullptr, dx_init, st);
+    hipError_t e = hipGetLastError();
+    if (e != hipSuccess) {
+        set_last_error((std::string("kkt_costate_kernel: ") + hipGetErrorString(e)).c_str());
         return MPC_E_LAUNCH;
     }
     return MPC_OK;

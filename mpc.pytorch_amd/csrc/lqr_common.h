@@ -87,6 +87,15 @@ bool kkt_wave_supported(const StepParams<float> &p, const float *dx, const float
 int launch_kkt_wave(const StepParams<float> &p, const float *dx, const float *du, const float *dl_dx, float *dC,
                     float *dc, float *dF, float *df, float *dx_init, hipStream_t st);
 
+// the costate recursion alone, parked in a compact [T-1,B,2 ns] area (kkt_wave.hip), and the batch-summed gradients of a shared
+// C, c, F, f built on it (kkt_shared.hip): outputs [T,n,n], [T,n], [T-1,ns,n], [T-1,ns], each may be NULL
+int launch_kkt_costates(const StepParams<float> &p, const float *dx, const float *du, const float *dl_dx, float *park, float *dx_init,
+                        hipStream_t st);
+int kkt_shared_partials(int T, int B);
+int64_t kkt_shared_workspace_bytes(int T, int B, int ns, int nc);
+int launch_kkt_shared(const StepParams<float> &p, const float *dx, const float *du, const float *dl_dx, float *sum_dC, float *sum_dc,
+                      float *sum_dF, float *sum_df, float *dx_init, void *workspace, hipStream_t st);
+
 int launch_kkt_outer(const StepParams<float> &p, const float *dx, const float *du, float *dC, float *dc, float *dF, hipStream_t st);
 
 // register-resident MFMA step for n_state = 32, n_ctrl = 8, f32 (lqr_mfma40.hip)

@@ -216,7 +216,8 @@ EXPORTS = ("mpc_lqr_abi_version", "mpc_lqr_build_info", "mpc_lqr_last_error", "m
            "mpc_mlp_workspace_bytes", "mpc_mlp_rollout", "mpc_mlp_linearize", "mpc_mlp_linearize_carry",
            "mpc_mlp_param_grad_workspace_bytes", "mpc_mlp_param_grad",
            "mpc_mlp_supported", "mpc_lqr_kkt_fused_supported", "mpc_lqr_kkt_fused_workspace_bytes", "mpc_lqr_kkt_fused",
-           "mpc_du_norm_reference", "mpc_slew_augment")
+           "mpc_du_norm_reference", "mpc_slew_augment",
+           "mpc_lqr_kkt_shared_supported", "mpc_lqr_kkt_shared_workspace_bytes", "mpc_lqr_kkt_grads_shared")
 
 _lib = None
 
@@ -259,6 +260,10 @@ def load():
     L.mpc_lqr_kkt_fused_workspace_bytes.restype = _i64
     L.mpc_lqr_kkt_fused_workspace_bytes.argtypes = [PP]
     L.mpc_lqr_kkt_fused.argtypes = [PP, OP] + [_vp] * 11 + [_i64, _vp]
+    L.mpc_lqr_kkt_shared_supported.argtypes = [PP]
+    L.mpc_lqr_kkt_shared_workspace_bytes.restype = _i64
+    L.mpc_lqr_kkt_shared_workspace_bytes.argtypes = [PP]
+    L.mpc_lqr_kkt_grads_shared.argtypes = [PP] + [_vp] * 10 + [_i64, _vp]
     L.mpc_pnqp.argtypes = [ctypes.c_int] * 3 + [_vp] * 5 + [ctypes.c_int] + [_vp] * 6
     L.mpc_pnqp_lu.argtypes = [ctypes.c_int] * 3 + [_vp] * 5 + [ctypes.c_int] + [_vp] * 8
     L.mpc_traj_cost.argtypes = [PP, _vp, _vp, _vp]
@@ -722,6 +727,60 @@ class HipBackend:
                                    dF.data_ptr(), _ptr(df), dx_init.data_ptr(), st), "mpc_lqr_kkt_grads")
         return dict(dx_init=dx_init, dC=dC, dc=dc, dF=dF, df=df, dx=sol["new_x"], du=sol["new_u"],
                     _keep=(keep, keep_o, negr, mask, sol))
+
+    def kkt_backward_shared(self, C, c, F, f, x_star, u_star, dl_dx, dl_du, opts, want=(True, True, True, True)):
+        """The backward for a cost and a linear model the whole batch shares: dx_init [B,ns] and the gradients SUMMED over the
+        batch, sum_dC [T,n,n], sum_dc [T,n], sum_dF [T-1,ns,n], sum_df [T-1,ns] -- None where `want` (four booleans, in that
+        order) says no, or f is empty -- plus the KKT solve's dx, du.  C, c, F, f are the [T,B,...] views the kernels read
+        (stride-0 where shared; the sums are what they are for per-problem inputs too).  mpc_lqr_kkt_prepare, the nested solve on
+        the fastest step kernel of the shape (as kkt_backward's three-call path), then mpc_lqr_kkt_grads_shared: no per-problem
+        dC / dF is ever written.  Where that entry does not cover the problem (float64, n_state + n_ctrl > 64) the same dict
+        comes from kkt_backward and a sum over the batch axis."""
+        dev = _require_device(C, c, F, x_star, u_star, dl_dx, dl_du)
+        L = load()
+        T, B, n = C.shape[0], C.shape[1], C.shape[2]
+        ns = x_star.shape[2]
+        nc = n - ns
+        has_f = f is not None and f.numel() > 0
+        want = tuple(bool(w) for w in want)
+        want = (want[0], want[1], want[2] and T > 1, want[3] and has_f and T > 1)
+        names = ("sum_dC", "sum_dc", "sum_dF", "sum_df")
+        x_star = x_star.detach().contiguous()
+        u_star = u_star.detach().contiguous()
+        probe, keep_probe = self._problem(x_star[0], C, c, F, f, x_star, u_star)
+        if not L.mpc_lqr_kkt_shared_supported(ctypes.byref(probe)):
+            g = self.kkt_backward(C, c, F, f, x_star, u_star, dl_dx, dl_du, opts)
+            out = dict(dx_init=g["dx_init"], dx=g["dx"], du=g["du"])
+            for name, src, w in zip(names, ("dC", "dc", "dF", "df"), want):
+                out[name] = g[src].sum(1) if (w and g[src] is not None) else None
+            return out
+        kw = dict(device=dev, dtype=C.dtype)
+        code = _dtype_code(C)
+        st = _stream(dev)
+        dl_dx = dl_dx.detach().to(**kw).contiguous()
+        dl_du = dl_du.detach().to(**kw).contiguous()
+        o, keep_o = opts.to_struct(T, B, nc, C)
+        negr = torch.empty(T, B, n, **kw)
+        mask = None
+        if o.bound_mode != BOUND_NONE:
+            mask = torch.empty(T, B, nc, device=dev, dtype=torch.uint8)
+        _check(L.mpc_lqr_kkt_prepare(code, B, T, ns, nc, dl_dx.data_ptr(), dl_du.data_ptr(), u_star.data_ptr(),
+                                     ctypes.byref(o), negr.data_ptr(), _ptr(mask), st), "mpc_lqr_kkt_prepare")
+        zx, zu, z0 = self._zero_nominal(T, B, ns, nc, kw)
+        inner = StepOptions(u_zero_I=mask, nominal_on_dynamics=True, c_symmetric=opts.c_symmetric)
+        sol = self.lqr_step(z0, C, negr, F, None, zx, zu, inner)
+        p, keep = self._problem(z0, C, c, F, f, x_star, u_star)
+        shapes = ((T, n, n), (T, n), (T - 1, ns, n), (T - 1, ns))
+        sums = [torch.empty(shape, **kw) if w else None for shape, w in zip(shapes, want)]
+        dx_init = torch.empty(B, ns, **kw)
+        nbytes = int(L.mpc_lqr_kkt_shared_workspace_bytes(ctypes.byref(p)))
+        ws = torch.empty(nbytes, device=dev, dtype=torch.uint8)
+        _check(L.mpc_lqr_kkt_grads_shared(ctypes.byref(p), sol["new_x"].data_ptr(), sol["new_u"].data_ptr(), dl_dx.data_ptr(),
+                                          dl_du.data_ptr(), _ptr(sums[0]), _ptr(sums[1]), _ptr(sums[2]), _ptr(sums[3]),
+                                          dx_init.data_ptr(), ws.data_ptr(), nbytes, st), "mpc_lqr_kkt_grads_shared")
+        out = dict(dx_init=dx_init, dx=sol["new_x"], du=sol["new_u"], _keep=(keep, keep_o, keep_probe, negr, mask, sol, ws))
+        out.update(zip(names, sums))
+        return out
 
     def plan_kkt_backward(self, C, c, F, f, x_star, u_star, dl_dx, dl_du, opts, _prepared=False):
         """Pre-bind the fused KKT backward (mpc_lqr_kkt_fused): argument structs, the gradient buffers and the workspace are

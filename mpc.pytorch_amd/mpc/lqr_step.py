@@ -266,7 +266,34 @@ def _host_scalar_async(dev_scalar):
 
 class _StepConfig:
     """What one LQRStep(...) call fixes for its autograd node (closure state of the reference's factory)."""
-    __slots__ = ("solve", "no_op_forward", "delta_space", "current_x", "current_u", "u_lower", "u_upper", "c_symmetric")
+    __slots__ = ("solve", "no_op_forward", "delta_space", "current_x", "current_u", "u_lower", "u_upper", "c_symmetric", "T")
+
+
+def _step_forward(ctx, cfg, x_init, given, views):
+    """The forward of both Functions: `views` = (C, c, F, f) as the kernels read them, `given` = the same four as the Function
+    received them (what the backward gets back: `_LQRStepFn` passes the same tuple twice)."""
+    # Only the bounds go on ctx.  (The reference also parks current_x / current_u there, :281, 300-301: in
+    # the no-op forward those ARE the outputs, and output -> grad_fn -> ctx -> output is a cycle the
+    # garbage collector cannot see -- every differentiated solve would pin its tensors forever.)
+    ctx.u_lower, ctx.u_upper = cfg.u_lower, cfg.u_upper
+    ctx.c_symmetric = cfg.c_symmetric
+    if cfg.no_op_forward:
+        ctx.save_for_backward(x_init, *given, cfg.current_x, cfg.current_u)
+        return cfg.current_x, cfg.current_u
+    if not cfg.delta_space:
+        assert False      # unimplemented upstream too (mpc/lqr_step.py:297-298)
+    assert cfg.current_x is not None
+    assert cfg.current_u is not None
+    new_x, new_u, qp_iters, costs, full_du_norm, alphas = cfg.solve(x_init, *views)
+    ctx.save_for_backward(x_init, *given, new_x, new_u)
+    # n_total_qp_iter stays on the device here; LQRStep's wrapper turns it into the CPU float tensor of the
+    # reference (mpc/lqr_step.py:308) by an asynchronous copy -- no host synchronisation in a forward.
+    # Value: max over the problems of sum_t (1 + that problem's pnqp iterations).  The reference's loops are
+    # batch-global, so it reports sum_t (1 + max over the batch) >= this; they agree for n_batch = 1.  Only the
+    # "total_qp_iters" log column and this third return value see it.
+    n_qp = qp_iters.max().reshape(1) if cfg.u_lower is not None else qp_iters[:1]     # unbounded: zeros, no kernel
+    ctx.mark_non_differentiable(n_qp)
+    return new_x, new_u, n_qp, costs, full_du_norm, alphas.mean()
 
 
 class _LQRStepFn(Function):
@@ -278,28 +305,7 @@ class _LQRStepFn(Function):
     def forward(ctx, cfg, x_init, C, c, F, f=None):
         if f is None:
             f = torch.empty(0)
-        # Only the bounds go on ctx.  (The reference also parks current_x / current_u there, :281, 300-301: in
-        # the no-op forward those ARE the outputs, and output -> grad_fn -> ctx -> output is a cycle the
-        # garbage collector cannot see -- every differentiated solve would pin its tensors forever.)
-        ctx.u_lower, ctx.u_upper = cfg.u_lower, cfg.u_upper
-        ctx.c_symmetric = cfg.c_symmetric
-        if cfg.no_op_forward:
-            ctx.save_for_backward(x_init, C, c, F, f, cfg.current_x, cfg.current_u)
-            return cfg.current_x, cfg.current_u
-        if not cfg.delta_space:
-            assert False      # unimplemented upstream too (mpc/lqr_step.py:297-298)
-        assert cfg.current_x is not None
-        assert cfg.current_u is not None
-        new_x, new_u, qp_iters, costs, full_du_norm, alphas = cfg.solve(x_init, C, c, F, f)
-        ctx.save_for_backward(x_init, C, c, F, f, new_x, new_u)
-        # n_total_qp_iter stays on the device here; LQRStep's wrapper turns it into the CPU float tensor of the
-        # reference (mpc/lqr_step.py:308) by an asynchronous copy -- no host synchronisation in a forward.
-        # Value: max over the problems of sum_t (1 + that problem's pnqp iterations).  The reference's loops are
-        # batch-global, so it reports sum_t (1 + max over the batch) >= this; they agree for n_batch = 1.  Only the
-        # "total_qp_iters" log column and this third return value see it.
-        n_qp = qp_iters.max().reshape(1) if cfg.u_lower is not None else qp_iters[:1]     # unbounded: zeros, no kernel
-        ctx.mark_non_differentiable(n_qp)
-        return new_x, new_u, n_qp, costs, full_du_norm, alphas.mean()
+        return _step_forward(ctx, cfg, x_init, (C, c, F, f), (C, c, F, f))
 
     @staticmethod
     def backward(ctx, dl_dx, dl_du, *unused):
@@ -313,6 +319,78 @@ class _LQRStepFn(Function):
             StepOptions(u_lower=ctx.u_lower, u_upper=ctx.u_upper, c_symmetric=ctx.c_symmetric))
         df = g["df"] if g["df"] is not None else torch.Tensor()
         return None, g["dx_init"], g["dC"], g["dc"], g["dF"], df
+
+
+_FULL_RANK = (4, 3, 4, 3)      # C [T,B,n,n], c [T,B,n], F [T-1,B,ns,n], f [T-1,B,ns]
+
+
+def _is_shared(t, k):
+    """Is argument k (0..3 = C, c, F, f) given in batch-shared form: one or two axes short of [T,B,...]?"""
+    return t is not None and t.numel() > 0 and t.dim() < _FULL_RANK[k]
+
+
+def _expand_shared(t, k, T, B):
+    """The [T,B,...] stride-0 view of a batch-shared (or time-invariant) C, c, F or f; never a copy.  F, f have T - 1 blocks."""
+    if not _is_shared(t, k):
+        return t
+    steps = T if k < 2 else T - 1
+    if t.dim() == _FULL_RANK[k] - 2:
+        return t.unsqueeze(0).unsqueeze(0).expand(steps, B, *t.shape)
+    if t.shape[0] != steps:
+        raise ValueError("LQRStep: a batch-shared %s needs %d blocks along its first axis, got %d" % ("CcFf"[k], steps, t.shape[0]))
+    return t.unsqueeze(1).expand(steps, B, *t.shape[1:])
+
+
+class _LQRStepSharedFn(Function):
+    """`_LQRStepFn` for C, c, F, f given in BATCH-SHARED form (`LQRStep(..., shared_grad_kernel=True)`): C [T,n,n] or [n,n],
+    c [T,n] or [n], F [T-1,ns,n] or [ns,n], f [T-1,ns] or [ns], each independently; full-rank [T,B,...] arguments pass through.
+    The forward hands the kernels stride-0 views of the bases (no copy) and is otherwise `_LQRStepFn`'s; the backward returns
+    gradients in the BASE shapes.  When every one of C, c, F, f that needs a gradient is shared, they come from
+    `kkt_backward_shared` (mpc_lqr_kkt_grads_shared): summed over the batch inside the kernels, no [T,B,n,n] block is written
+    or read back; a time-invariant base gets the sum of the [T,...] result over T here (a few KB).  When a full-rank argument
+    needs a gradient too, or the backend has no such method, `kkt_backward` serves everything and the shared ones are its
+    outputs summed over the batch axis -- correct, only not faster.
+    A view the caller expanded themselves is a full-rank argument here: a Function sees the tensors it is given, not how they
+    were made, so such a view keeps today's route (per-problem blocks, then autograd's sum through the expand)."""
+
+    @staticmethod
+    def forward(ctx, cfg, x_init, C, c, F, f=None):
+        if f is None:
+            f = torch.empty(0)
+        T, B = cfg.T, x_init.shape[0]
+        ctx.T = T
+        ctx.shared = tuple(_is_shared(t, k) for k, t in enumerate((C, c, F, f)))
+        return _step_forward(ctx, cfg, x_init, (C, c, F, f), tuple(_expand_shared(t, k, T, B) for k, t in enumerate((C, c, F, f))))
+
+    @staticmethod
+    def backward(ctx, dl_dx, dl_du, *unused):
+        x_init, C, c, F, f, new_x, new_u = ctx.saved_tensors
+        if dl_dx is None:
+            dl_dx = torch.zeros_like(new_x)
+        if dl_du is None:
+            dl_du = torch.zeros_like(new_u)
+        T, B = ctx.T, x_init.shape[0]
+        bases = (C, c, F, f)
+        Ce, ce, Fe, fe = (_expand_shared(t, k, T, B) for k, t in enumerate(bases))
+        fe = None if _is_empty(fe) else fe
+        needs, shared = ctx.needs_input_grad[2:6], ctx.shared
+        opts = StepOptions(u_lower=ctx.u_lower, u_upper=ctx.u_upper, c_symmetric=ctx.c_symmetric)
+        be = _native.backend()
+        if hasattr(be, "kkt_backward_shared") and not any(n and not s for n, s in zip(needs, shared)):
+            g = be.kkt_backward_shared(Ce, ce, Fe, fe, new_x, new_u, dl_dx, dl_du, opts, tuple(bool(n) for n in needs))
+            grads = [g["sum_dC"], g["sum_dc"], g["sum_dF"], g["sum_df"]]
+        else:
+            g = be.kkt_backward(Ce, ce, Fe, fe, new_x, new_u, dl_dx, dl_du, opts)
+            grads = [g["dC"], g["dc"], g["dF"], g["df"]]
+            grads = [v.sum(1) if (v is not None and s) else v for v, s in zip(grads, shared)]
+        out = []
+        for k, (v, n, base) in enumerate(zip(grads, needs, bases)):
+            if not n or v is None:
+                v = None
+            elif base.dim() == _FULL_RANK[k] - 2:
+                v = v.sum(0)                      # a time-invariant base: the [T,...] result added over T
+            out.append(v)
+        return (None, g["dx_init"]) + tuple(out)
 
 
 def LQRStep(n_state,
@@ -333,7 +411,8 @@ def LQRStep(n_state,
             back_eps=1e-3,
             no_op_forward=False,
             c_symmetric=False,
-            reference_du_norm=False):
+            reference_du_norm=False,
+            shared_grad_kernel=False):
     """A single step of the box-constrained iLQR solver.
 
     Required: n_state, n_ctrl, T.  The returned callable takes (x_init [B,ns], C [T,B,n,n],
@@ -352,6 +431,12 @@ def LQRStep(n_state,
     makes entry r the norm of T n_ctrl consecutive elements of the [T, n_ctrl, n_batch] array, which mixes the problems of the
     batch.  Off (default), entry b is problem b's own norm (= the reference called with n_batch = 1).  On, one more rollout (the
     full step, alpha = 1, for every problem: mpc_lqr_rollout) and mpc_du_norm_reference reproduce the reference's vector.
+
+    shared_grad_kernel (not in the reference; off by default): the callable also accepts each of C, c, F, f in BATCH-SHARED
+    form -- C [T,n,n] or [n,n], c [T,n] or [n], F [T-1,ns,n] or [ns,n], f [T-1,ns] or [ns]; the batch size is x_init's -- and
+    returns their gradients in those shapes, summed over the batch inside the kernels (`_LQRStepSharedFn`,
+    mpc_lqr_kkt_grads_shared) when every argument that needs a gradient is shared.  `reference_du_norm` with a batch, and
+    views the caller expanded themselves, keep the per-problem route.
     """
     opts = StepOptions(u_lower=u_lower, u_upper=u_upper, u_zero_I=u_zero_I, delta_u=delta_u,
                        linesearch_decay=linesearch_decay, max_linesearch_iter=max_linesearch_iter,
@@ -422,9 +507,18 @@ def LQRStep(n_state,
     cfg.current_x, cfg.current_u = current_x, current_u
     cfg.u_lower, cfg.u_upper = u_lower, u_upper
     cfg.c_symmetric = bool(c_symmetric)
+    cfg.T = T
 
     def apply(x_init, C, c, F, f=None):
-        out = _LQRStepFn.apply(cfg, x_init, C, c, F, f)
+        if shared_grad_kernel and any(_is_shared(t, k) for k, t in enumerate((C, c, F, f))):
+            if reference_du_norm and x_init.shape[0] > 1:
+                # today's route: full-rank views, autograd adds the per-problem gradients up through the expand
+                C, c, F, f = (_expand_shared(t, k, T, x_init.shape[0]) for k, t in enumerate((C, c, F, f)))
+                out = _LQRStepFn.apply(cfg, x_init, C, c, F, f)
+            else:
+                out = _LQRStepSharedFn.apply(cfg, x_init, C, c, F, f)
+        else:
+            out = _LQRStepFn.apply(cfg, x_init, C, c, F, f)
         if no_op_forward:
             return out
         n_qp = _host_scalar_async(out[2]) if u_lower is not None else torch.zeros(1)

@@ -175,7 +175,7 @@ class MPC(Module):
                  back_eps=1e-7, n_batch=None, linesearch_decay=0.2, max_linesearch_iter=10,
                  exit_unconverged=True, detach_unconverged=True, backprop=True, slew_rate_penalty=None,
                  prev_ctrl=None, not_improved_lim=5, best_cost_eps=1e-4, reference_du_norm=False,
-                 weight_grad_kernel=False, planned_network_slew=False):
+                 shared_grad_kernel=False, weight_grad_kernel=False, planned_network_slew=False):
         super().__init__()
         assert (u_lower is None) == (u_upper is None)
         assert max_linesearch_iter > 0
@@ -214,6 +214,12 @@ class MPC(Module):
         # test_slew_rate_penalty_on_a_wide_network pin the general route by spying on HipBackend.mlp_rollout, a method a pre-bound
         # iteration never goes through (it calls mpc_mlp_rollout itself), and existing tests are the yardstick of every change
         self.planned_network_slew = bool(planned_network_slew)
+        # OPT-IN: a QuadCost / LinDx given in batch-shared form (C [T,n,n] or [n,n], c [T,n] or [n], F [T-1,ns,n] or [ns,n], f
+        # likewise) reaches the final no-op step UN-expanded, whose backward then sums the gradients over the batch inside the
+        # kernels (lqr_step._LQRStepSharedFn, mpc_lqr_kkt_grads_shared) instead of writing one [n,n] block per problem for
+        # autograd's expand to add up.  The iterations are untouched.  Slew-rate solves, module costs, `reference_du_norm` with a
+        # batch and views the caller expanded themselves keep the per-problem route.  Off by default (docs/history/r14.md)
+        self.shared_grad_kernel = bool(shared_grad_kernel)
         self.flag_reducer = None     # set by mpc.shard for lock-step sharded solves
         self.prev_ctrl = prev_ctrl
 
@@ -235,6 +241,26 @@ class MPC(Module):
             raise ValueError("MPC Error: Unexpected QuadCost shape.")
         return QuadCost(C, c)
 
+    def _expand_dx(self, dx, n_batch):
+        """[ns,n] / [T-1,ns,n] linear models (f [ns] / [T-1,ns], or None) are broadcast to [T-1,B,ns,n] as stride-0 views,
+        exactly like the cost."""
+        F, f = dx
+        ns, n = self.n_state, self.n_state + self.n_ctrl
+        if F.ndimension() == 2:
+            F = F.unsqueeze(0).unsqueeze(0).expand(self.T - 1, n_batch, ns, n)
+        elif F.ndimension() == 3:
+            F = F.unsqueeze(1).expand(self.T - 1, n_batch, ns, n)
+        if f is not None and f.numel() > 0:
+            if f.ndimension() == 1:
+                f = f.unsqueeze(0).unsqueeze(0).expand(self.T - 1, n_batch, ns)
+            elif f.ndimension() == 2:
+                f = f.unsqueeze(1).expand(self.T - 1, n_batch, ns)
+            if f.ndimension() != 3:
+                raise ValueError("MPC Error: Unexpected LinDx shape.")
+        if F.ndimension() != 4:
+            raise ValueError("MPC Error: Unexpected LinDx shape.")
+        return LinDx(F, f)
+
     def forward(self, x_init, cost, dx):
         assert isinstance(cost, (QuadCost, Module)) or callable(cost)
         assert isinstance(dx, (LinDx, Module)) or callable(dx)
@@ -244,8 +270,11 @@ class MPC(Module):
             n_batch = cost.C.size(1)
         else:
             raise ValueError("MPC Error: Could not infer batch size, pass in as n_batch")
+        given_cost, given_dx = cost, dx           # as the caller gave them: what `shared_grad_kernel` hands to the final step
         if isinstance(cost, QuadCost):
             cost = self._expand_cost(cost, n_batch)
+        if isinstance(dx, LinDx) and torch.is_tensor(dx.F) and dx.F.ndimension() < 4:
+            dx = self._expand_dx(dx, n_batch)
         assert x_init.ndimension() == 2 and x_init.size(0) == n_batch
 
         T, ns, nc = self.T, self.n_state, self.n_ctrl
@@ -300,8 +329,11 @@ class MPC(Module):
             # step of mpc/mpc.py:308-319 would only build a graph nobody can reach
             self._check_converged(full_du_norm)
             return (x, u, best["costs"])
+        # batch-shared arguments stay un-expanded for the final step (its Function expands them itself and returns their
+        # gradients summed over the batch); everything that keeps the per-problem route gets the views as before
+        shared = (self.shared_grad_kernel and isinstance(cost, QuadCost) and self.slew_rate_penalty is None and not ref_norm)
         if isinstance(dx, LinDx):
-            F, f = dx.F, dx.f
+            F, f = (given_dx.F, given_dx.f) if shared else (dx.F, dx.f)
         elif sim is not None and not _any_requires_grad(dx):
             # the simulator's parameters are constants here: closed-form kernel instead of autograd
             Fl, fl = be.env_linearize(sim, x[:-1].reshape(-1, ns), u[:-1].reshape(-1, nc))
@@ -309,12 +341,12 @@ class MPC(Module):
         else:
             F, f = self.linearize_dynamics(x, u, dx, diff=True)
         if isinstance(cost, QuadCost):
-            C, c = cost.C, cost.c
+            C, c = (given_cost.C, given_cost.c) if shared else (cost.C, cost.c)
         else:
             C, c, _ = self.approximate_cost(x, u, cost, diff=True)
 
         # attach the KKT backward at the best iterate (no compute), mpc/mpc.py:318-319
-        x, u = self.solve_lqr_subproblem(x_init, C, c, F, f, cost, dx, x, u, no_op_forward=True)
+        x, u = self.solve_lqr_subproblem(x_init, C, c, F, f, cost, dx, x, u, no_op_forward=True, shared_grad_kernel=shared)
 
         if self._check_converged(full_du_norm):
             keep = (full_du_norm < self.eps).to(x.dtype).view(1, -1, 1)
@@ -600,7 +632,7 @@ class MPC(Module):
                            delta_u=self.delta_u, linesearch_decay=self.linesearch_decay,
                            max_linesearch_iter=self.max_linesearch_iter)
 
-    def solve_lqr_subproblem(self, x_init, C, c, F, f, cost, dynamics, x, u, no_op_forward=False):
+    def solve_lqr_subproblem(self, x_init, C, c, F, f, cost, dynamics, x, u, no_op_forward=False, shared_grad_kernel=False):
         """Build the LQRStep for the current nominal (x,u) and apply it (mpc/mpc.py:339-361)."""
         if self.slew_rate_penalty is not None and not isinstance(cost, Module):
             return self._solve_slew_subproblem(x_init, C, c, F, f, cost, dynamics, x, u, no_op_forward)
@@ -611,7 +643,7 @@ class MPC(Module):
             linesearch_decay=self.linesearch_decay, max_linesearch_iter=self.max_linesearch_iter,
             delta_space=True, current_x=x, current_u=u, back_eps=self.back_eps,
             no_op_forward=no_op_forward, c_symmetric=no_op_forward and getattr(self, "_c_symmetric", False),
-            reference_du_norm=self.reference_du_norm and not no_op_forward)
+            reference_du_norm=self.reference_du_norm and not no_op_forward, shared_grad_kernel=shared_grad_kernel)
         empty = torch.empty(0, dtype=x_init.dtype, device=x_init.device)
         return step(x_init, C, c, F, f if f is not None else empty)
 
