@@ -212,6 +212,16 @@ int64_t mpc_lqr_workspace_bytes(const mpc_lqr_problem *p);
 int mpc_lqr_step(const mpc_lqr_problem *p, const mpc_lqr_options *o, const mpc_lqr_outputs *out,
                  void *workspace, int64_t workspace_bytes, int impl, void *stream);
 
+/* (ABI 9, additive) Which kernel mpc_lqr_step would launch for exactly these arguments: the `impl` code 1..8 of the list above, and in
+ * *ring (may be NULL) the depth of the sweep ring where the kernel has two (3: 2 or 4, 5: 2 or 3; 0 otherwise).  The same argument
+ * checks and the same decision as mpc_lqr_step, nothing launched: where that call would be refused, its negative code, with the same
+ * text in mpc_lqr_last_error().  0: B = 0 (mpc_lqr_step succeeds and launches nothing).  Every pointer -- the tensors of p, o and out,
+ * the workspace -- is inspected for NULL and alignment only, never dereferenced: no device is needed to ask.  (What a kernel's own
+ * launcher checks on top of the decision -- the 32/8 kernel wants out->new_x / new_u, and gains it parks in the workspace, on 16
+ * bytes -- is not anticipated.) */
+int mpc_lqr_step_route(const mpc_lqr_problem *p, const mpc_lqr_options *o, const mpc_lqr_outputs *out,
+                       const void *workspace, int64_t workspace_bytes, int impl, int *ring);
+
 /* (ABI 8) Where mpc_lqr_step (this p, o, impl; out->K / out->k NULL; a workspace of mpc_lqr_workspace_bytes) leaves the
  * solutions k_t of its sweep's box QPs inside `workspace`: byte offset of k[0][0][0] and the ELEMENT strides of its T and B
  * axes -- the array a later call at the same nominal may pass as o->qp_start (workspace + offset; that later call may be

@@ -119,50 +119,359 @@ static int check_options(const mpc_lqr_problem *p, const mpc_lqr_options *o)
     return MPC_OK;
 }
 
-// floats of the padded 32/8 instantiation's workspace: K [T,B,8,32] | k [T,B,8] | (M, Quu, m) [T,B,328] | second trial [T,B,40]
-static int64_t pad_workspace_bytes(int T, int B) { return (int64_t)T * B * (256 + 8 + 328 + 40) * 4; }
+// ---------------------------------------------------------------------------------------------------------------------
+// The kernels behind mpc_lqr_step (MPC_IMPL_*, lqr_common.h): what each one takes, what it keeps in the workspace, and -- step_route
+// -- which of them takes a call.  mpc_lqr_step, mpc_lqr_step_route, mpc_lqr_impl_supported, mpc_lqr_qp_record and
+// mpc_lqr_workspace_bytes all ask here; nothing else in this file spells out a kernel's shape or a record's size.
+// ---------------------------------------------------------------------------------------------------------------------
 
-// where a caller's missing status array lives inside the workspace: behind the larger of the two uses of it
+// the sizes of a call and its simulator kind, nothing else: default options, no tensors (so every block counts as aligned)
+static mpc_lqr_problem sizes_only(int B, int T, int ns, int nc, int dtype)
+{
+    mpc_lqr_problem q;
+    memset(&q, 0, sizeof(q));
+    q.B = B; q.T = T; q.ns = ns; q.nc = nc; q.dtype = dtype;
+    return q;
+}
+template <typename real>
+static StepParams<real> sizes_only(const StepParams<real> &sp)
+{
+    const mpc_lqr_problem q = sizes_only(sp.B, sp.T, sp.ns, sp.nc, sizeof(real) == 4 ? MPC_F32 : MPC_F64);
+    StepParams<real> s = make_params<real>(&q, nullptr, nullptr);
+    s.env.kind = sp.env.kind;
+    return s;
+}
+
+// Does `kernel` take this call, by its own rule (lqr_*.hip)?  query: the form mpc_lqr_impl_supported asks -- sizes, dtype and options;
+// the alignment of the actual tensors is checked at launch.  The two exact kernels (12/4, 32/8), whose rule looks at the tensors,
+// answer a query from the sizes alone, as their queries always have; the others never look at a problem tensor.
+template <typename real>
+static bool kernel_takes(int kernel, const StepParams<real> &sp, bool query = false)
+{
+    if (kernel == MPC_IMPL_GENERIC) return generic_lds_bytes(sp.ns, sp.nc, sizeof(real)) <= 160 * 1024;
+    if (kernel == MPC_IMPL_TINY) return tiny_supported(sp.ns, sp.nc);
+    if (kernel == MPC_IMPL_MFMA16) return mfma16_supported(sp);
+    if constexpr (sizeof(real) == 4) {
+        switch (kernel) {
+        case MPC_IMPL_DPP16: return dpp16_supported(query ? sizes_only(sp) : sp);
+        case MPC_IMPL_DPP16_PAD: return dpp16_pad_supported(sp);
+        case MPC_IMPL_MFMA40: return mfma40_supported(query ? sizes_only(sp) : sp);
+        case MPC_IMPL_MFMA40_PAD: return mfma40_pad_supported(sp);
+        case MPC_IMPL_WAVE1: return tiny_supported(sp.ns, sp.nc) && wave1_supported(sp);
+        }
+    }
+    return false;
+}
+
+// the kernels that can stop after their sweep (MPC_OPT_SWEEP_ONLY): the 12/4 and 32/8 fused ones, exact and padded; a call heading
+// for any other kernel takes the generic sweep
+static bool stops_after_sweep(int kernel)
+{
+    return kernel == MPC_IMPL_DPP16 || kernel == MPC_IMPL_DPP16_PAD || kernel == MPC_IMPL_MFMA40 || kernel == MPC_IMPL_MFMA40_PAD;
+}
+
+// What a kernel keeps in the workspace, in bytes from its start (-1: not there): the gains K | k where the caller passes none, its own
+// record Kk, all it asks for (`bytes`), and the k_t of its box QPs a later step may start from (qp: byte offset, element strides).
+struct WsLayout {
+    int64_t K, k, Kk, bytes, qp, qp_st, qp_sb;
+};
+template <typename real>
+static WsLayout ws_layout(int kernel, int T, int B, int ns, int nc)
+{
+    const int64_t TB = (int64_t)T * B, e = sizeof(real), needK = TB * nc * ns * e, needk = TB * nc * e;
+    WsLayout w = {0, needK, -1, needK + needk, -1, 0, 0};            // the generic kernels: K [T,B,nc,ns] | k [T,B,nc]
+    switch (kernel) {
+    case MPC_IMPL_TINY:
+    case MPC_IMPL_WAVE1:
+        // one lane per problem; gains parked as [T][ns+1][B], behind them one trajectory column [T][ns+1] per line-search trial
+        // lane (<= 8 per problem): 9 (ns + 1) reals per problem-step <= 504 bytes
+        w.Kk = 0; w.bytes = (needK + needk) * 9;
+        break;
+    case MPC_IMPL_MFMA16:
+    case MPC_IMPL_DPP16:
+    case MPC_IMPL_DPP16_PAD:
+        // the fused kernels park their gains [T,B,64] in the workspace; float32: gain record + (m, M) record + the second line-search
+        // trial's trajectory (box-constrained 12/4 kernel)
+        w.Kk = 0; w.bytes = e == 4 ? TB * (128 + 16) * 4 : TB * 64 * 8;
+        // the 12/4 kernel's gain record Kk[t][b][lane 0..15][4]: lane 12 holds k
+        if (kernel == MPC_IMPL_DPP16) { w.qp = 48 * 4; w.qp_st = (int64_t)B * 64; w.qp_sb = 64; }
+        break;
+    case MPC_IMPL_MFMA40:
+        // the constrained modes park (M, Quu, m) [T,B,328] + the second trial's trajectory [T,B,40] behind the gains, for the rollout
+        // that prices without C
+        w.Kk = needK + needk; w.bytes = w.Kk + TB * (328 + 40) * 4;
+        w.qp = w.k; w.qp_st = (int64_t)B * nc; w.qp_sb = nc;
+        break;
+    case MPC_IMPL_MFMA40_PAD:
+        // the kernel's own padded gains K [T,B,8,32] | k [T,B,8] (entries >= n_ctrl zero) | (M, Quu, m) [T,B,328] | second trial [T,B,40]
+        w.K = 0; w.k = TB * 256 * 4; w.Kk = w.k + TB * 8 * 4; w.bytes = w.Kk + TB * (328 + 40) * 4;
+        w.qp = w.k; w.qp_st = (int64_t)B * 8; w.qp_sb = 8;
+        break;
+    }
+    return w;
+}
+
+// where a caller's missing status array lives inside the workspace: behind the largest layout among the kernels the shape can reach
+// -- and never in front of the float32 12/4-class record, whatever the shape and dtype (the size callers have always been handed)
+template <typename real>
+static int64_t largest_layout(const mpc_lqr_problem *p)
+{
+    const mpc_lqr_problem q = sizes_only(p->B, p->T, p->ns, p->nc, p->dtype);
+    const StepParams<real> s = make_params<real>(&q, nullptr, nullptr);
+    int64_t m = ws_layout<float>(MPC_IMPL_DPP16, p->T, p->B, p->ns, p->nc).bytes;
+    for (int kernel = MPC_IMPL_GENERIC; kernel <= MPC_IMPL_DPP16_PAD; ++kernel) {
+        const int64_t b = ws_layout<real>(kernel, p->T, p->B, p->ns, p->nc).bytes;
+        if ((kernel == MPC_IMPL_GENERIC || kernel_takes<real>(kernel, s, true)) && b > m) m = b;
+    }
+    return m;
+}
 static int64_t status_scratch_offset(const mpc_lqr_problem *p)
 {
-    const int64_t e = p->dtype == MPC_F64 ? 8 : 4;
-    int64_t generic = ((int64_t)p->T * p->B * p->nc * p->ns + (int64_t)p->T * p->B * p->nc) * e;
-    // the 32/8 kernel's constrained modes park (M, Quu, m) behind the gains for the rollout that prices without C
-    if (p->dtype == MPC_F32 && p->ns == 32 && p->nc == 8) generic += (int64_t)p->T * p->B * (328 + 40) * 4;   // + the second trial's trajectory
-    // its padded instantiation (any n_state <= 32, n_ctrl <= 8): the kernel's own padded gains [T,B,8,32] | [T,B,8] + the same records
-    else if (p->dtype == MPC_F32 && p->ns <= 32 && p->nc <= 8) {
-        const int64_t pad = pad_workspace_bytes(p->T, p->B);
-        generic = generic > pad ? generic : pad;
-    }
-    const int64_t fused = (int64_t)p->T * p->B * (128 + 16) * 4;     // gain records of the fused kernels + the second
-                                                                       // line-search trial's trajectory (box-constrained 12/4 kernel)
-    return ((generic > fused ? generic : fused) + 15) & ~(int64_t)15;
+    return ((p->dtype == MPC_F64 ? largest_layout<double>(p) : largest_layout<float>(p)) + 15) & ~(int64_t)15;
 }
+
+// A lane per problem leaves the chip empty at the batch sizes iLQR is run at (B = 1024: 16 .. 128 wavefronts
+// on 1024 SIMDs) and its time is one lane's instruction count times the horizon; a 16-lane row per problem
+// does everything that is independent over t for 16 timesteps at once and every line-search trial at once.
+// Worth its sixteen lanes while all its wavefronts are resident together, at most two to a SIMD (measured,
+// profiles/r03_experiments.md section 6: pendulum up to B = 8192, cart-pole -- 39.6 KB of LDS per wavefront --
+// up to 4096; twice that and the lane-per-problem kernel is level or ahead).
+static bool wave1_pays(const StepParams<float> &sp)
+{
+    if (!wave1_supported(sp)) return false;
+    const long per_cu = (160L * 1024) / wave1_lds_bytes(sp);
+    return (sp.B + 3) / 4 <= (device_facts().simds / 4) * (per_cu < 8 ? per_cu : 8);
+}
+static bool wave1_pays(const StepParams<double> &) { return false; }
+
+// ring depth of the 12/4 kernel (lqr_dpp16.hip): the unconstrained step always on the short ring; the constrained one there
+// only when the batch has more waves (4 problems each) than the chip has SIMDs (256 CUs x 4)
+static int dpp16_ring(const StepParams<float> &sp)
+{
+    const bool constrained = sp.bound_mode != MPC_BOUND_NONE || sp.zero_mask != nullptr;
+    const int force = dpp16_ring_force();
+    return (force ? force == 2 : (!constrained || (sp.B + 3) / 4 > device_facts().simds)) ? 2 : 4;
+}
+
+// Which kernel takes this call, and where its pieces live in the workspace.  Launches nothing, sets no error state, allocates
+// nothing; never cached (the answer depends on the pointers and, with MPC_DPP16_RING_DYNAMIC, on the environment).
+template <typename real>
+StepRoute step_route(const StepParams<real> &sp, const mpc_lqr_problem *p, int impl, int phase_mask, const void *workspace,
+                     int64_t workspace_bytes)
+{
+    constexpr bool f32 = sizeof(real) == 4;
+    StepRoute r;
+    r.code = 0; r.msg = nullptr; r.kernel = 0; r.phase = phase_mask; r.ring = 0; r.pad16 = false; r.needs_resolve = false;
+    r.K_off = r.k_off = r.Kk_off = r.status_off = r.qp_off = -1; r.qp_st = r.qp_sb = 0;
+    const auto refuse = [&r](int code, const char *msg) { r.code = code; r.msg = msg; return r; };
+    const bool step = phase_mask == 3, aligned = (uintptr_t)workspace % 16 == 0, tiny = tiny_supported(sp.ns, sp.nc);
+    const auto room = [&](int64_t bytes) { return workspace && workspace_bytes >= bytes; };
+    const auto layout = [&](int kernel) { return ws_layout<real>(kernel, sp.T, sp.B, sp.ns, sp.nc); };
+    // a kernel takes the call: by its own rule; with a simulator only the lane- / row-per-problem and the generic kernels; and with the
+    // workspace where the call falls through to the next kernel without it -- the padded 32/8 instantiation (its padded gains and the
+    // constrained modes' records, 16-byte aligned) and the float64 MFMA kernel (a caller written against ABI 7 -- out->K /
+    // out->k given, no or a small workspace -- keeps the generic kernel under impl 0)
+    const auto takes_now = [&](int kernel) {
+        if (!kernel_takes<real>(kernel, sp)) return false;
+        if (kernel == MPC_IMPL_GENERIC || kernel == MPC_IMPL_TINY || kernel == MPC_IMPL_WAVE1) return true;
+        if (sp.env.kind) return false;
+        if (kernel == MPC_IMPL_MFMA40_PAD || (!f32 && kernel == MPC_IMPL_MFMA16)) return room(layout(kernel).bytes) && aligned;
+        return true;
+    };
+    signed char asked[MPC_IMPL_DPP16_PAD + 1] = {-1, -1, -1, -1, -1, -1, -1, -1, -1};      // each kernel is asked once per call
+    const auto takes = [&](int kernel) {
+        if (kernel < MPC_IMPL_GENERIC || kernel > MPC_IMPL_DPP16_PAD) return false;
+        if (asked[kernel] < 0) asked[kernel] = takes_now(kernel);
+        return asked[kernel] != 0;
+    };
+    // a fused kernel took the call: under impl 0 the problems it flags MPC_ST_C_ASYMMETRIC are solved again (resolve_asymmetric)
+    const auto fused = [&](int kernel, const WsLayout &w) {
+        r.kernel = kernel;
+        r.Kk_off = w.Kk;
+        r.needs_resolve = impl == 0 && !sp.c_symmetric;
+        return r;
+    };
+
+    // The kernel the call is heading for: the forced one, or under impl 0 the first of this order that takes it -- the one-control
+    // shapes up to six states on the lane- / row-per-problem kernels; 12/4 on its own kernel; every other float32 shape up to 12/4,
+    // and 12/4 itself where a block is not 16-byte aligned, on that kernel's PADDED instantiation (round 6; ahead of the
+    // one-problem-per-wavefront kernel that served them in rounds 1-5 and still serves float64: round 5, v_mfma_f64_16x16x4_f64, what
+    // every test and gradient check of the reference runs in, tests/test_mpc.py .double()); 32/8 on its own kernel; every float32
+    // shape up to 32/8 that has no kernel of its own (13/4, 20/5, 24/8, 32/4, 8/6 ...) on the 32/8 kernel's PADDED instantiation
+    // (lqr_mfma40_body.h, PADK) -- the reference's sweep is shape-agnostic (mpc/lqr_step.py:61-158), and between the hand-tuned
+    // shapes the generic kernel ran at 4 % of the roofline (missing 1); everything else on the generic kernels.
+    int kernel = impl;
+    if (impl == 0) {
+        kernel = MPC_IMPL_GENERIC;
+        if (step && tiny) kernel = wave1_pays(sp) ? MPC_IMPL_WAVE1 : MPC_IMPL_TINY;
+        else if (step)
+            for (int next : {MPC_IMPL_DPP16, MPC_IMPL_DPP16_PAD, MPC_IMPL_MFMA16, MPC_IMPL_MFMA40, MPC_IMPL_MFMA40_PAD})
+                if (takes(next)) { kernel = next; break; }
+    }
+
+    // the symmetry verdict travels in the status words: a caller that passes none gets them parked behind the workspace
+    if (!sp.status && step && workspace) {
+        const int64_t off = status_scratch_offset(p);
+        if (workspace_bytes >= off + (int64_t)sp.B * 4) r.status_off = off;
+    }
+    if ((phase_mask & 2) && !sp.sweep_only && (!sp.new_x || !sp.new_u)) return refuse(MPC_E_NULL, "new_x / new_u is NULL");
+    if (sp.sweep_only) {
+        if (!step) return refuse(MPC_E_ARG, "MPC_OPT_SWEEP_ONLY is an option of mpc_lqr_step");
+        if (!sp.K || !sp.k) return refuse(MPC_E_NULL, "MPC_OPT_SWEEP_ONLY needs out->K and out->k");
+        if (sp.env.kind) return refuse(MPC_E_ARG, "MPC_OPT_SWEEP_ONLY with a simulator as true_dynamics");
+        if (!(stops_after_sweep(kernel) && takes(kernel))) {
+            if (impl != 0 && impl != 1) return refuse(MPC_E_ARG, "MPC_OPT_SWEEP_ONLY: this kernel cannot stop after its sweep");
+            r.kernel = MPC_IMPL_GENERIC;
+            r.phase = 1;
+            return r;
+        }
+    }
+    // MPC_ENV_CTRL_CARRY: the lane-per-problem kernel carries the control (lqr_tiny_body.h); the row-per-problem and the generic
+    // kernels call the simulator as it is and REFUSE the flag -- never a silent un-augmented answer
+    if (sp.env.carry && (!step || (impl != 0 && impl != 4)))
+        return refuse(MPC_E_UNSUPPORTED, "MPC_ENV_CTRL_CARRY: only mpc_lqr_step on the lane-per-problem kernel (impl 0 or 4) carries the control");
+    if (sp.env.kind && sp.env.linearize && !(step && tiny && (impl == 0 || impl == 4 || impl == 6)))
+        return refuse(MPC_E_ARG, "in-kernel linearisation needs the lane-per-problem kernel (n_ctrl = 1, n_state <= 6)");
+    if (sp.env.kind && (impl == 2 || impl == 3 || impl == 8))
+        return refuse(MPC_E_ARG, "a simulator as true_dynamics runs on the generic kernels only");
+    if ((impl == 4 || impl == 6) && (!step || !tiny))
+        return refuse(MPC_E_DIMS, "lane-per-problem / wavefront-per-problem kernel needs n_ctrl = 1, n_state <= 6");
+    if (impl == 6 && !takes(MPC_IMPL_WAVE1))
+        return refuse(MPC_E_DIMS, "the row-per-problem kernel is float32, max_linesearch_iter <= 16, four problems in 150 KiB of LDS");
+    if (step && (kernel == MPC_IMPL_TINY || kernel == MPC_IMPL_WAVE1)) {
+        // (these kernels keep Q and V as general matrices, like the reference: nothing to test, nothing to re-solve)
+        const WsLayout w = layout(kernel);
+        if (!room(w.bytes)) return refuse(MPC_E_ARG, "workspace too small (see mpc_lqr_workspace_bytes)");
+        r.kernel = kernel;
+        r.Kk_off = w.Kk;
+        return r;
+    }
+    if (step && impl != 1 && !sp.env.kind) {
+        const bool half_gains = (sp.K == nullptr) != (sp.k == nullptr);
+        const WsLayout w = layout(MPC_IMPL_MFMA16);                   // out->K / out->k are optional on these three kernels
+        if constexpr (f32) {
+            if (half_gains) return refuse(MPC_E_NULL, "pass both K and k, or neither");
+            const bool dpp = takes(MPC_IMPL_DPP16), mfma = takes(MPC_IMPL_MFMA16), dpad = takes(MPC_IMPL_DPP16_PAD);
+            if (impl == 3 && !dpp)
+                return refuse(MPC_E_DIMS, "DPP kernel needs fp32, n_state = 12, n_ctrl = 4 and 16-byte aligned blocks");
+            if (impl == 8 && !dpad)
+                return refuse(MPC_E_DIMS, "padded DPP kernel needs fp32, n_state <= 12, n_ctrl <= 4, max_linesearch_iter <= 16");
+            if (impl == 2 && !mfma)
+                return refuse(MPC_E_DIMS, "fused MFMA kernel needs fp32, n_state <= 12, n_ctrl <= 4, max_linesearch_iter <= 16");
+            if ((impl == 3 || impl == 2 || impl == 8 || dpp || mfma || dpad) && !(room(w.bytes) && aligned))
+                return refuse(MPC_E_ARG, "workspace too small or not 16-byte aligned (see mpc_lqr_workspace_bytes)");
+            if (kernel == MPC_IMPL_DPP16 || kernel == MPC_IMPL_DPP16_PAD || kernel == MPC_IMPL_MFMA16) {
+                const WsLayout wk = layout(kernel);
+                if (kernel == MPC_IMPL_DPP16) r.ring = dpp16_ring(sp);
+                r.qp_off = wk.qp; r.qp_st = wk.qp_st; r.qp_sb = wk.qp_sb;
+                return fused(kernel, wk);
+            }
+        } else {
+            if (impl == 3 || impl == 8) return refuse(MPC_E_DTYPE, "the 4-problems-per-wave kernel is fp32 only");
+            if (impl == 2 && !mfma16_supported(sp))
+                return refuse(MPC_E_DIMS, "fused MFMA kernel needs n_state <= 12, n_ctrl <= 4, max_linesearch_iter <= 16");
+            // (only a FORCED impl 2 insists on the fused kernel's workspace)
+            if (impl == 2 && !takes(impl))
+                return refuse(MPC_E_ARG, "workspace too small or not 16-byte aligned (see mpc_lqr_workspace_bytes)");
+            if (takes(MPC_IMPL_MFMA16)) {                             // (whatever impl asked for, as ever: a forced 5 or 7 lands here too)
+                if (half_gains) return refuse(MPC_E_NULL, "pass both K and k, or neither");
+                return fused(MPC_IMPL_MFMA16, w);
+            }
+        }
+    }
+    if constexpr (f32) {
+        if (impl == 7 && !(step && takes(impl)))
+            return refuse(MPC_E_DIMS, "padded MFMA kernel needs fp32, n_state <= 32, n_ctrl <= 8, max_linesearch_iter <= 16, no simulator, and the "
+                                      "workspace of mpc_lqr_workspace_bytes (16-byte aligned)");
+        if (step && kernel == MPC_IMPL_MFMA40_PAD) {
+            const WsLayout w = layout(kernel);
+            r.K_off = w.K; r.k_off = w.k;
+            r.pad16 = mfma40_pad16_supported(sp);
+            r.qp_off = w.qp; r.qp_st = w.qp_st; r.qp_sb = w.qp_sb;
+            return fused(kernel, w);
+        }
+    }
+    if (!sp.K || !sp.k) {
+        const WsLayout w = layout(MPC_IMPL_GENERIC);
+        if (!step) return refuse(MPC_E_NULL, "K / k is NULL");
+        if (!room(w.bytes)) return refuse(MPC_E_ARG, "workspace too small (see mpc_lqr_workspace_bytes)");
+        r.K_off = w.K; r.k_off = w.k;
+    }
+    if constexpr (f32) {
+        // n_state = 32, n_ctrl = 8: register-resident MFMA sweep and rollout (lqr_mfma40_body.h)
+        if (impl == 5 && !(step && takes(impl)))
+            return refuse(MPC_E_DIMS, "MFMA kernel needs fp32, n_state = 32, n_ctrl = 8, 16-byte aligned blocks, no simulator");
+        if (step && kernel == MPC_IMPL_MFMA40) {
+            WsLayout w = layout(kernel);
+            // (M, Quu, m) record of the constrained modes: behind K | k where the workspace has the room (rollout_priced)
+            if (!((sp.bound_mode != MPC_BOUND_NONE || sp.zero_mask) && room(w.bytes) && aligned)) w.Kk = -1;
+            r.ring = mfma40_ring(sp);
+            if (r.K_off >= 0) { r.qp_off = w.qp; r.qp_st = w.qp_st; r.qp_sb = w.qp_sb; }
+            return fused(kernel, w);
+        }
+    } else if (impl == 5) {
+        return refuse(MPC_E_DTYPE, "the MFMA sweep is fp32 only");
+    }
+    r.kernel = MPC_IMPL_GENERIC;
+    return r;
+}
+
+// (instantiated here, and so visible in the library, for tests/step_route_probe.cpp alone, which prints the whole route on the host:
+// an internal C++ template over StepParams, NOT part of the API -- that is include/mpc_lqr.h, and mpc_lqr_step_route is its query)
+template StepRoute step_route<float>(const StepParams<float> &, const mpc_lqr_problem *, int, int, const void *, int64_t);
+template StepRoute step_route<double>(const StepParams<double> &, const mpc_lqr_problem *, int, int, const void *, int64_t);
 
 // After a fused kernel under impl = 0 (auto): the problems it flagged MPC_ST_C_ASYMMETRIC are solved again by the generic
 // kernels, which use C exactly as the reference does (mpc/lqr_step.py:68, 294); everything else is left as it is.  A
 // compact grid reads the flags -- no host round trip, nothing to synchronise on.
 template <typename real>
-static int resolve_asymmetric(StepParams<real> sp, int impl, void *workspace, int64_t needK, hipStream_t st)
+static int resolve_asymmetric(StepParams<real> sp, void *workspace, hipStream_t st)
 {
-    if (impl != 0 || sp.c_symmetric || !sp.status) return MPC_OK;
+    if (!sp.status) return MPC_OK;
     if (sp.env.kind && sp.env.linearize) return MPC_OK;      // no F, f arrays to fall back on: the bit is the answer
     sp.gate = sp.status;
     sp.Kk = nullptr;
     if (!sp.K || !sp.k) {
-        sp.K = (real *)workspace;
-        sp.k = (real *)((char *)workspace + needK);
+        const WsLayout w = ws_layout<real>(MPC_IMPL_GENERIC, sp.T, sp.B, sp.ns, sp.nc);
+        sp.K = (real *)((char *)workspace + w.K);
+        sp.k = (real *)((char *)workspace + w.k);
     }
     return launch_step_generic<real>(sp, sp.sweep_only ? 1 : 3, st);
 }
 
-// may this call take the padded 32/8 instantiation?  (shape and options: mfma40_pad_supported; its workspace: the padded gains
-// and the constrained modes' records, 16-byte aligned)
-static bool pad_route(const StepParams<float> &sp, const void *workspace, int64_t workspace_bytes)
+// one launch per kernel
+static int launch_routed(const StepRoute &r, const StepParams<float> &q, hipStream_t st)
 {
-    return mfma40_pad_supported(sp) && workspace && ((uintptr_t)workspace % 16 == 0) && workspace_bytes >= pad_workspace_bytes(sp.T, sp.B);
+    switch (r.kernel) {
+    case MPC_IMPL_GENERIC: return launch_step_generic<float>(q, r.phase, st);
+    case MPC_IMPL_MFMA16: return launch_step_mfma16(q, st);
+    case MPC_IMPL_DPP16: return r.ring == 2 ? launch_step_dpp16_ring2(q, st) : launch_step_dpp16(q, st);
+    case MPC_IMPL_TINY: return launch_step_tiny<float>(q, st);
+    case MPC_IMPL_MFMA40: return r.ring == 2 ? launch_step_mfma40_ring2(q, st) : launch_step_mfma40(q, st);
+    case MPC_IMPL_WAVE1: return launch_step_wave1(q, st);
+    case MPC_IMPL_MFMA40_PAD: return r.pad16 ? launch_step_mfma40_pad16(q, st) : launch_step_mfma40_pad4(q, st);
+    case MPC_IMPL_DPP16_PAD: return launch_step_dpp16_pad(q, st);
+    }
+    return MPC_E_ARG;
 }
-static bool pad_route(const StepParams<double> &, const void *, int64_t) { return false; }
+static int launch_routed(const StepRoute &r, const StepParams<double> &q, hipStream_t st)
+{
+    switch (r.kernel) {
+    case MPC_IMPL_GENERIC: return launch_step_generic<double>(q, r.phase, st);
+    case MPC_IMPL_MFMA16: return launch_step_mfma16(q, st);
+    case MPC_IMPL_TINY: return launch_step_tiny<double>(q, st);
+    }
+    return MPC_E_ARG;
+}
+
+// mpc_lqr_options.qp_start is a hint: an array the staging DMAs cannot fetch (16-byte granules) is ignored, not an error
+template <typename real>
+static void filter_qp_start(StepParams<real> &sp)
+{
+    if (sp.qp_start && (sp.bound_mode == MPC_BOUND_NONE || (uintptr_t)sp.qp_start % 16 || sp.qp_start_st % 4 || sp.qp_start_sb % 4 ||
+                        sp.qp_start_st < 0 || sp.qp_start_sb < 0 || sp.qp_start_st * 4 >= (1ll << 32) || sizeof(real) != 4))
+        sp.qp_start = nullptr;
+}
 
 template <typename real>
 static int step_impl(const mpc_lqr_problem *p, const mpc_lqr_options *o, const mpc_lqr_outputs *out,
@@ -171,181 +480,45 @@ static int step_impl(const mpc_lqr_problem *p, const mpc_lqr_options *o, const m
 {
     StepParams<real> sp = make_params<real>(p, o, out);
     sp.old_costs_in = (const real *)old_costs_in;
-    // mpc_lqr_options.qp_start is a hint: an array the staging DMAs cannot fetch (16-byte granules) is ignored, not an error
-    if (sp.qp_start && (sp.bound_mode == MPC_BOUND_NONE || (uintptr_t)sp.qp_start % 16 || sp.qp_start_st % 4 || sp.qp_start_sb % 4 ||
-                        sp.qp_start_st < 0 || sp.qp_start_sb < 0 || sp.qp_start_st * 4 >= (1ll << 32) || sizeof(real) != 4))
-        sp.qp_start = nullptr;
-    // the symmetry verdict travels in the status words: a caller that passes none gets them parked behind the workspace
-    if (!sp.status && phase_mask == 3 && workspace) {
-        const int64_t off = status_scratch_offset(p);
-        if (workspace_bytes >= off + (int64_t)p->B * 4) sp.status = (int *)((char *)workspace + off);
+    filter_qp_start(sp);
+    const StepRoute r = step_route(sp, p, impl, phase_mask, workspace, workspace_bytes);
+    if (r.code) return fail(r.code, r.msg);
+    const auto at = [workspace](int64_t off) { return off < 0 ? nullptr : (char *)workspace + off; };
+    if (r.status_off >= 0) sp.status = (int *)at(r.status_off);
+    real *const K_caller = sp.K, *const k_caller = sp.k;
+    sp.Kk = (real *)at(r.Kk_off);
+    if (r.K_off >= 0) {                          // gains where the route put them
+        if (r.kernel == MPC_IMPL_MFMA40_PAD) { sp.K_user = sp.K; sp.k_user = sp.k; }
+        sp.K = (real *)at(r.K_off);
+        sp.k = (real *)at(r.k_off);
     }
-    if ((phase_mask & 2) && !sp.sweep_only) {
-        if (!sp.new_x || !sp.new_u) return fail(MPC_E_NULL, "new_x / new_u is NULL");
-    }
-    const int64_t needK = (int64_t)p->T * p->B * p->nc * p->ns * (int64_t)sizeof(real);
-    const int64_t needk = (int64_t)p->T * p->B * p->nc * (int64_t)sizeof(real);
-    if (sp.sweep_only) {
-        if (phase_mask != 3) return fail(MPC_E_ARG, "MPC_OPT_SWEEP_ONLY is an option of mpc_lqr_step");
-        if (!sp.K || !sp.k) return fail(MPC_E_NULL, "MPC_OPT_SWEEP_ONLY needs out->K and out->k");
-        if (sp.env.kind) return fail(MPC_E_ARG, "MPC_OPT_SWEEP_ONLY with a simulator as true_dynamics");
-        // the kernels that can stop after their sweep: the 12/4 and 32/8 fused ones; every other shape takes the generic sweep
-        bool fused = false;
-        if constexpr (sizeof(real) == 4) fused = (impl == 0 || impl == 3) ? dpp16_supported(sp) : false;
-        // (round 6: the padded 12/4 instantiation stops after its sweep like the exact kernel -- where the call reaches it: under impl 0
-        // the one-control shapes up to six states belong to the lane-per-problem kernels in front of it, which cannot)
-        if constexpr (sizeof(real) == 4)
-            fused = fused || ((impl == 8 || (impl == 0 && !tiny_supported(p->ns, p->nc))) && dpp16_pad_supported(sp));
-        if constexpr (sizeof(real) == 4) fused = fused || ((impl == 0 || impl == 5) && mfma40_supported(sp));
-        // (the padded 32/8 instantiation can stop after its sweep too -- for the shapes that reach it: under impl 0 the 12/4-class
-        // shapes belong to kernels in front of it that cannot, and keep the generic sweep they had)
-        if constexpr (sizeof(real) == 4)
-            fused = fused || (pad_route(sp, workspace, workspace_bytes) &&
-                              (impl == 7 || (impl == 0 && !mfma16_supported(sp) && !tiny_supported(p->ns, p->nc))));
-        if (!fused) {
-            if (impl != 0 && impl != 1) return fail(MPC_E_ARG, "MPC_OPT_SWEEP_ONLY: this kernel cannot stop after its sweep");
-            return launch_step_generic<real>(sp, 1, st);
-        }
-    }
-    // MPC_ENV_CTRL_CARRY: the lane-per-problem kernel carries the control (lqr_tiny_body.h); the row-per-problem and the generic
-    // kernels call the simulator as it is and REFUSE the flag -- never a silent un-augmented answer
-    if (sp.env.carry && (phase_mask != 3 || (impl != 0 && impl != 4)))
-        return fail(MPC_E_UNSUPPORTED, "MPC_ENV_CTRL_CARRY: only mpc_lqr_step on the lane-per-problem kernel (impl 0 or 4) carries the control");
-    if (sp.env.kind && sp.env.linearize && !(phase_mask == 3 && tiny_supported(p->ns, p->nc) && (impl == 0 || impl == 4 || impl == 6)))
-        return fail(MPC_E_ARG, "in-kernel linearisation needs the lane-per-problem kernel (n_ctrl = 1, n_state <= 6)");
-    if (sp.env.kind && (impl == 2 || impl == 3 || impl == 8))
-        return fail(MPC_E_ARG, "a simulator as true_dynamics runs on the generic kernels only");
-    if ((impl == 4 || impl == 6) && (phase_mask != 3 || !tiny_supported(p->ns, p->nc)))
-        return fail(MPC_E_DIMS, "lane-per-problem / wavefront-per-problem kernel needs n_ctrl = 1, n_state <= 6");
-    if (impl == 6) {
-        bool ok = false;
-        if constexpr (sizeof(real) == 4) ok = wave1_supported(sp);
-        if (!ok) return fail(MPC_E_DIMS, "the row-per-problem kernel is float32, max_linesearch_iter <= 16, four problems in 150 KiB of LDS");
-    }
-    if (phase_mask == 3 && (impl == 4 || impl == 6 || (impl == 0 && tiny_supported(p->ns, p->nc)))) {
-        // one lane per problem; gains parked in the workspace as [T][ns+1][B], behind them one trajectory column
-        // [T][ns+1] per line-search trial lane (<= 8 per problem): 9 (ns + 1) reals per problem-step <= 504 bytes
-        if (!workspace || workspace_bytes < (needK + needk) * 9)
-            return fail(MPC_E_ARG, "workspace too small (see mpc_lqr_workspace_bytes)");
-        sp.Kk = (real *)workspace;
-        // (these kernels keep Q and V as general matrices, like the reference: nothing to test, nothing to re-solve)
-        if constexpr (sizeof(real) == 4) {
-            // A lane per problem leaves the chip empty at the batch sizes iLQR is run at (B = 1024: 16 .. 128 wavefronts
-            // on 1024 SIMDs) and its time is one lane's instruction count times the horizon; a 16-lane row per problem
-            // does everything that is independent over t for 16 timesteps at once and every line-search trial at once.
-            // Worth its sixteen lanes while all its wavefronts are resident together, at most two to a SIMD (measured,
-            // profiles/r03_experiments.md section 6: pendulum up to B = 8192, cart-pole -- 39.6 KB of LDS per wavefront --
-            // up to 4096; twice that and the lane-per-problem kernel is level or ahead).
-            bool wide = impl == 6;
-            if (impl == 0 && wave1_supported(sp)) {
-                const long per_cu = (160L * 1024) / wave1_lds_bytes(sp);
-                wide = (p->B + 3) / 4 <= (device_facts().simds / 4) * (per_cu < 8 ? per_cu : 8);
-            }
-            if (wide) return launch_step_wave1(sp, st);
-        }
-        return launch_step_tiny<real>(sp, st);
-    }
-    if (phase_mask == 3 && impl != 1 && !sp.env.kind) {
-        if constexpr (sizeof(real) == 4) {
-            // the fused kernels park their gains [T,B,64] in the workspace; out->K / out->k are optional
-            const int64_t need = (int64_t)p->T * p->B * (128 + 16) * (int64_t)sizeof(float);   // gain record + (m, M) record + trial trajectory
-            const bool have_ws = workspace && workspace_bytes >= need && ((uintptr_t)workspace % 16 == 0);
-            if ((sp.K == nullptr) != (sp.k == nullptr)) return fail(MPC_E_NULL, "pass both K and k, or neither");
-            sp.Kk = (float *)workspace;
-            const bool dpp = dpp16_supported(sp), mfma = mfma16_supported(sp), dpad = dpp16_pad_supported(sp);
-            if (impl == 3 && !dpp)
-                return fail(MPC_E_DIMS, "DPP kernel needs fp32, n_state = 12, n_ctrl = 4 and 16-byte aligned blocks");
-            if (impl == 8 && !dpad)
-                return fail(MPC_E_DIMS, "padded DPP kernel needs fp32, n_state <= 12, n_ctrl <= 4, max_linesearch_iter <= 16");
-            if (impl == 2 && !mfma)
-                return fail(MPC_E_DIMS, "fused MFMA kernel needs fp32, n_state <= 12, n_ctrl <= 4, max_linesearch_iter <= 16");
-            if ((impl == 3 || impl == 2 || impl == 8 || dpp || mfma || dpad) && !have_ws)
-                return fail(MPC_E_ARG, "workspace too small or not 16-byte aligned (see mpc_lqr_workspace_bytes)");
-            if (impl == 3 || (impl == 0 && dpp)) {
-                // ring depth (lqr_dpp16.hip): the unconstrained step always on the short ring; the constrained one there
-                // only when the batch has more waves (4 problems each) than the chip has SIMDs (256 CUs x 4)
-                const bool constrained = sp.bound_mode != MPC_BOUND_NONE || sp.zero_mask != nullptr;
-                const int force = dpp16_ring_force();
-                const bool ring2 = force ? force == 2 : (!constrained || (sp.B + 3) / 4 > device_facts().simds);
-                const int rc = ring2 ? launch_step_dpp16_ring2(sp, st) : launch_step_dpp16(sp, st);
-                return rc ? rc : resolve_asymmetric(sp, impl, workspace, needK, st);
-            }
-            // (round 6) every other float32 shape up to 12/4 -- and 12/4 itself where a block is not 16-byte aligned --: the 12/4
-            // kernel's PADDED instantiation, ahead of the one-problem-per-wavefront kernel that served them in rounds 1-5
-            if (impl == 8 || (impl == 0 && dpad)) {
-                const int rc = launch_step_dpp16_pad(sp, st);
-                return rc ? rc : resolve_asymmetric(sp, impl, workspace, needK, st);
-            }
-            if (impl == 2 || (impl == 0 && mfma)) {
-                const int rc = launch_step_mfma16(sp, st);
-                return rc ? rc : resolve_asymmetric(sp, impl, workspace, needK, st);
-            }
-            sp.Kk = nullptr;
-        } else {
-            // float64 (round 5): n_state <= 12, n_ctrl <= 4 on the one-problem-per-wavefront kernel's float64 instantiation
-            // (v_mfma_f64_16x16x4_f64); what every test and gradient check of the reference runs in (tests/test_mpc.py .double())
-            if (impl == 3 || impl == 8) return fail(MPC_E_DTYPE, "the 4-problems-per-wave kernel is fp32 only");
-            const bool mfma = mfma16_supported(sp);
-            if (impl == 2 && !mfma)
-                return fail(MPC_E_DIMS, "fused MFMA kernel needs n_state <= 12, n_ctrl <= 4, max_linesearch_iter <= 16");
-            const int64_t need = (int64_t)p->T * p->B * 64 * (int64_t)sizeof(double);
-            const bool have_ws = workspace && workspace_bytes >= need && ((uintptr_t)workspace % 16 == 0);
-            // (a caller written against ABI 7 -- out->K / out->k given, no or a small workspace -- keeps the generic
-            // kernel under impl 0; only a FORCED impl 2 insists on the fused kernel's workspace)
-            if (impl == 2 && !have_ws)
-                return fail(MPC_E_ARG, "workspace too small or not 16-byte aligned (see mpc_lqr_workspace_bytes)");
-            if (mfma && have_ws) {
-                if ((sp.K == nullptr) != (sp.k == nullptr)) return fail(MPC_E_NULL, "pass both K and k, or neither");
-                sp.Kk = (real *)workspace;
-                const int rc = launch_step_mfma16(sp, st);
-                return rc ? rc : resolve_asymmetric(sp, impl, workspace, needK, st);
-            }
-        }
-    }
-    if constexpr (sizeof(real) == 4) {
-        // Every float32 shape up to 32/8 that has no kernel of its own (13/4, 20/5, 24/8, 32/4, 8/6 ...): the 32/8 kernel's
-        // PADDED instantiation (lqr_mfma40_body.h, PADK) -- the reference's sweep is shape-agnostic (mpc/lqr_step.py:61-158), and
-        // between the hand-tuned shapes the generic kernel ran at 4 % of the roofline (missing 1)
-        if (impl == 7 && !(phase_mask == 3 && pad_route(sp, workspace, workspace_bytes)))
-            return fail(MPC_E_DIMS, "padded MFMA kernel needs fp32, n_state <= 32, n_ctrl <= 8, max_linesearch_iter <= 16, no simulator, and the "
-                                    "workspace of mpc_lqr_workspace_bytes (16-byte aligned)");
-        if (phase_mask == 3 && (impl == 7 || (impl == 0 && !mfma40_supported(sp))) && pad_route(sp, workspace, workspace_bytes)) {
-            if ((sp.K == nullptr) != (sp.k == nullptr)) return fail(MPC_E_NULL, "pass both K and k, or neither");
-            StepParams<float> q = sp;
-            const int64_t TB = (int64_t)p->T * p->B;
-            q.K_user = sp.K;
-            q.k_user = sp.k;
-            q.K = (float *)workspace;
-            q.k = q.K + TB * 256;
-            q.Kk = q.k + TB * 8;
-            const int rc = mfma40_pad16_supported(q) ? launch_step_mfma40_pad16(q, st) : launch_step_mfma40_pad4(q, st);
-            return rc ? rc : resolve_asymmetric(sp, impl, workspace, needK, st);
-        }
-    }
-    if (!sp.K || !sp.k) {
-        if (phase_mask != 3) return fail(MPC_E_NULL, "K / k is NULL");
-        if (!workspace || workspace_bytes < needK + needk)
-            return fail(MPC_E_ARG, "workspace too small (see mpc_lqr_workspace_bytes)");
-        sp.K = (real *)workspace;
-        sp.k = (real *)((char *)workspace + needK);
-    }
-    if constexpr (sizeof(real) == 4) {
-        // n_state = 32, n_ctrl = 8, unconstrained: register-resident MFMA sweep and rollout (lqr_mfma40_body.h)
-        if (impl == 5 && !(phase_mask == 3 && mfma40_supported(sp)))
-            return fail(MPC_E_DIMS, "MFMA kernel needs fp32, n_state = 32, n_ctrl = 8, 16-byte aligned blocks, no simulator");
-        if (phase_mask == 3 && (impl == 5 || impl == 0) && mfma40_supported(sp)) {
-            // (M, Quu, m) record of the constrained modes: behind K | k where the workspace has the room (rollout_priced)
-            sp.Kk = nullptr;
-            if ((sp.bound_mode != MPC_BOUND_NONE || sp.zero_mask) && workspace && ((uintptr_t)workspace % 16 == 0) &&
-                workspace_bytes >= needK + needk + (int64_t)p->T * p->B * (328 + 40) * 4)
-                sp.Kk = (real *)((char *)workspace + needK + needk);
-            const int rc = mfma40_ring(sp) == 2 ? launch_step_mfma40_ring2(sp, st) : launch_step_mfma40(sp, st);
-            return rc ? rc : resolve_asymmetric(sp, impl, workspace, needK, st);
-        }
-    } else if (impl == 5) {
-        return fail(MPC_E_DTYPE, "the MFMA sweep is fp32 only");
-    }
-    return launch_step_generic<real>(sp, phase_mask, st);
+    const int rc = launch_routed(r, sp, st);
+    if (rc || !r.needs_resolve) return rc;
+    sp.K = K_caller; sp.k = k_caller; sp.K_user = sp.k_user = nullptr;      // the re-solve writes the caller's gains, or parks its own
+    return resolve_asymmetric(sp, workspace, st);
+}
+
+// the argument checks of mpc_lqr_step, and of mpc_lqr_step_route, which answers for the same arguments
+static int check_step(const mpc_lqr_problem *p, const mpc_lqr_options *o, const mpc_lqr_outputs *out)
+{
+    const bool inline_lin = o && o->true_dynamics && o->true_dynamics->linearize;
+    int rc = check_problem(p, true, true, !inline_lin);
+    if (rc) return rc;
+    if ((rc = check_options(p, o))) return rc;
+    if (!out) return fail(MPC_E_NULL, "outputs is NULL");
+    return MPC_OK;
+}
+
+template <typename real>
+static int route_query(const mpc_lqr_problem *p, const mpc_lqr_options *o, const mpc_lqr_outputs *out, const void *workspace,
+                       int64_t workspace_bytes, int impl, int *ring)
+{
+    StepParams<real> sp = make_params<real>(p, o, out);
+    filter_qp_start(sp);
+    const StepRoute r = step_route(sp, p, impl, 3, workspace, workspace_bytes);
+    if (r.code) return fail(r.code, r.msg);
+    if (ring) *ring = r.ring;
+    return r.kernel;
 }
 }  // namespace mpclqr
 
@@ -373,88 +546,52 @@ int64_t mpc_lqr_workspace_bytes(const mpc_lqr_problem *p)
 int mpc_lqr_step(const mpc_lqr_problem *p, const mpc_lqr_options *o, const mpc_lqr_outputs *out,
                  void *workspace, int64_t workspace_bytes, int impl, void *stream)
 {
-    const bool inline_lin = o && o->true_dynamics && o->true_dynamics->linearize;
-    int rc = check_problem(p, true, true, !inline_lin);
+    const int rc = check_step(p, o, out);
     if (rc) return rc;
-    if ((rc = check_options(p, o))) return rc;
-    if (!out) return fail(MPC_E_NULL, "outputs is NULL");
     if (p->B == 0) return MPC_OK;
     hipStream_t st = (hipStream_t)stream;
     return p->dtype == MPC_F32 ? step_impl<float>(p, o, out, workspace, workspace_bytes, impl, 3, nullptr, st)
                                : step_impl<double>(p, o, out, workspace, workspace_bytes, impl, 3, nullptr, st);
 }
 
+int mpc_lqr_step_route(const mpc_lqr_problem *p, const mpc_lqr_options *o, const mpc_lqr_outputs *out, const void *workspace,
+                       int64_t workspace_bytes, int impl, int *ring)
+{
+    const int rc = check_step(p, o, out);
+    if (rc) return rc;
+    if (ring) *ring = 0;
+    if (p->B == 0) return 0;                 // (mpc_lqr_step succeeds and launches nothing)
+    return p->dtype == MPC_F32 ? route_query<float>(p, o, out, workspace, workspace_bytes, impl, ring)
+                               : route_query<double>(p, o, out, workspace, workspace_bytes, impl, ring);
+}
+
 int mpc_lqr_impl_supported(const mpc_lqr_problem *p, const mpc_lqr_options *o, int impl)
 {
     if (!p || check_problem(p, false, false) != MPC_OK || check_options(p, o) != MPC_OK) return 0;
-    if (o && o->true_dynamics && (o->true_dynamics->kind & MPC_ENV_CTRL_CARRY)) return (impl == 4 && tiny_supported(p->ns, p->nc)) ? 1 : 0;
-    if (impl == 1) return generic_lds_bytes(p->ns, p->nc, p->dtype == MPC_F64 ? 8 : 4) <= 160 * 1024;
-    if (impl == 4) return tiny_supported(p->ns, p->nc) ? 1 : 0;
-    if (impl == 6) return (p->dtype == MPC_F32 && tiny_supported(p->ns, p->nc) && wave1_supported(make_params<float>(p, o, nullptr))) ? 1 : 0;
-    if (impl == 5) {
-        if (p->dtype != MPC_F32) return 0;
-        mpc_lqr_outputs out;
-        memset(&out, 0, sizeof(out));
-        StepParams<float> sp = make_params<float>(p, o, &out);
-        return (sp.ns == 32 && sp.nc == 8 && !sp.env.kind) ? 1 : 0;
-    }
-    if (impl == 7) {
-        if (p->dtype != MPC_F32) return 0;
-        mpc_lqr_outputs out;
-        memset(&out, 0, sizeof(out));
-        return mfma40_pad_supported(make_params<float>(p, o, &out)) ? 1 : 0;
-    }
-    if (impl == 8) {
-        if (p->dtype != MPC_F32) return 0;
-        mpc_lqr_outputs out;
-        memset(&out, 0, sizeof(out));
-        return dpp16_pad_supported(make_params<float>(p, o, &out)) ? 1 : 0;
-    }
-    if (impl == 2 && p->dtype == MPC_F64) {
-        mpc_lqr_outputs out;
-        memset(&out, 0, sizeof(out));
-        return mfma16_supported(make_params<double>(p, o, &out)) ? 1 : 0;
-    }
-    if (impl == 2 || impl == 3) {
-        if (p->dtype != MPC_F32) return 0;
-        mpc_lqr_outputs out;
-        memset(&out, 0, sizeof(out));
-        StepParams<float> sp = make_params<float>(p, o, &out);
-        if (impl == 2) return mfma16_supported(sp) ? 1 : 0;
-        // sizes only: the alignment of the actual tensors is checked at launch
-        return (sp.ns == 12 && sp.nc == 4) ? 1 : 0;
-    }
-    return 0;
+    if (impl < MPC_IMPL_GENERIC || impl > MPC_IMPL_DPP16_PAD) return 0;
+    // (MPC_ENV_CTRL_CARRY: the lane-per-problem kernel alone, see step_route)
+    if (o && o->true_dynamics && (o->true_dynamics->kind & MPC_ENV_CTRL_CARRY) && impl != MPC_IMPL_TINY) return 0;
+    // sizes, dtype and options only: the alignment of the actual tensors is checked at launch
+    return p->dtype == MPC_F32 ? kernel_takes<float>(impl, make_params<float>(p, o, nullptr), true)
+                               : kernel_takes<double>(impl, make_params<double>(p, o, nullptr), true);
 }
 
 int mpc_lqr_qp_record(const mpc_lqr_problem *p, const mpc_lqr_options *o, int impl, int64_t *offset_bytes, int64_t *st, int64_t *sb)
 {
-    // mirrors the routing of step_impl for a box-constrained float32 step whose out->K / out->k are NULL
+    // the route of a box-constrained float32 step whose out->K / out->k are NULL, on a workspace of mpc_lqr_workspace_bytes
     if (!p || !o || !offset_bytes || !st || !sb) return 0;
     if (check_problem(p, false, false) != MPC_OK || check_options(p, o) != MPC_OK) return 0;
     if (p->dtype != MPC_F32 || o->bound_mode == MPC_BOUND_NONE || o->true_dynamics || p->B == 0) return 0;
     mpc_lqr_outputs out;
     memset(&out, 0, sizeof(out));
-    const StepParams<float> sp = make_params<float>(p, o, &out);
-    const int64_t TB = (int64_t)p->T * p->B;
-    if ((impl == 0 || impl == 3) && p->ns == 12 && p->nc == 4 && dpp16_supported(sp)) {
-        // the 12/4 kernel's gain record Kk[t][b][lane 0..15][4]: lane 12 holds k.  (only where that kernel really takes
-        // the call -- blocks or strides that are not 16-byte aligned go to the one-problem-per-wavefront kernel under impl 0, whose
-        // record keeps k elsewhere: "0 = not filled" below; a forced impl 3 fails at launch with MPC_E_DIMS)
-        *offset_bytes = 48 * 4; *st = (int64_t)p->B * 64; *sb = 64;
-        return 1;
-    }
-    if (impl == 3) return 0;
-    if (impl == 0 && (tiny_supported(p->ns, p->nc) || mfma16_supported(sp))) return 0;
-    if ((impl == 0 || impl == 5) && p->ns == 32 && p->nc == 8) {
-        *offset_bytes = TB * 256 * 4; *st = (int64_t)p->B * 8; *sb = 8;       // K [T,B,8,32] | k [T,B,8]
-        return 1;
-    }
-    if ((impl == 0 || impl == 7) && mfma40_pad_supported(sp)) {
-        *offset_bytes = TB * 256 * 4; *st = (int64_t)p->B * 8; *sb = 8;       // the padded gains: K [T,B,8,32] | k [T,B,8] (entries >= n_ctrl zero)
-        return 1;
-    }
-    return 0;
+    out.new_x = out.new_u = (void *)16;          // (a step has them; the route looks at pointers for NULL and alignment only)
+    // (a forced impl 5 has always been answered from the sizes alone: off the 16-byte grid the step itself is refused at launch)
+    const mpc_lqr_problem q = impl == MPC_IMPL_MFMA40 ? sizes_only(p->B, p->T, p->ns, p->nc, p->dtype) : *p;
+    const StepParams<float> sp = make_params<float>(&q, o, &out);
+    const StepRoute r = step_route(sp, p, impl, 3, (const void *)16, mpc_lqr_workspace_bytes(p));
+    if (r.code || r.qp_off < 0) return 0;        // 0 = not filled (only where the kernel that keeps the record really takes the call)
+    *offset_bytes = r.qp_off; *st = r.qp_st; *sb = r.qp_sb;
+    return 1;
 }
 
 int mpc_lqr_sweep(const mpc_lqr_problem *p, const mpc_lqr_options *o, const mpc_lqr_outputs *out, void *stream)
@@ -586,39 +723,30 @@ int mpc_lqr_kkt_fused(const mpc_lqr_problem *p, const mpc_lqr_options *o, const 
     memset(&out, 0, sizeof(out));
     out.status = status;
     StepParams<float> sp = make_params<float>(p, o, &out);
+    const float *gx = (const float *)dl_dx, *gu = (const float *)dl_du, *ws = (const float *)workspace;
+    int (*launch)(const StepParams<float> &, const float *, const float *, float *, float *, float *, float *, float *, float *, float *,
+                  float *, float, int, hipStream_t);
     if (p->ns > 12 || p->nc > 4) {
         // config 5's shape: the nested step with the costates riding along, then the outer-product kernel (two launches)
-        if (!kkt_fused_mfma40_supported(sp, (const float *)dl_dx, (const float *)dl_du, (const float *)dC, (const float *)dF,
-                                        (const float *)workspace) ||
+        launch = launch_kkt_fused_mfma40;
+        if (!kkt_fused_mfma40_supported(sp, gx, gu, (const float *)dC, (const float *)dF, ws) ||
             (dx_out && (((uintptr_t)dx_out | (uintptr_t)du_out) & 15)) || ((uintptr_t)dx_init & 15) || (df && ((uintptr_t)df & 15))) {
             // every other shape up to 32/8, and 32/8 itself off the 16-byte grid: the padded instantiation (round 6)
-            if (!kkt_fused_mfma40_pad_supported(sp, (const float *)workspace))
+            if (!kkt_fused_mfma40_pad_supported(sp, ws))
                 return fail(MPC_E_DIMS, "mpc_lqr_kkt_fused: the workspace must be 16-byte aligned (tensor bounds 4-byte aligned)");
-            if (kkt_fused_mfma40_pad16_supported(sp, (const float *)workspace))
-                return launch_kkt_fused_mfma40_pad16(sp, (const float *)dl_dx, (const float *)dl_du, (float *)dC, (float *)dc, (float *)dF,
-                                                     (float *)df, (float *)dx_init, (float *)dx_out, (float *)du_out, (float *)workspace, 0.2f,
-                                                     10, (hipStream_t)stream);
-            return launch_kkt_fused_mfma40_pad(sp, (const float *)dl_dx, (const float *)dl_du, (float *)dC, (float *)dc, (float *)dF,
-                                               (float *)df, (float *)dx_init, (float *)dx_out, (float *)du_out, (float *)workspace, 0.2f,
-                                               10, (hipStream_t)stream);
+            launch = kkt_fused_mfma40_pad16_supported(sp, ws) ? launch_kkt_fused_mfma40_pad16 : launch_kkt_fused_mfma40_pad;
         }
-        return launch_kkt_fused_mfma40(sp, (const float *)dl_dx, (const float *)dl_du, (float *)dC, (float *)dc, (float *)dF,
-                                       (float *)df, (float *)dx_init, (float *)dx_out, (float *)du_out, (float *)workspace, 0.2f,
-                                       10, (hipStream_t)stream);
-    }
-    if (!kkt_fused_dpp16_supported(sp, (const float *)dl_dx, (const float *)dl_du, (const float *)dC, (const float *)dF,
-                                   (const float *)workspace)) {
-        // every other shape up to 12/4, and 12/4 itself where a block is not 16-byte aligned: the padded instantiation (round 6)
-        if (!kkt_fused_dpp16_pad_supported(sp, (const float *)workspace))
-            return fail(MPC_E_DIMS, "mpc_lqr_kkt_fused: the workspace must be 16-byte aligned");
-        return launch_kkt_fused_dpp16_pad(sp, (const float *)dl_dx, (const float *)dl_du, (float *)dC, (float *)dc, (float *)dF,
-                                          (float *)df, (float *)dx_init, (float *)dx_out, (float *)du_out, (float *)workspace, 0.2f, 10,
-                                          (hipStream_t)stream);
+    } else {
+        launch = launch_kkt_fused_dpp16;
+        if (!kkt_fused_dpp16_supported(sp, gx, gu, (const float *)dC, (const float *)dF, ws)) {
+            // every other shape up to 12/4, and 12/4 itself where a block is not 16-byte aligned: the padded instantiation (round 6)
+            if (!kkt_fused_dpp16_pad_supported(sp, ws)) return fail(MPC_E_DIMS, "mpc_lqr_kkt_fused: the workspace must be 16-byte aligned");
+            launch = launch_kkt_fused_dpp16_pad;
+        }
     }
     // the nested solve is a plain LQRStep(...) in the reference (:328-338): linesearch_decay 0.2, max_linesearch_iter 10
-    return launch_kkt_fused_dpp16(sp, (const float *)dl_dx, (const float *)dl_du, (float *)dC, (float *)dc, (float *)dF,
-                                  (float *)df, (float *)dx_init, (float *)dx_out, (float *)du_out, (float *)workspace, 0.2f, 10,
-                                  (hipStream_t)stream);
+    return launch(sp, gx, gu, (float *)dC, (float *)dc, (float *)dF, (float *)df, (float *)dx_init, (float *)dx_out, (float *)du_out,
+                  (float *)workspace, 0.2f, 10, (hipStream_t)stream);
 }
 
 int mpc_env_traj_cost(const mpc_lqr_problem *p, const mpc_env_dynamics *env, void *x, void *cost, void *stream)

@@ -15,6 +15,28 @@ namespace mpclqr {
 
 void set_last_error(const char *msg);
 
+// the kernels behind mpc_lqr_step: the values of its `impl` argument (include/mpc_lqr.h)
+enum { MPC_IMPL_AUTO = 0, MPC_IMPL_GENERIC = 1, MPC_IMPL_MFMA16 = 2, MPC_IMPL_DPP16 = 3, MPC_IMPL_TINY = 4, MPC_IMPL_MFMA40 = 5,
+       MPC_IMPL_WAVE1 = 6, MPC_IMPL_MFMA40_PAD = 7, MPC_IMPL_DPP16_PAD = 8 };
+
+// Which kernel takes one step call and where its pieces live in the workspace (capi.hip: step_route decides, step_impl executes,
+// the queries mpc_lqr_step_route / mpc_lqr_qp_record read it off).  Host only.
+struct StepRoute {
+    int code; const char *msg;     // code != 0: refused, with mpc_lqr_step's code and text (a string literal)
+    int kernel;                    // MPC_IMPL_* 1..8: the kernel that takes the call
+    int phase;                     // the generic kernels: 3 = sweep + rollout, 1 = sweep, 2 = rollout
+    int ring;                      // 0, or the sweep ring of the 12/4 / 32/8 kernel (2 / 4, 2 / 3)
+    bool pad16;                    // padded 32/8: 16-byte gathers
+    bool needs_resolve;            // the generic re-solve of the problems flagged MPC_ST_C_ASYMMETRIC follows the launch
+    // where things live in the workspace (byte offsets, -1 = not there)
+    int64_t K_off, k_off;          // gains the kernel parks there (the caller's out->K / out->k otherwise)
+    int64_t Kk_off, status_off;    // the kernel's own record; the status words of a caller that passes none
+    int64_t qp_off, qp_st, qp_sb;  // the k_t record a later step may start from (mpc_lqr_qp_record; qp_off < 0: none), element strides
+};
+template <typename real>
+StepRoute step_route(const StepParams<real> &sp, const mpc_lqr_problem *p, int impl, int phase_mask, const void *workspace,
+                     int64_t workspace_bytes);
+
 // generic path (lqr_generic.hip)
 template <typename real> int launch_step_generic(const StepParams<real> &p, int phase_mask, hipStream_t st);
 template <typename real> int launch_pnqp(int B, int n, const real *H, const real *q, const real *lo,

@@ -210,7 +210,7 @@ class Outputs(ctypes.Structure):
 
 
 EXPORTS = ("mpc_lqr_abi_version", "mpc_lqr_build_info", "mpc_lqr_last_error", "mpc_lqr_workspace_bytes",
-           "mpc_lqr_step", "mpc_lqr_impl_supported", "mpc_lqr_qp_record", "mpc_lqr_sweep", "mpc_lqr_rollout", "mpc_lqr_kkt_grads", "mpc_lqr_kkt_prepare",
+           "mpc_lqr_step", "mpc_lqr_step_route", "mpc_lqr_impl_supported", "mpc_lqr_qp_record", "mpc_lqr_sweep", "mpc_lqr_rollout", "mpc_lqr_kkt_grads", "mpc_lqr_kkt_prepare",
            "mpc_pnqp", "mpc_pnqp_lu", "mpc_traj_cost", "mpc_env_traj_cost", "mpc_env_linearize", "mpc_select_best",
            "mpc_env_param_grad_workspace_bytes", "mpc_env_param_grad",
            "mpc_mlp_workspace_bytes", "mpc_mlp_rollout", "mpc_mlp_linearize", "mpc_mlp_linearize_carry",
@@ -249,6 +249,7 @@ def load():
     L.mpc_lqr_workspace_bytes.argtypes = [ctypes.POINTER(Problem)]
     PP, OP, UP = ctypes.POINTER(Problem), ctypes.POINTER(Options), ctypes.POINTER(Outputs)
     L.mpc_lqr_step.argtypes = [PP, OP, UP, _vp, _i64, ctypes.c_int, _vp]
+    L.mpc_lqr_step_route.argtypes = [PP, OP, UP, _vp, _i64, ctypes.c_int, ctypes.POINTER(ctypes.c_int)]
     L.mpc_lqr_impl_supported.argtypes = [PP, OP, ctypes.c_int]
     L.mpc_lqr_qp_record.argtypes = [PP, OP, ctypes.c_int] + [ctypes.POINTER(_i64)] * 3
     L.mpc_lqr_sweep.argtypes = [PP, OP, UP, _vp]
@@ -453,6 +454,18 @@ class HipBackend:
             if t is not None and t.numel() > 0 and (t.dtype != C.dtype or t.device != C.device):
                 raise TypeError("all tensors of one LQR problem must share dtype and device")
 
+    def _open(self, x_init, C, c, F, f, cur_x, cur_u, opts, *more):
+        """The opening of every step-shaped call: device and dtype checks (`more`: further tensors of the call), sizes, the
+        problem and options structs with what they keep alive, and the keywords of a fresh output tensor.
+        -> (library, device, (T, B, ns, nc), Problem, Options, kw, keep, keep_o)"""
+        dev = _require_device(x_init, C, c, F, cur_x, cur_u, *more)
+        self._check_same(C, x_init, c, F, f, cur_x, cur_u, *more)
+        T, B, ns = C.shape[0], C.shape[1], x_init.shape[1]
+        nc = C.shape[2] - ns
+        p, keep = self._problem(x_init, C, c, F, f, cur_x, cur_u)
+        o, keep_o = opts.to_struct(T, B, nc, C)
+        return load(), dev, (T, B, ns, nc), p, o, dict(device=dev, dtype=C.dtype), keep, keep_o
+
     def impl_supported(self, ns, nc, dtype, impl, opts=None):
         p = Problem()
         p.B, p.T, p.ns, p.nc = 1, 1, ns, nc
@@ -472,15 +485,7 @@ class HipBackend:
 
         rollout_problem: optional (C, c, F, f) the rollout/true cost should use when they differ
         from the sweep's (mpc/lqr_step.py:218-232 reads true_dynamics / true_cost)."""
-        dev = _require_device(x_init, C, c, F, cur_x, cur_u)
-        self._check_same(C, x_init, c, F, f, cur_x, cur_u)
-        L = load()
-        T, B, n = C.shape[0], C.shape[1], C.shape[2]
-        ns = x_init.shape[1]
-        nc = n - ns
-        p, keep = self._problem(x_init, C, c, F, f, cur_x, cur_u)
-        o, keep_o = opts.to_struct(T, B, nc, C)
-        kw = dict(device=dev, dtype=C.dtype)
+        L, dev, (T, B, ns, nc), p, o, kw, keep, keep_o = self._open(x_init, C, c, F, f, cur_x, cur_u, opts)
         if out_x is not None:
             assert out_x.is_contiguous() and out_u.is_contiguous() and tuple(out_x.shape) == (T, B, ns) and tuple(out_u.shape) == (T, B, nc)
             assert out_x.dtype == C.dtype and out_x.device == C.device and out_u.dtype == C.dtype and out_u.device == C.device
@@ -521,15 +526,7 @@ class HipBackend:
         then a single C call (no allocation, hipGraph-capturable).  Outputs are overwritten by
         every call -- clone what must survive.  out_x / out_u: write the new trajectory into these
         (contiguous) tensors, e.g. the nominal buffers of the NEXT iteration's plan."""
-        dev = _require_device(x_init, C, c, F, cur_x, cur_u)
-        self._check_same(C, x_init, c, F, f, cur_x, cur_u)
-        L = load()
-        T, B, n = C.shape[0], C.shape[1], C.shape[2]
-        ns = x_init.shape[1]
-        nc = n - ns
-        p, keep = self._problem(x_init, C, c, F, f, cur_x, cur_u)
-        o, keep_o = opts.to_struct(T, B, nc, C)
-        kw = dict(device=dev, dtype=C.dtype)
+        L, dev, (T, B, ns, nc), p, o, kw, keep, keep_o = self._open(x_init, C, c, F, f, cur_x, cur_u, opts)
         res = dict(new_x=torch.empty(T, B, ns, **kw) if out_x is None else out_x,
                    new_u=torch.empty(T, B, nc, **kw) if out_u is None else out_u)
         res.update(self._per_problem_outputs(B, dev, C.dtype))
@@ -579,6 +576,19 @@ class HipBackend:
         flat = ws[off.value:].view(torch.float32)
         return flat.as_strided((p.T, p.B, p.nc), (st.value, sb.value, 1))
 
+    @staticmethod
+    def step_route(plan):
+        """(kernel, ring) of the step `plan` runs: the IMPL_* code of the kernel mpc_lqr_step picks for exactly the plan's
+        arguments, and the depth of its sweep ring where it has two (mpc_lqr_step_route; nothing is launched)."""
+        p, o, out, _keep, ws = plan._keep
+        nbytes, impl, _dev = plan._bind
+        ring = ctypes.c_int(0)
+        kernel = int(load().mpc_lqr_step_route(ctypes.byref(p), ctypes.byref(o), ctypes.byref(out), ws.data_ptr(), nbytes, int(impl),
+                                               ctypes.byref(ring)))
+        if kernel < 0:
+            _check(kernel, "mpc_lqr_step_route")
+        return kernel, ring.value
+
     def plan_variant(self, plan, opts=None, cur_x=None, cur_u=None, out_x=None, out_u=None):
         """A second plan over the SAME problem tensors as `plan`, differing in the nominal it reads (`cur_x`, `cur_u`), the
         buffers it writes (`out_x`, `out_u`) and / or its options: the structs are copied and patched, nothing is walked or
@@ -609,15 +619,7 @@ class HipBackend:
 
     def lqr_sweep(self, x_init, C, c, F, cur_x, cur_u, opts):
         """c_back + lqr_backward only -> dict(K, k, old_costs, qp_iters, status)."""
-        dev = _require_device(x_init, C, c, F, cur_x, cur_u)
-        self._check_same(C, x_init, c, F, cur_x, cur_u)
-        L = load()
-        T, B, n = C.shape[0], C.shape[1], C.shape[2]
-        ns = x_init.shape[1]
-        nc = n - ns
-        p, keep = self._problem(x_init, C, c, F, None, cur_x, cur_u)
-        o, keep_o = opts.to_struct(T, B, nc, C)
-        kw = dict(device=dev, dtype=C.dtype)
+        L, dev, (T, B, ns, nc), p, o, kw, keep, keep_o = self._open(x_init, C, c, F, None, cur_x, cur_u, opts)
         res = dict(K=torch.empty(T, B, nc, ns, **kw), k=torch.empty(T, B, nc, **kw),
                    old_costs=torch.empty(B, **kw), qp_iters=torch.zeros(B, device=dev, dtype=torch.int32),
                    status=torch.zeros(B, device=dev, dtype=torch.int32))
@@ -635,15 +637,7 @@ class HipBackend:
     def lqr_rollout(self, x_init, C, c, F, f, cur_x, cur_u, K, k, opts, old_costs=None):
         """lqr_forward alone (mpc/lqr_step.py:164-261) given the gains K [T,B,nc,ns], k [T,B,nc] of a sweep: mpc_lqr_rollout.
         Returns dict(new_x, new_u, costs, full_du_norm, alpha_du_norm, alphas)."""
-        dev = _require_device(x_init, C, c, F, cur_x, cur_u, K, k)
-        self._check_same(C, x_init, c, F, f, cur_x, cur_u, K, k)
-        L = load()
-        T, B, n = C.shape[0], C.shape[1], C.shape[2]
-        ns = x_init.shape[1]
-        nc = n - ns
-        p, keep = self._problem(x_init, C, c, F, f, cur_x, cur_u)
-        o, keep_o = opts.to_struct(T, B, nc, C)
-        kw = dict(device=dev, dtype=C.dtype)
+        L, dev, (T, B, ns, nc), p, o, kw, keep, keep_o = self._open(x_init, C, c, F, f, cur_x, cur_u, opts, K, k)
         res = dict(new_x=torch.empty(T, B, ns, **kw), new_u=torch.empty(T, B, nc, **kw), costs=torch.empty(B, **kw),
                    full_du_norm=torch.empty(B, **kw), alpha_du_norm=torch.empty(B, **kw), alphas=torch.empty(B, **kw),
                    status=torch.zeros(B, device=dev, dtype=torch.int32))
@@ -681,6 +675,29 @@ class HipBackend:
             z = cache[key] = (torch.zeros(T, B, ns, **kw), torch.zeros(T, B, nc, **kw), torch.zeros(B, ns, **kw))
         return z
 
+    def _nested_kkt_solve(self, C, F, dl_dx, dl_du, u_star, opts, impl):
+        """The KKT solve of the backward (mpc/lqr_step.py:322-340): mpc_lqr_kkt_prepare builds -r and the mask of the controls
+        pinned at a bound from the (contiguous) dl_dx, dl_du, u*; then one LQR step on (C, -r, F, f=None) from the zero nominal
+        with those controls pinned, defaults linesearch_decay=0.2, max_linesearch_iter=10.  -> (sol, negr, mask, keep): the
+        step's dict, the two prepared tensors and what the options keep alive."""
+        dev = C.device
+        T, B, n = C.shape[0], C.shape[1], C.shape[2]
+        nc = u_star.shape[2]
+        ns = n - nc
+        kw = dict(device=dev, dtype=C.dtype)
+        o, keep = opts.to_struct(T, B, nc, C)
+        negr = torch.empty(T, B, n, **kw)
+        mask = None
+        if o.bound_mode != BOUND_NONE:
+            mask = torch.empty(T, B, nc, device=dev, dtype=torch.uint8)
+        _check(load().mpc_lqr_kkt_prepare(_dtype_code(C), B, T, ns, nc, dl_dx.data_ptr(), dl_du.data_ptr(), u_star.data_ptr(),
+                                          ctypes.byref(o), negr.data_ptr(), _ptr(mask), _stream(dev)), "mpc_lqr_kkt_prepare")
+        zx, zu, z0 = self._zero_nominal(T, B, ns, nc, kw)
+        # (the zero nominal obeys x+ = F tau with f = None: the step may skip verifying it)
+        inner = StepOptions(u_zero_I=mask, nominal_on_dynamics=True, c_symmetric=opts.c_symmetric)
+        sol = self.lqr_step(z0, C, negr, F, None, zx, zu, inner, impl=impl)
+        return sol, negr, mask, keep
+
     def kkt_backward(self, C, c, F, f, x_star, u_star, dl_dx, dl_du, opts, impl=IMPL_AUTO):
         """dx_init, dC, dc, dF, df of mpc/lqr_step.py:312-407 (reference), all on device."""
         dev = _require_device(C, c, F, x_star, u_star, dl_dx, dl_du)
@@ -689,13 +706,11 @@ class HipBackend:
         ns = x_star.shape[2]
         nc = n - ns
         kw = dict(device=dev, dtype=C.dtype)
-        code = _dtype_code(C)
         st = _stream(dev)
         dl_dx = dl_dx.detach().to(**kw).contiguous()
         dl_du = dl_du.detach().to(**kw).contiguous()
         x_star = x_star.detach().contiguous()
         u_star = u_star.detach().contiguous()
-        o, keep_o = opts.to_struct(T, B, nc, C)
         has_f = f is not None and f.numel() > 0
         if impl == IMPL_AUTO:
             # the whole backward in one launch where a kernel for it exists (12/4 or 32/8, fp32, C vouched symmetric)
@@ -704,19 +719,8 @@ class HipBackend:
                 g = plan()
                 if g is not None:
                     return g
-        negr = torch.empty(T, B, n, **kw)
-        mask = None
-        if o.bound_mode != BOUND_NONE:
-            mask = torch.empty(T, B, nc, device=dev, dtype=torch.uint8)
-        _check(L.mpc_lqr_kkt_prepare(code, B, T, ns, nc, dl_dx.data_ptr(), dl_du.data_ptr(), u_star.data_ptr(),
-                                     ctypes.byref(o), negr.data_ptr(), _ptr(mask), st), "mpc_lqr_kkt_prepare")
-        # nested solve of :328-340: one LQR step on (C, -r, F, f=None) from the zero nominal with
-        # the active controls pinned; defaults linesearch_decay=0.2, max_linesearch_iter=10.
-        zx, zu, z0 = self._zero_nominal(T, B, ns, nc, kw)
-        # (the zero nominal obeys x+ = F tau with f = None: the step may skip verifying it)
-        inner = StepOptions(u_zero_I=mask, nominal_on_dynamics=True, c_symmetric=opts.c_symmetric)
-        sol = self.lqr_step(z0, C, negr, F, None, zx, zu, inner, impl=impl)
-        p, keep = self._problem(z0, C, c, F, f, x_star, u_star)
+        sol, negr, mask, keep_o = self._nested_kkt_solve(C, F, dl_dx, dl_du, u_star, opts, impl)
+        p, keep = self._problem(self._zero_nominal(T, B, ns, nc, kw)[2], C, c, F, f, x_star, u_star)
         dC = torch.empty(T, B, n, n, **kw)
         dc = torch.empty(T, B, n, **kw)
         dF = torch.empty(F.shape, **kw)          # every kernel writes all of it (t < T-1 is all there is)
@@ -755,21 +759,11 @@ class HipBackend:
                 out[name] = g[src].sum(1) if (w and g[src] is not None) else None
             return out
         kw = dict(device=dev, dtype=C.dtype)
-        code = _dtype_code(C)
         st = _stream(dev)
         dl_dx = dl_dx.detach().to(**kw).contiguous()
         dl_du = dl_du.detach().to(**kw).contiguous()
-        o, keep_o = opts.to_struct(T, B, nc, C)
-        negr = torch.empty(T, B, n, **kw)
-        mask = None
-        if o.bound_mode != BOUND_NONE:
-            mask = torch.empty(T, B, nc, device=dev, dtype=torch.uint8)
-        _check(L.mpc_lqr_kkt_prepare(code, B, T, ns, nc, dl_dx.data_ptr(), dl_du.data_ptr(), u_star.data_ptr(),
-                                     ctypes.byref(o), negr.data_ptr(), _ptr(mask), st), "mpc_lqr_kkt_prepare")
-        zx, zu, z0 = self._zero_nominal(T, B, ns, nc, kw)
-        inner = StepOptions(u_zero_I=mask, nominal_on_dynamics=True, c_symmetric=opts.c_symmetric)
-        sol = self.lqr_step(z0, C, negr, F, None, zx, zu, inner)
-        p, keep = self._problem(z0, C, c, F, f, x_star, u_star)
+        sol, negr, mask, keep_o = self._nested_kkt_solve(C, F, dl_dx, dl_du, u_star, opts, IMPL_AUTO)
+        p, keep = self._problem(self._zero_nominal(T, B, ns, nc, kw)[2], C, c, F, f, x_star, u_star)
         shapes = ((T, n, n), (T, n), (T - 1, ns, n), (T - 1, ns))
         sums = [torch.empty(shape, **kw) if w else None for shape, w in zip(shapes, want)]
         dx_init = torch.empty(B, ns, **kw)
