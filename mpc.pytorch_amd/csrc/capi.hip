@@ -157,6 +157,7 @@ static bool kernel_takes(int kernel, const StepParams<real> &sp, bool query = fa
         case MPC_IMPL_DPP16_PAD: return dpp16_pad_supported(sp);
         case MPC_IMPL_MFMA40: return mfma40_supported(query ? sizes_only(sp) : sp);
         case MPC_IMPL_MFMA40_PAD: return mfma40_pad_supported(sp);
+        case MPC_IMPL_MFMA40_NARROW: return mfma40_narrow_supported(sp);
         case MPC_IMPL_WAVE1: return tiny_supported(sp.ns, sp.nc) && wave1_supported(sp);
         }
     }
@@ -167,7 +168,8 @@ static bool kernel_takes(int kernel, const StepParams<real> &sp, bool query = fa
 // for any other kernel takes the generic sweep
 static bool stops_after_sweep(int kernel)
 {
-    return kernel == MPC_IMPL_DPP16 || kernel == MPC_IMPL_DPP16_PAD || kernel == MPC_IMPL_MFMA40 || kernel == MPC_IMPL_MFMA40_PAD;
+    return kernel == MPC_IMPL_DPP16 || kernel == MPC_IMPL_DPP16_PAD || kernel == MPC_IMPL_MFMA40 || kernel == MPC_IMPL_MFMA40_PAD ||
+           kernel == MPC_IMPL_MFMA40_NARROW;
 }
 
 // What a kernel keeps in the workspace, in bytes from its start (-1: not there): the gains K | k where the caller passes none, its own
@@ -202,6 +204,9 @@ static WsLayout ws_layout(int kernel, int T, int B, int ns, int nc)
         w.Kk = needK + needk; w.bytes = w.Kk + TB * (328 + 40) * 4;
         w.qp = w.k; w.qp_st = (int64_t)B * nc; w.qp_sb = nc;
         break;
+    case MPC_IMPL_MFMA40_NARROW:
+        // (the narrow instantiation lives inside the padded kernel's layout: its gains K [T,B,8,16] in the front half of the K region, k
+        // where the padded kernel keeps it -- the record a later step starts from is the same --, (M, Quu, m) [T,B,200] | [T,B,24] in Kk)
     case MPC_IMPL_MFMA40_PAD:
         // the kernel's own padded gains K [T,B,8,32] | k [T,B,8] (entries >= n_ctrl zero) | (M, Quu, m) [T,B,328] | second trial [T,B,40]
         w.K = 0; w.k = TB * 256 * 4; w.Kk = w.k + TB * 8 * 4; w.bytes = w.Kk + TB * (328 + 40) * 4;
@@ -275,12 +280,13 @@ StepRoute step_route(const StepParams<real> &sp, const mpc_lqr_problem *p, int i
         if (!kernel_takes<real>(kernel, sp)) return false;
         if (kernel == MPC_IMPL_GENERIC || kernel == MPC_IMPL_TINY || kernel == MPC_IMPL_WAVE1) return true;
         if (sp.env.kind) return false;
-        if (kernel == MPC_IMPL_MFMA40_PAD || (!f32 && kernel == MPC_IMPL_MFMA16)) return room(layout(kernel).bytes) && aligned;
+        if (kernel == MPC_IMPL_MFMA40_PAD || kernel == MPC_IMPL_MFMA40_NARROW || (!f32 && kernel == MPC_IMPL_MFMA16))
+            return room(layout(kernel).bytes) && aligned;
         return true;
     };
-    signed char asked[MPC_IMPL_DPP16_PAD + 1] = {-1, -1, -1, -1, -1, -1, -1, -1, -1};      // each kernel is asked once per call
+    signed char asked[MPC_IMPL_MFMA40_NARROW + 1] = {-1, -1, -1, -1, -1, -1, -1, -1, -1, -1};      // each kernel is asked once per call
     const auto takes = [&](int kernel) {
-        if (kernel < MPC_IMPL_GENERIC || kernel > MPC_IMPL_DPP16_PAD) return false;
+        if (kernel < MPC_IMPL_GENERIC || kernel > MPC_IMPL_MFMA40_NARROW) return false;
         if (asked[kernel] < 0) asked[kernel] = takes_now(kernel);
         return asked[kernel] != 0;
     };
@@ -334,6 +340,7 @@ StepRoute step_route(const StepParams<real> &sp, const mpc_lqr_problem *p, int i
         return refuse(MPC_E_ARG, "in-kernel linearisation needs the lane-per-problem kernel (n_ctrl = 1, n_state <= 6)");
     if (sp.env.kind && (impl == 2 || impl == 3 || impl == 8))
         return refuse(MPC_E_ARG, "a simulator as true_dynamics runs on the generic kernels only");
+    if (impl == MPC_IMPL_MFMA40_NARROW && !f32) return refuse(MPC_E_DTYPE, "the narrow MFMA kernel is fp32 only");
     if ((impl == 4 || impl == 6) && (!step || !tiny))
         return refuse(MPC_E_DIMS, "lane-per-problem / wavefront-per-problem kernel needs n_ctrl = 1, n_state <= 6");
     if (impl == 6 && !takes(MPC_IMPL_WAVE1))
@@ -383,7 +390,11 @@ StepRoute step_route(const StepParams<real> &sp, const mpc_lqr_problem *p, int i
         if (impl == 7 && !(step && takes(impl)))
             return refuse(MPC_E_DIMS, "padded MFMA kernel needs fp32, n_state <= 32, n_ctrl <= 8, max_linesearch_iter <= 16, no simulator, and the "
                                       "workspace of mpc_lqr_workspace_bytes (16-byte aligned)");
-        if (step && kernel == MPC_IMPL_MFMA40_PAD) {
+        // (impl 9, the padded kernel's narrow instantiation: forced only -- the loop above never proposes it)
+        if (impl == MPC_IMPL_MFMA40_NARROW && !(step && takes(impl)))
+            return refuse(MPC_E_DIMS, "narrow MFMA kernel needs fp32, n_state <= 16, n_ctrl <= 8, max_linesearch_iter <= 16, no simulator, and the "
+                                      "workspace of mpc_lqr_workspace_bytes (16-byte aligned)");
+        if (step && (kernel == MPC_IMPL_MFMA40_PAD || kernel == MPC_IMPL_MFMA40_NARROW)) {
             const WsLayout w = layout(kernel);
             r.K_off = w.K; r.k_off = w.k;
             r.pad16 = mfma40_pad16_supported(sp);
@@ -451,6 +462,7 @@ static int launch_routed(const StepRoute &r, const StepParams<float> &q, hipStre
     case MPC_IMPL_WAVE1: return launch_step_wave1(q, st);
     case MPC_IMPL_MFMA40_PAD: return r.pad16 ? launch_step_mfma40_pad16(q, st) : launch_step_mfma40_pad4(q, st);
     case MPC_IMPL_DPP16_PAD: return launch_step_dpp16_pad(q, st);
+    case MPC_IMPL_MFMA40_NARROW: return r.pad16 ? launch_step_mfma40_narrow16(q, st) : launch_step_mfma40_narrow4(q, st);
     }
     return MPC_E_ARG;
 }
@@ -488,7 +500,7 @@ static int step_impl(const mpc_lqr_problem *p, const mpc_lqr_options *o, const m
     real *const K_caller = sp.K, *const k_caller = sp.k;
     sp.Kk = (real *)at(r.Kk_off);
     if (r.K_off >= 0) {                          // gains where the route put them
-        if (r.kernel == MPC_IMPL_MFMA40_PAD) { sp.K_user = sp.K; sp.k_user = sp.k; }
+        if (r.kernel == MPC_IMPL_MFMA40_PAD || r.kernel == MPC_IMPL_MFMA40_NARROW) { sp.K_user = sp.K; sp.k_user = sp.k; }
         sp.K = (real *)at(r.K_off);
         sp.k = (real *)at(r.k_off);
     }
@@ -531,7 +543,7 @@ int mpc_lqr_abi_version(void) { return MPC_LQR_ABI_VERSION; }
 const char *mpc_lqr_build_info(void)
 {
     return "libmpc_lqr_hip gfx950 (CDNA4) | kernels: lqr_step_generic<f32,f64>, lqr_step_mfma16<f32,f64>, lqr_step_dpp16<f32>, lqr_step_dpp16_padded<f32>, "
-           "lqr_step_tiny<f32,f64>, lqr_step_wave1<f32>, lqr_step_mfma40<f32>, lqr_step_mfma40_padded<f32>, nn_rollout<f32>, nn_linearize<f32>, nn_param_grad<f32>, env_linearize, env_param_grad<f32,f64>, kkt_grads, kkt_grads_shared<f32>, kkt_fused<f32>, kkt_fused_padded<f32>, pnqp, traj_cost, select_best, slew_augment<f32,f64> | built " __DATE__ " " __TIME__;
+           "lqr_step_tiny<f32,f64>, lqr_step_wave1<f32>, lqr_step_mfma40<f32>, lqr_step_mfma40_padded<f32>, lqr_step_mfma40_narrow<f32>, nn_rollout<f32>, nn_linearize<f32>, nn_param_grad<f32>, env_linearize, env_param_grad<f32,f64>, kkt_grads, kkt_grads_shared<f32>, kkt_fused<f32>, kkt_fused_padded<f32>, pnqp, traj_cost, select_best, slew_augment<f32,f64> | built " __DATE__ " " __TIME__;
 }
 
 const char *mpc_lqr_last_error(void) { return g_last_error.c_str(); }
@@ -568,7 +580,7 @@ int mpc_lqr_step_route(const mpc_lqr_problem *p, const mpc_lqr_options *o, const
 int mpc_lqr_impl_supported(const mpc_lqr_problem *p, const mpc_lqr_options *o, int impl)
 {
     if (!p || check_problem(p, false, false) != MPC_OK || check_options(p, o) != MPC_OK) return 0;
-    if (impl < MPC_IMPL_GENERIC || impl > MPC_IMPL_DPP16_PAD) return 0;
+    if (impl < MPC_IMPL_GENERIC || impl > MPC_IMPL_MFMA40_NARROW) return 0;
     // (MPC_ENV_CTRL_CARRY: the lane-per-problem kernel alone, see step_route)
     if (o && o->true_dynamics && (o->true_dynamics->kind & MPC_ENV_CTRL_CARRY) && impl != MPC_IMPL_TINY) return 0;
     // sizes, dtype and options only: the alignment of the actual tensors is checked at launch

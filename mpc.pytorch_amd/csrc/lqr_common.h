@@ -17,16 +17,17 @@ void set_last_error(const char *msg);
 
 // the kernels behind mpc_lqr_step: the values of its `impl` argument (include/mpc_lqr.h)
 enum { MPC_IMPL_AUTO = 0, MPC_IMPL_GENERIC = 1, MPC_IMPL_MFMA16 = 2, MPC_IMPL_DPP16 = 3, MPC_IMPL_TINY = 4, MPC_IMPL_MFMA40 = 5,
-       MPC_IMPL_WAVE1 = 6, MPC_IMPL_MFMA40_PAD = 7, MPC_IMPL_DPP16_PAD = 8 };
+       MPC_IMPL_WAVE1 = 6, MPC_IMPL_MFMA40_PAD = 7, MPC_IMPL_DPP16_PAD = 8,
+       MPC_IMPL_MFMA40_NARROW = 9 };       // (9: forced only -- impl 0 never chooses it; the narrow instantiation of 7 for n_state <= 16)
 
 // Which kernel takes one step call and where its pieces live in the workspace (capi.hip: step_route decides, step_impl executes,
 // the queries mpc_lqr_step_route / mpc_lqr_qp_record read it off).  Host only.
 struct StepRoute {
     int code; const char *msg;     // code != 0: refused, with mpc_lqr_step's code and text (a string literal)
-    int kernel;                    // MPC_IMPL_* 1..8: the kernel that takes the call
+    int kernel;                    // MPC_IMPL_* 1..9: the kernel that takes the call
     int phase;                     // the generic kernels: 3 = sweep + rollout, 1 = sweep, 2 = rollout
     int ring;                      // 0, or the sweep ring of the 12/4 / 32/8 kernel (2 / 4, 2 / 3)
-    bool pad16;                    // padded 32/8: 16-byte gathers
+    bool pad16;                    // padded 32/8 and its narrow instantiation: 16-byte gathers
     bool needs_resolve;            // the generic re-solve of the problems flagged MPC_ST_C_ASYMMETRIC follows the launch
     // where things live in the workspace (byte offsets, -1 = not there)
     int64_t K_off, k_off;          // gains the kernel parks there (the caller's out->K / out->k otherwise)
@@ -130,6 +131,11 @@ bool mfma40_pad_supported(const StepParams<float> &p);
 bool mfma40_pad16_supported(const StepParams<float> &p);                        // ... with 16-byte gathers (n_state, n_ctrl multiples of 4)
 int launch_step_mfma40_pad4(const StepParams<float> &p, hipStream_t st);
 int launch_step_mfma40_pad16(const StepParams<float> &p, hipStream_t st);
+// ... and its NARROW instantiation for n_state <= 16 (-DMPC_MFMA40_XT=1: one state tile, tau padded to [x(16); u(8)]); p.K / p.k =
+// the kernel's own gains [T,B,8,16] / [T,B,8] inside the padded kernel's workspace layout
+bool mfma40_narrow_supported(const StepParams<float> &p);                       // the padded predicate with n_state <= 16
+int launch_step_mfma40_narrow4(const StepParams<float> &p, hipStream_t st);
+int launch_step_mfma40_narrow16(const StepParams<float> &p, hipStream_t st);
 // the KKT backward of that shape: the nested step with both costates riding along + kkt_outer_kernel (lqr_mfma40.hip, -DMPC_MFMA40_KKT)
 bool kkt_fused_mfma40_supported(const StepParams<float> &p, const float *dl_dx, const float *dl_du, const float *dC,
                                 const float *dF, const float *ws);

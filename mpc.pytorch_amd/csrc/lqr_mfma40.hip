@@ -101,17 +101,30 @@ MPC_DEV unsigned load_uniform_u32(const unsigned *g)
 MPC_DEV void sched_fence() { __builtin_amdgcn_sched_barrier(0); }
 // an opaque register-to-register identity (see mfma40::pick)
 MPC_DEV void pin(float &x) { asm volatile("" : "+v"(x)); }
-// Compiled three times (Makefile): the step kernels on the three-slot sweep ring (launch_step_mfma40), the same with
-// -DMPC_MFMA40_SWEEP_NSTAGE=2 (launch_step_mfma40_ring2), and with -DMPC_MFMA40_KKT the fused KKT backward (three slots).
+// Compiled nine times (Makefile): the step kernels on the three-slot sweep ring (launch_step_mfma40), the same with
+// -DMPC_MFMA40_SWEEP_NSTAGE=2 (launch_step_mfma40_ring2), with -DMPC_MFMA40_KKT the fused KKT backward (three slots); the padded
+// instantiation -DMPC_MFMA40_PAD=4 | 16 on two slots, as step kernels and as fused KKT backward (four objects); and the padded step
+// kernels on one state tile, -DMPC_MFMA40_XT=1 with either granule, on three slots (launch_step_mfma40_narrow4 / _narrow16).
 #ifndef MPC_MFMA40_SWEEP_NSTAGE
 #define MPC_MFMA40_SWEEP_NSTAGE 3              // (lqr_mfma40_body.h: why the sweep looks two timesteps ahead)
 #endif
-// the sweep's slots (12032 B each) or the pricing rollout's two (13056 B), + the layout-turn words; the fused backward's
-// second ring (31.5 KiB) lies inside its three sweep slots
-#define MPC_MFMA40_LDS_STEP ((MPC_MFMA40_SWEEP_NSTAGE * 12032 > 2 * 13056 ? MPC_MFMA40_SWEEP_NSTAGE * 12032 : 2 * 13056) + 512)
+// state tiles of 16 rows (lqr_mfma40_body.h): 2 = the 32/8 kernel, 1 = its narrow instantiation (n_state <= 16, padded only)
+#ifndef MPC_MFMA40_XT
+#define MPC_MFMA40_XT 2
+#endif
+#define MPC_MFMA40_NS_ (16 * MPC_MFMA40_XT)
+#define MPC_MFMA40_N_ (MPC_MFMA40_NS_ + 8)
+// a sweep stage C | F | record and a pricing-rollout stage C | F | K | record: 12032 and 13056 B at two state tiles, 4352 and 4864 at one
+#define MPC_MFMA40_STAGE_ (4 * MPC_MFMA40_N_ * MPC_MFMA40_N_ + 4 * MPC_MFMA40_NS_ * MPC_MFMA40_N_ + 512)
+#define MPC_MFMA40_RSTAGE_ (MPC_MFMA40_STAGE_ + 32 * MPC_MFMA40_NS_)
+// pass 2's stage of the fused backward, F | K | record | V: 10752 B at two state tiles
+#define MPC_MFMA40_KSTAGE_ (4 * MPC_MFMA40_NS_ * MPC_MFMA40_N_ + 32 * MPC_MFMA40_NS_ + 512 + 1024 * MPC_MFMA40_XT * MPC_MFMA40_XT)
+// the sweep's slots or the pricing rollout's two, + the layout-turn words; the fused backward's second ring (31.5 KiB) lies inside
+// its three sweep slots
+#define MPC_MFMA40_LDS_STEP ((MPC_MFMA40_SWEEP_NSTAGE * MPC_MFMA40_STAGE_ > 2 * MPC_MFMA40_RSTAGE_ ? MPC_MFMA40_SWEEP_NSTAGE * MPC_MFMA40_STAGE_ : 2 * MPC_MFMA40_RSTAGE_) + 512)
 // (the padded fused backward sweeps on two slots: its second ring alone sets the size then)
-#if defined(MPC_MFMA40_KKT) && MPC_MFMA40_LDS_STEP < 3 * 10752
-#define MPC_MFMA40_LDS (3 * 10752)
+#if defined(MPC_MFMA40_KKT) && MPC_MFMA40_LDS_STEP < 3 * MPC_MFMA40_KSTAGE_
+#define MPC_MFMA40_LDS (3 * MPC_MFMA40_KSTAGE_)
 #else
 #define MPC_MFMA40_LDS MPC_MFMA40_LDS_STEP
 #endif
@@ -216,6 +229,7 @@ MPC_DEV void absmax3(float &acc, float a, float b)
 }  // namespace mpclqr
 
 #include "lqr_mfma40_body.h"
+// (the fused KKT builds, whose array may be set by pass 2's ring instead; the step builds assert equality further down)
 static_assert(mpclqr::mfma40::LDS_TOTAL <= MPC_MFMA40_LDS, "the staging array is smaller than the body's rings");
 
 #ifdef MPC_MFMA40_KKT
@@ -316,7 +330,42 @@ template <int MODE> __global__ void __launch_bounds__(64, 1) lqr_step_mfma40_ker
 
 }  // namespace
 
-#ifdef MPC_MFMA40_PAD
+static_assert(mpclqr::mfma40::LDS_TOTAL == MPC_MFMA40_LDS, "the step kernels reserve their rings and nothing more");
+#if defined(MPC_MFMA40_PAD) && MPC_MFMA40_XT == 1
+// ---- the NARROW instantiation (two more compilations: -DMPC_MFMA40_PAD=4 / =16 -DMPC_MFMA40_XT=1): n_state <= 16 on ONE state tile ----
+// The padded kernel below with 24 x 24 | 16 x 24 stages and a fifth of the sweep's MFMAs.  Three sweep slots: a stage is 4352 B
+// and 17 (dword) or 7 (16-byte) staging instructions, so the ring that looks two timesteps ahead fits vmcnt's six bits and costs
+// 13.5 KiB of LDS a wave, where the 32/8 shape's dword gathers (47 a stage) had to stay on two slots.
+#if MPC_MFMA40_PAD == 4
+bool mfma40_narrow_supported(const StepParams<float> &p) { return mfma40_pad_supported(p) && p.ns <= 16; }
+#define MPC_MFMA40_LAUNCH launch_step_mfma40_narrow4
+#else
+#define MPC_MFMA40_LAUNCH launch_step_mfma40_narrow16
+#endif
+// p.K / p.k: the kernel's own gains [T,B,8,16] / [T,B,8] (16-byte aligned, workspace); p.K_user / p.k_user the caller's
+int MPC_MFMA40_LAUNCH(const StepParams<float> &p, hipStream_t st)
+{
+    if (!mfma40_narrow_supported(p)) { set_last_error("mfma40 (narrow): needs fp32, n_state <= 16, n_ctrl <= 8, max_linesearch_iter <= 16, no simulator"); return MPC_E_DIMS; }
+#if MPC_MFMA40_PAD == 16
+    if (!mfma40_pad16_supported(p)) { set_last_error("mfma40 (narrow): 16-byte gathers need n_state, n_ctrl multiples of 4 and 16-byte aligned blocks"); return MPC_E_ARG; }
+#endif
+    if (!p.K || !p.k || (!p.sweep_only && (!p.new_x || !p.new_u))) { set_last_error("mfma40 (narrow): K / k / new_x / new_u missing"); return MPC_E_NULL; }
+    if (((uintptr_t)p.K & 15) || ((uintptr_t)p.k & 15) || ((uintptr_t)p.Kk & 15)) { set_last_error("mfma40 (narrow): the gain workspace must be 16-byte aligned"); return MPC_E_ARG; }
+    if (p.bound_mode != MPC_BOUND_NONE)
+        hipLaunchKernelGGL(lqr_step_mfma40_kernel<2>, dim3(p.B), dim3(64), 0, st, p);
+    else if (p.zero_mask)
+        hipLaunchKernelGGL(lqr_step_mfma40_kernel<1>, dim3(p.B), dim3(64), 0, st, p);
+    else
+        hipLaunchKernelGGL(lqr_step_mfma40_kernel<0>, dim3(p.B), dim3(64), 0, st, p);
+    hipError_t e = hipGetLastError();
+    if (e != hipSuccess) {
+        set_last_error((std::string("lqr_step_mfma40_kernel (narrow): ") + hipGetErrorString(e)).c_str());
+        return MPC_E_LAUNCH;
+    }
+    return MPC_OK;
+}
+}  // namespace mpclqr
+#elif defined(MPC_MFMA40_PAD)
 // ---- the padded instantiation (two more compilations of this file: -DMPC_MFMA40_PAD=4 / =16, both on the two-slot sweep ring) ----
 #if MPC_MFMA40_PAD == 4
 // any n_state <= 32, n_ctrl <= 8 in float32: every staging access is a dword, nothing but 4-byte alignment is asked for

@@ -67,7 +67,24 @@ MPC_DEV float uniform_f32(const float *g)
 
 
 using wv::f32x4;
-constexpr int NS = 32, NC = 8, N = 40;
+// ---- The NARROW instantiation (-DMPC_MFMA40_XT=1 together with -DMPC_MFMA40_PAD=4|16): n_state <= 16 --------------------------
+// XT = number of 16-row state tiles.  The padded instantiation runs a 13..16-state problem (12/4 with a slew-rate penalty is 16/4)
+// with its second state tile all zeros: 104 MFMAs per timestep of the sweep where one state tile needs 20, and a 40 x 40 | 32 x 40
+// stage where 24 x 24 | 16 x 24 holds the problem.  Everything below that is a function of the number of state tiles is written in
+// XT, NS = 16 XT, N = NS + 8 and NT = XT + 1 (the control tile is tile XT); the sums over the real entries keep their order, so
+// that the narrow kernel adds the same numbers in the same order and leaves out only exact zeros.  The exact (unpadded) staging
+// paths are 32/8's own and stay literal: XT = 1 never takes them.
+#ifndef MPC_MFMA40_XT
+#define MPC_MFMA40_XT 2
+#endif
+constexpr int XT = MPC_MFMA40_XT, NT = XT + 1;
+#ifndef MPC_MFMA40_PAD
+static_assert(XT == 2, "one state tile: the padded instantiation only (-DMPC_MFMA40_PAD)");
+#endif
+static_assert(XT == 1 || XT == 2, "one or two state tiles");
+constexpr int NS = 16 * XT, NC = 8, N = NS + NC;
+// words of a timestep's record: c | x | u | f | k (+ the fused backward's 16 bound words behind it)
+constexpr int RW_X = N, RW_U = N + NS, RW_F = N + NS + NC, RW_K = N + 2 * NS + NC;
 constexpr int NSTAGE = 2;      // slots of the pricing rollout's LDS-DMA ring: one step in flight (27 KiB per wave -> 6 waves per CU)
 // Slots of the SWEEP's ring.  Two (the DMA one timestep = 3.6 us ahead) is enough while the address translations of the
 // blocks are cached; behind a kernel that has walked other memory (its own outer-product kernel in the fused backward: 810 MB
@@ -80,7 +97,7 @@ constexpr int NSTAGE = 2;      // slots of the pricing rollout's LDS-DMA ring: o
 #define MPC_MFMA40_SWEEP_NSTAGE 3
 #endif
 constexpr int SNSTAGE = MPC_MFMA40_SWEEP_NSTAGE;
-constexpr unsigned OFF_C = 0, OFF_F = 6400, OFF_R = 11520, STAGE_BYTES = 12032;   // (the record: 320 B, 448 B in the fused backward)
+constexpr unsigned OFF_C = 0, OFF_F = 4 * N * N, OFF_R = OFF_F + 4 * NS * N, STAGE_BYTES = OFF_R + 512;   // 6400, 11520, 12032 (the record: 320 B, 448 B in the fused backward)
 // ---- The PADDED instantiation (round 4; -DMPC_MFMA40_PAD=4|16, lqr_mfma40.hip): any n_state <= 32, n_ctrl <= 8 -----------------
 // The reference's sweep is shape-agnostic (mpc/lqr_step.py:61-158); rounds 1-3 had fast kernels for exactly 12/4 and 32/8 and a
 // generic kernel at 4 % of the roofline for everything between.  Here the 32/8 kernel runs ANY smaller shape: tau is padded to
@@ -104,9 +121,12 @@ constexpr int CH_F = PADK ? (NS * N * 4 + 64 * PADG - 1) / (64 * PADG) : 5;     
 constexpr int CH_R = PADK ? 2 : 1;                                               // ... of a record (dwords: 2 x 64 words)
 constexpr int DMA_PER_STAGE = CH_C + CH_F + CH_R;           // 13 = 7 (C) + 5 (F) + 1 (c | x | u) in the exact kernel
 // rollout stage: C | F | K_t (1 KiB) | record (c, x_{t+1}, u_t, f_t, k_t)
-constexpr unsigned ROFF_K = 11520, ROFF_R = 12544, RSTAGE_BYTES = 13056;
+constexpr unsigned KBYTES = 4 * NC * NS;                    // a timestep's gain block K_t [8][NS] (and M_t of the priced rollout's record)
+constexpr unsigned ROFF_K = OFF_R, ROFF_R = ROFF_K + KBYTES, RSTAGE_BYTES = ROFF_R + 512;      // 11520, 12544, 13056
 constexpr int RDMA_PER_STAGE = CH_C + CH_F + 1 + CH_R;      // 14 = 7 (C) + 5 (F) + 1 (K) + 1 (record)
 static_assert((SNSTAGE - 1) * DMA_PER_STAGE < 64 && RDMA_PER_STAGE < 64, "vmcnt is 6 bits: the dword gather needs the two-slot sweep ring");
+// (OFF_SCR lies behind the sweep's and the pricing rollout's rings; the lean and the priced rollout's rings, which never turn a
+// layout, may run over it -- see PSLOTS)
 constexpr unsigned OFF_SCR = SNSTAGE * STAGE_BYTES > NSTAGE * RSTAGE_BYTES ? SNSTAGE * STAGE_BYTES : NSTAGE * RSTAGE_BYTES;   // 512 B: row -> column layout turns
 constexpr unsigned LDS_TOTAL = OFF_SCR + 512;
 typedef StepParams<float> P;
@@ -147,7 +167,7 @@ struct KktArgs40 {
     float *vgws;                    // workspace [T,B,64]: v_t | g_t
 };
 // pass 2's stage: F | K_t | record (v_{t+1}, g_{t+1}, k_t) | V_{t+1}; three slots, the DMA two timesteps ahead
-constexpr unsigned KOFF_F = 0, KOFF_K = 5120, KOFF_R = 6144, KOFF_V = 6656, KSTAGE_BYTES = 10752;
+constexpr unsigned KOFF_F = 0, KOFF_K = 4 * NS * N, KOFF_R = KOFF_K + KBYTES, KOFF_V = KOFF_R + 512, KSTAGE_BYTES = KOFF_V + 1024 * XT * XT;   // 5120, 6144, 6656, 10752
 #ifdef MPC_KF40_VFULL
 constexpr int KSLOTS = 3, KDMA_PER_STAGE = 11;                 // 5 (F) + 1 (K) + 1 (record) + 4 (V)
 #else
@@ -160,8 +180,8 @@ constexpr int KDMA_PER_STAGE = PADK ? CH_F + 5 + 3 : KDMA_PER_STAGE_EXACT;
 static_assert((KSLOTS - 2) * KDMA_PER_STAGE < 64, "vmcnt is 6 bits");
 #endif
 // the constrained modes' record for the rollout that prices without C (rollout_priced): floats per problem-step
-constexpr int PREC = 328;                                      // M [8][32] | Quu [8][8] | m [8]
-constexpr int PSCR = 40;                                       // behind the records [T,B,PREC]: the second line-search trial's x' | u' [T,B,40]
+constexpr int PREC = NC * NS + NC * NC + NC;                   // M [8][32] | Quu [8][8] | m [8]: 328
+constexpr int PSCR = N;                                      // behind the records [T,B,PREC]: the second line-search trial's x' | u' [T,B,40]
 constexpr unsigned KLDS_TOTAL = KSLOTS * KSTAGE_BYTES;         // 31.5 KiB per wave: four waves per CU
 
 // ---- staging of the padded instantiation ---------------------------------------------------------------------------------
@@ -211,7 +231,12 @@ MPC_DEV void gather_F(const Gather &g, const float *blk_, unsigned nbytes_, unsi
     const float *blk = (const float *)wv::uniform_ptr(blk_);
     const unsigned nbytes = wv::uniform_u32(nbytes_);
 #pragma unroll
-    for (int k = 0; k < CH_F; ++k) wv::dma_buf<PADG>(true, blk, nbytes, g.foff[k], off + (unsigned)(64 * PADG * k));
+    for (int k = 0; k < CH_F; ++k) {
+        // (32 x 40 words are whole chunks at either granule; the narrow 16 x 24 block ends inside its second 16-byte chunk, and the
+        // lanes beyond it would write their zeros over the record that follows F in every stage)
+        const bool whole = 64 * (k + 1) * (PADG / 4) <= NS * N;
+        wv::dma_buf<PADG>(whole || (64 * k + wv::lane()) * (PADG / 4) < NS * N, blk, nbytes, g.foff[k], off + (unsigned)(64 * PADG * k));
+    }
 }
 // The record (the small vectors of a timestep: c | x | u | f | k at words 0, 40, 72, 80, 112 of its 128) gathered dword by
 // dword: lane l fetches words l and 64 + l, each from its own array (or sits the instruction out: padding stays the zero
@@ -233,17 +258,17 @@ MPC_DEV void rec_init(RecMap &m, const P &p, int lane, long b, bool with_c, bool
         m.step[j] = 0;
         m.kind[j] = 0;
         m.act[j] = false;
-        if (w < 40) {
+        if (w < RW_X) {
             const int a = pad_tau(w, ns, nc);
             if (with_c && a >= 0) { m.act[j] = true; m.ptr[j] = (const char *)(p.c + b * p.c_sb + a); m.step[j] = p.c_st * 4; }
-        } else if (w < 72) {
-            const int i = w - 40;
+        } else if (w < RW_U) {
+            const int i = w - RW_X;
             if (i < ns) { m.act[j] = true; m.ptr[j] = (const char *)(p.cur_x + b * ns + i); m.step[j] = (long)p.B * ns * 4; m.kind[j] = x_next ? 2 : 0; }
-        } else if (w < 80) {
-            const int a = w - 72;
+        } else if (w < RW_F) {
+            const int a = w - RW_U;
             if (a < nc) { m.act[j] = true; m.ptr[j] = (const char *)(p.cur_u + b * nc + a); m.step[j] = (long)p.B * nc * 4; }
-        } else if (w < 112) {
-            const int i = w - 80;
+        } else if (w < RW_K) {
+            const int i = w - RW_F;
             if (with_f && p.f != nullptr && p.T > 1 && i < ns) {
                 m.act[j] = true; m.ptr[j] = (const char *)(p.f + b * p.f_sb + i); m.step[j] = p.f_st * 4; m.kind[j] = 1;
             } else if (!with_f && !x_next && p.bound_mode == MPC_BOUND_TENSOR && i < 16 && (i & 7) < nc) {
@@ -251,11 +276,11 @@ MPC_DEV void rec_init(RecMap &m, const P &p, int lane, long b, bool with_c, bool
                 // scalar loads a timestep they sat in scalar registers across the QP's loop (round 6)
                 m.act[j] = true; m.ptr[j] = (const char *)((i < 8 ? p.lo : p.hi) + b * nc + (i & 7)); m.step[j] = (long)p.B * nc * 4;
             }
-        } else if (w < 120) {
-            if (kin) { m.act[j] = true; m.ptr[j] = (const char *)(kin + b * NC + (w - 112)); m.step[j] = (long)p.B * NC * 4; }
-            else if (MPC_QP_START && !x_next && p.qp_start && p.bound_mode != MPC_BOUND_NONE && w - 112 < nc) {
+        } else if (w < RW_K + 8) {
+            if (kin) { m.act[j] = true; m.ptr[j] = (const char *)(kin + b * NC + (w - RW_K)); m.step[j] = (long)p.B * NC * 4; }
+            else if (MPC_QP_START && !x_next && p.qp_start && p.bound_mode != MPC_BOUND_NONE && w - RW_K < nc) {
                 // mpc_lqr_options.qp_start in the sweep's record, where the exact kernel carries it (strides may be 0)
-                m.act[j] = true; m.ptr[j] = (const char *)(p.qp_start + b * p.qp_start_sb + (w - 112)); m.step[j] = p.qp_start_st * 4;
+                m.act[j] = true; m.ptr[j] = (const char *)(p.qp_start + b * p.qp_start_sb + (w - RW_K)); m.step[j] = p.qp_start_st * 4;
             }
         }
     }
@@ -272,20 +297,20 @@ MPC_DEV void rec_init_kkt(RecMap &m, const P &p, int lane, long b, const float *
         m.step[j] = 0;
         m.kind[j] = 0;
         m.act[j] = false;
-        if (w < 32) {
+        if (w < NS) {
             if (w < ns) { m.act[j] = true; m.ptr[j] = (const char *)(dl_dx + b * ns + w); m.step[j] = (long)p.B * ns * 4; }
-        } else if (w < 40) {
-            if (w - 32 < nc) { m.act[j] = true; m.ptr[j] = (const char *)(dl_du + b * nc + (w - 32)); m.step[j] = (long)p.B * nc * 4; }
-        } else if (w < 72) {
-            if (w - 40 < ns) { m.act[j] = true; m.ptr[j] = (const char *)(p.cur_x + b * ns + (w - 40)); m.step[j] = (long)p.B * ns * 4; }
-        } else if (w < 80) {
-            if (w - 72 < nc) { m.act[j] = true; m.ptr[j] = (const char *)(p.cur_u + b * nc + (w - 72)); m.step[j] = (long)p.B * nc * 4; }
-        } else if (w < 112) {
-            if (w - 80 < ns) { m.act[j] = true; m.ptr[j] = (const char *)(p.c + b * p.c_sb + (w - 80)); m.step[j] = p.c_st * 4; }
-        } else if (p.bound_mode == MPC_BOUND_TENSOR) {
+        } else if (w < RW_X) {
+            if (w - NS < nc) { m.act[j] = true; m.ptr[j] = (const char *)(dl_du + b * nc + (w - NS)); m.step[j] = (long)p.B * nc * 4; }
+        } else if (w < RW_U) {
+            if (w - RW_X < ns) { m.act[j] = true; m.ptr[j] = (const char *)(p.cur_x + b * ns + (w - RW_X)); m.step[j] = (long)p.B * ns * 4; }
+        } else if (w < RW_F) {
+            if (w - RW_U < nc) { m.act[j] = true; m.ptr[j] = (const char *)(p.cur_u + b * nc + (w - RW_U)); m.step[j] = (long)p.B * nc * 4; }
+        } else if (w < RW_K) {
+            if (w - RW_F < ns) { m.act[j] = true; m.ptr[j] = (const char *)(p.c + b * p.c_sb + (w - RW_F)); m.step[j] = p.c_st * 4; }
+        } else if (p.bound_mode == MPC_BOUND_TENSOR && (XT == 2 || w < RW_K + 16)) {
             // words 112..119 u_lower_t, 120..127 u_upper_t: the pinned set is decided from the record (kkt_pinned_lds)
-            const int a = (w - 112) & 7;
-            if (a < nc) { m.act[j] = true; m.ptr[j] = (const char *)((w < 120 ? p.lo : p.hi) + b * nc + a); m.step[j] = (long)p.B * nc * 4; }
+            const int a = (w - RW_K) & 7;
+            if (a < nc) { m.act[j] = true; m.ptr[j] = (const char *)((w < RW_K + 8 ? p.lo : p.hi) + b * nc + a); m.step[j] = (long)p.B * nc * 4; }
         }
     }
 }
@@ -312,7 +337,7 @@ MPC_DEV void rec_issue(const RecMap &m, long tl, long tf, long tx, unsigned off,
 #pragma unroll
     for (int j = 0; j < 2; ++j) {
         const long ti = m.kind[j] == 1 ? tf : (m.kind[j] == 2 ? tx : tl);
-        wv::dma4_if(m.act[j] && !(skip_c && j == 0 && lane < 40), m.ptr[j] + ti * m.step[j], off + 256u * (unsigned)j);
+        wv::dma4_if(m.act[j] && !(skip_c && j == 0 && lane < N), m.ptr[j] + ti * m.step[j], off + 256u * (unsigned)j);
     }
 }
 // every pass of the padded instantiation starts on cleared staging memory: the record words of padded entries are never
@@ -858,8 +883,8 @@ MPC_DEV int pnqp8v(const float (&col0)[8], float diagv, float qv, float lbv, flo
 // MODE 0: unconstrained; 1: u_zero_I mask; 2: box constraints (pnqp8v).
 // V_t (the four tiles as they sit in the registers: pass 2 reads them back as A operands) and v_t | g_t (column layout:
 // lane group q holds entries 16I + 4q + v) to the fused backward's workspace
-MPC_DEV void kkt_store_vvg(const KktArgs40 &kx, long tb, const Lane &L, const wv::f32x4 (&Vd)[2][2], const float (&vcol)[2][4],
-                           const float (&gcol)[2][4])
+MPC_DEV void kkt_store_vvg(const KktArgs40 &kx, long tb, const Lane &L, const wv::f32x4 (&Vd)[XT][XT], const float (&vcol)[XT][4],
+                           const float (&gcol)[XT][4])
 {
 #ifdef MPC_KF40_NOVS              // (diagnostic build: what the V stores cost)
     if (tb < 0)
@@ -868,17 +893,18 @@ MPC_DEV void kkt_store_vvg(const KktArgs40 &kx, long tb, const Lane &L, const wv
     // (1, 0) tile with the indices swapped (`-DMPC_KF40_VFULL`: all four tiles, as in round 3).  3 KiB per problem-step each way
     // instead of 4 in a kernel that moves 1.9 GB at 5 TB/s.
 #pragma unroll
-    for (int I = 0; I < 2; ++I)
+    for (int I = 0; I < XT; ++I)
 #pragma unroll
-        for (int J = 0; J < 2; ++J) {
+        for (int J = 0; J < XT; ++J) {
 #ifndef MPC_KF40_VFULL
             if (I == 0 && J == 1) continue;
 #endif
-            wv::store_f32x4(kx.Vws + tb * 1024 + (2 * I + J) * 256 + 4 * L.lane, Vd[I][J]);
+            wv::store_f32x4(kx.Vws + tb * 1024 + (XT * I + J) * 256 + 4 * L.lane, Vd[I][J]);
         }
     if (L.r == 0) {
+        // (the workspace keeps its 32/8 layout at every XT: V_t 1024 words, v_t | g_t 32 + 32 -- pass 2's record is fetched from it by lane)
 #pragma unroll
-        for (int I = 0; I < 2; ++I) {
+        for (int I = 0; I < XT; ++I) {
             wv::store_f32x4(kx.vgws + tb * 64 + 16 * I + 4 * L.q, wv::f32x4{vcol[I][0], vcol[I][1], vcol[I][2], vcol[I][3]});
             wv::store_f32x4(kx.vgws + tb * 64 + 32 + 16 * I + 4 * L.q, wv::f32x4{gcol[I][0], gcol[I][1], gcol[I][2], gcol[I][3]});
         }
@@ -921,21 +947,21 @@ MPC_DEV double sweep_wave(const P &p, float *Kout, float *kout, double *w0_out =
     // instead of 33 %; one that fails is priced from C like the reference and reports MPC_ST_NOMINAL_OFF_DYNAMICS.
     const bool verify = MODE == 0 && !KKT && !p.on_dynamics && on_dynamics_out != nullptr;
     float offdyn = 0.f;                // largest violation this lane has seen (> 0: off the dynamics)
-    float xnext[2][4];                 // the nominal state of the timestep worked on last (t + 1), column layout
+    float xnext[XT][4];                // the nominal state of the timestep worked on last (t + 1), column layout
 #pragma unroll
-    for (int I = 0; I < 2; ++I)
+    for (int I = 0; I < XT; ++I)
 #pragma unroll
         for (int v = 0; v < 4; ++v) xnext[I][v] = 0.f;
     Stream d;
     stream_init(d, p, L, KKT ? kx : nullptr, verify && p.f != nullptr && T > 1);
     const f32x4 zero4 = {0.f, 0.f, 0.f, 0.f};
-    f32x4 Vd[2][2];                    // V, D layout
-    float vcol[2][4];                  // v, column layout: vcol[I][v] = v[16I + 4q + v]
-    float lcol[2][4], gcol[2][4];      // lambda_{t+1}, g_{t+1} in the same layout (KKT)
+    f32x4 Vd[XT][XT];                  // V, D layout
+    float vcol[XT][4];                 // v, column layout: vcol[I][v] = v[16I + 4q + v]
+    float lcol[XT][4], gcol[XT][4];    // lambda_{t+1}, g_{t+1} in the same layout (KKT)
 #pragma unroll
-    for (int I = 0; I < 2; ++I) {
+    for (int I = 0; I < XT; ++I) {
 #pragma unroll
-        for (int J = 0; J < 2; ++J) Vd[I][J] = zero4;
+        for (int J = 0; J < XT; ++J) Vd[I][J] = zero4;
 #pragma unroll
         for (int v = 0; v < 4; ++v) vcol[I][v] = lcol[I][v] = gcol[I][v] = 0.f;
     }
@@ -973,13 +999,13 @@ MPC_DEV double sweep_wave(const P &p, float *Kout, float *kout, double *w0_out =
         // Tile (I, J), registers v = 0..3 of lane (q, r) = C[16I + 4q + v][16J + r] -- read through C's symmetry as
         // C[16J + r][16I + 4q .. + 3]: four consecutive floats of one row, ONE 16-byte LDS read per tile instead of four
         // 4-byte reads (rows are 160 B, so every such quadruple is 16-byte aligned)
-        f32x4 Qd[3][3];
+        f32x4 Qd[NT][NT];
 #pragma unroll
-        for (int I = 0; I < 3; ++I)
+        for (int I = 0; I < NT; ++I)
 #pragma unroll
-            for (int J = 0; J < 3; ++J) {
+            for (int J = 0; J < NT; ++J) {
                 // only tile row / column 2 has padding (rows, columns 40..47)
-                const bool in = (I < 2 || L.q < 2) && (J < 2 || L.r < 8);
+                const bool in = (I < XT || L.q < 2) && (J < XT || L.r < 8);
                 // (a padding lane reads on -- into the next row, or F's block of the stage -- and is zeroed below: one lane address + compile-time offsets)
                 const f32x4 x = wv::lds_f32x4(base + OFF_C + 4u * (unsigned)(L.r * N + 4 * L.q) + 4u * (unsigned)(16 * J * N + 16 * I));
 #pragma unroll
@@ -995,16 +1021,16 @@ MPC_DEV double sweep_wave(const P &p, float *Kout, float *kout, double *w0_out =
             // adds a timestep less; the maxima as v_max3 with |.| modifiers, two entries an instruction)
             const unsigned a0 = base + OFF_C + 4u * (unsigned)(4 * L.q * N + L.r);
 #pragma unroll
-            for (int I = 0; I < 3; ++I)
+            for (int I = 0; I < NT; ++I)
 #pragma unroll
-                for (int J = I; J < 3; ++J) {
-                    const bool in = (I < 2 || L.q < 2) && (J < 2 || L.r < 8);
+                for (int J = I; J < NT; ++J) {
+                    const bool in = (I < XT || L.q < 2) && (J < XT || L.r < 8);
                     float dq[4];
 #pragma unroll
                     for (int v = 0; v < 4; ++v) {
                         const float tr = wv::lds_f32(a0 + 4u * (unsigned)((16 * I + v) * N + 16 * J));
                         const float dd = Qd[I][J][v] - tr;
-                        dq[v] = (J < 2) ? dd : (in ? dd : 0.f);          // (I = 2 means J = 2: only the third tile column has padding here)
+                        dq[v] = (J < XT) ? dd : (in ? dd : 0.f);         // (I = 2 means J = 2: only the third tile column has padding here)
                     }
                     wv::absmax3(asym, dq[0], dq[1]);
                     wv::absmax3(asym, dq[2], dq[3]);
@@ -1012,19 +1038,19 @@ MPC_DEV double sweep_wave(const P &p, float *Kout, float *kout, double *w0_out =
                     wv::absmax3(cmax, Qd[I][J][2], Qd[I][J][3]);
                 }
         }
-        float tcol[3][4], trow[3], crow[3];
+        float tcol[NT][4], trow[NT], crow[NT];
 #pragma unroll
-        for (int I = 0; I < 3; ++I)
+        for (int I = 0; I < NT; ++I)
 #pragma unroll
             for (int v = 0; v < 4; ++v) {
                 const int i = 16 * I + 4 * L.q + v;
-                const float x = wv::lds_f32(base + OFF_R + 160 + 4u * (unsigned)i);        // (i up to 47: still inside the record, zeroed below)
+                const float x = wv::lds_f32(base + OFF_R + 4 * RW_X + 4u * (unsigned)i);   // (i up to 47: still inside the record, zeroed below)
                 tcol[I][v] = i < N ? x : 0.f;
             }
 #pragma unroll
-        for (int J = 0; J < 3; ++J) {
+        for (int J = 0; J < NT; ++J) {
             const int j = 16 * J + L.r;
-            const float x = wv::lds_f32(base + OFF_R + 160 + 4u * (unsigned)j);
+            const float x = wv::lds_f32(base + OFF_R + 4 * RW_X + 4u * (unsigned)j);
             const float c = wv::lds_f32(base + OFF_R + 4u * (unsigned)j);
             trow[J] = j < N ? x : 0.f;
             crow[J] = j < N ? (KKT ? -c : c) : 0.f;
@@ -1034,15 +1060,15 @@ MPC_DEV double sweep_wave(const P &p, float *Kout, float *kout, double *w0_out =
         // lpart, gpart: the products of its rows 16I + 4q + v) and reduced once, where its value is first needed -- q_u in
         // front of the control block, q_x not before v = q_x + Qxu k (one reduction for c_back, F'v and Qxu k together;
         // round 2 reduced each of them: eight two-swap butterflies per timestep, now three).
-        float qpart[3];
-        float lpart[2] = {0.f, 0.f}, gpart[2] = {0.f, 0.f};
+        float qpart[NT];
+        float lpart[XT] = {0.f}, gpart[XT] = {0.f};
 #pragma unroll
-        for (int J = 0; J < 3; ++J) {
+        for (int J = 0; J < NT; ++J) {
             qpart[J] = 0.f;
-            if (KKT && J == 2) continue;
+            if (KKT && J == XT) continue;
             float s = 0.f;
 #pragma unroll
-            for (int I = 0; I < 3; ++I)
+            for (int I = 0; I < NT; ++I)
 #pragma unroll
                 for (int v = 0; v < 4; ++v) s = fmaf(Qd[I][J][v], tcol[I][v], s);
             // (the nested nominal of the fused backward is zero: c_back = c = -r; tau there is tau*, C tau* + c_x starts lambda_t)
@@ -1053,36 +1079,36 @@ MPC_DEV double sweep_wave(const P &p, float *Kout, float *kout, double *w0_out =
             // nominal cost (:169): tau'(C tau / 2 + c) -- with the unreduced shares the sum runs over all 64 lanes after the loop
             float s = 0.f;
 #pragma unroll
-            for (int J = 0; J < 3; ++J) s = fmaf(trow[J], fmaf(0.5f, qpart[J], L.q == 0 ? crow[J] : 0.f), s);
+            for (int J = 0; J < NT; ++J) s = fmaf(trow[J], fmaf(0.5f, qpart[J], L.q == 0 ? crow[J] : 0.f), s);
             old_cost += (double)s;
         }
         PROF40_MARK(1);
 
         if (t < T - 1) {
             // ---- F as FB[(I',v)][J] = F[16I' + 4q + v][16J + r]
-            float FB[8][3];
+            float FB[4 * XT][NT];
 #pragma unroll
-            for (int Ip = 0; Ip < 2; ++Ip)
+            for (int Ip = 0; Ip < XT; ++Ip)
 #pragma unroll
                 for (int v = 0; v < 4; ++v)
 #pragma unroll
-                    for (int J = 0; J < 3; ++J) {
+                    for (int J = 0; J < NT; ++J) {
                         const int m = 16 * Ip + 4 * L.q + v, col = 16 * J + L.r;
-                        const bool in = J < 2 || L.r < 8;
+                        const bool in = J < XT || L.r < 8;
                         const float x = wv::lds_f32(base + OFF_F + 4u * (unsigned)(m * N + col));       // (col up to 47: the next row, zeroed below)
                         FB[4 * Ip + v][J] = in ? x : 0.f;
                     }
             if (verify) {
                 // F_t tau_t + f_t against x_{t+1}: rows 16I' + 4q + v of F times tau (row layout), summed over the 16 lanes
 #pragma unroll
-                for (int Ip = 0; Ip < 2; ++Ip) {
+                for (int Ip = 0; Ip < XT; ++Ip) {
                     f32x4 ft = zero4;
-                    if (p.f) ft = wv::lds_f32x4(base + OFF_R + 320 + 4u * (unsigned)(16 * Ip + 4 * L.q));
+                    if (p.f) ft = wv::lds_f32x4(base + OFF_R + 4 * RW_F + 4u * (unsigned)(16 * Ip + 4 * L.q));
 #pragma unroll
                     for (int v = 0; v < 4; ++v) {
                         float s = 0.f;
 #pragma unroll
-                        for (int J = 0; J < 3; ++J) s = fmaf(FB[4 * Ip + v][J], trow[J], s);
+                        for (int J = 0; J < NT; ++J) s = fmaf(FB[4 * Ip + v][J], trow[J], s);
                         const float pred = wv::row_sum(s) + ft[v];
                         float r = fabsf(pred - xnext[Ip][v]) - 1e-5f * (1.f + fabsf(xnext[Ip][v]));
                         r = (r == r) ? r : 1.f;
@@ -1096,38 +1122,38 @@ MPC_DEV double sweep_wave(const P &p, float *Kout, float *kout, double *w0_out =
             wv::sched_fence();
             // (three tiles at a time, their accumulation chains interleaved: an MFMA that waits for the previous one's
             // accumulator issues every 40 clocks, an independent one every 32)
-            f32x4 Yd[2][3];
+            f32x4 Yd[XT][NT];
 #pragma unroll
-            for (int Im = 0; Im < 2; ++Im) {
+            for (int Im = 0; Im < XT; ++Im) {
 #pragma unroll
-                for (int J = 0; J < 3; ++J) Yd[Im][J] = zero4;
+                for (int J = 0; J < NT; ++J) Yd[Im][J] = zero4;
 #pragma unroll
-                for (int Ip = 0; Ip < 2; ++Ip)
+                for (int Ip = 0; Ip < XT; ++Ip)
 #pragma unroll
                     for (int v = 0; v < 4; ++v)
 #pragma unroll
-                        for (int J = 0; J < 3; ++J) Yd[Im][J] = wv::mfma(Vd[Ip][Im][v], FB[4 * Ip + v][J], Yd[Im][J]);
+                        for (int J = 0; J < NT; ++J) Yd[Im][J] = wv::mfma(Vd[Ip][Im][v], FB[4 * Ip + v][J], Yd[Im][J]);
             }
             // ---- Q = C + F'Y  (A operand = F' = FB, B operand = Y in D layout); tiles (0,2), (1,2) are
             // not needed below (Qxu is used through Qux)
 #pragma unroll
-            for (int I = 0; I < 3; ++I)
+            for (int I = 0; I < NT; ++I)
 #pragma unroll
-                for (int Ip = 0; Ip < 2; ++Ip)
+                for (int Ip = 0; Ip < XT; ++Ip)
 #pragma unroll
                     for (int v = 0; v < 4; ++v)
 #pragma unroll
-                        for (int J = 0; J < 3; ++J) {
-                            if (J == 2 && I < 2) continue;
+                        for (int J = 0; J < NT; ++J) {
+                            if (J == XT && I < XT) continue;
                             Qd[I][J] = wv::mfma(FB[4 * Ip + v][I], Yd[Ip][J][v], Qd[I][J]);
                         }
             wv::sched_fence();
             // ---- q = c_back + F'v
 #pragma unroll
-            for (int J = 0; J < 3; ++J) {
+            for (int J = 0; J < NT; ++J) {
                 float s = qpart[J];
 #pragma unroll
-                for (int Ip = 0; Ip < 2; ++Ip)
+                for (int Ip = 0; Ip < XT; ++Ip)
 #pragma unroll
                     for (int v = 0; v < 4; ++v) s = fmaf(FB[4 * Ip + v][J], vcol[Ip][v], s);
                 qpart[J] = s;
@@ -1135,10 +1161,10 @@ MPC_DEV double sweep_wave(const P &p, float *Kout, float *kout, double *w0_out =
             if (KKT) {
                 // lambda_t += F_x' lambda_{t+1}, g_t = F_x' g_{t+1} (- Qxu k_t below); lambda_{t+1} into dF_t's block
 #pragma unroll
-                for (int J = 0; J < 2; ++J) {
+                for (int J = 0; J < XT; ++J) {
                     float sl = lpart[J], sg = 0.f;
 #pragma unroll
-                    for (int Ip = 0; Ip < 2; ++Ip)
+                    for (int Ip = 0; Ip < XT; ++Ip)
 #pragma unroll
                         for (int v = 0; v < 4; ++v) {
                             sl = fmaf(FB[4 * Ip + v][J], lcol[Ip][v], sl);
@@ -1149,7 +1175,7 @@ MPC_DEV double sweep_wave(const P &p, float *Kout, float *kout, double *w0_out =
                 }
                 if (L.r == 0) {
 #pragma unroll
-                    for (int I = 0; I < 2; ++I)
+                    for (int I = 0; I < XT; ++I)
                         st_row4(kx->dF + tb * (long)(PADK ? p.ns * (p.ns + p.nc) : NS * N), PADK ? p.ns : NS, 16 * I + 4 * L.q,
                                 f32x4{lcol[I][0], lcol[I][1], lcol[I][2], lcol[I][3]});
                 }
@@ -1159,7 +1185,7 @@ MPC_DEV double sweep_wave(const P &p, float *Kout, float *kout, double *w0_out =
         PROF40_MARK(2);
         if (PADK) {
 #pragma unroll
-            for (int v = 0; v < 4; ++v) Qd[2][2][v] += padd[v];
+            for (int v = 0; v < 4; ++v) Qd[XT][XT][v] += padd[v];
         }
         // ---- Quu, qu; K = -Quu^-1 Qux, k = -Quu^-1 qu   (:84-94; LDL' for the pinverse)
         // Quu stays spread over lanes in every mode (Ldl8V): column c of it is register c & 3 of lane row c >> 2 of the
@@ -1172,7 +1198,7 @@ MPC_DEV double sweep_wave(const P &p, float *Kout, float *kout, double *w0_out =
         float qu[8], kk[8];
         bool fr[8];
         // q_u (row layout): the one vector needed before the gains; q_x stays in shares until v takes it
-        const float qrow2 = crow[2] + sum_q(qpart[2]);
+        const float qrow2 = crow[XT] + sum_q(qpart[XT]);
 #pragma unroll
         for (int a = 0; a < 8; ++a) {
             qu[a] = wv::readlane(qrow2, a);
@@ -1182,7 +1208,7 @@ MPC_DEV double sweep_wave(const P &p, float *Kout, float *kout, double *w0_out =
         if (MODE == 0) {
             float col[8];
 #pragma unroll
-            for (int v = 0; v < 4; ++v) wv::rows01(Qd[2][2][v], col[v], col[4 + v]);
+            for (int v = 0; v < 4; ++v) wv::rows01(Qd[XT][XT][v], col[v], col[4 + v]);
             ldl8v<true>(facv, col);
             if (facv.sing != 0.f) status |= MPC_ST_QUU_SINGULAR;
         }
@@ -1193,7 +1219,7 @@ MPC_DEV double sweep_wave(const P &p, float *Kout, float *kout, double *w0_out =
         } else if (MODE == 1) {                          // :99-127: pinned controls drop out of the solve
             unsigned zlo, zhi;
             if (PADK && KKT) {
-                kkt_pinned_lds(p, base + OFF_R + 4u * 72u, base + OFF_R + 4u * 112u, base + OFF_R + 4u * 120u, L.lane, zlo, zhi);
+                kkt_pinned_lds(p, base + OFF_R + 4u * RW_U, base + OFF_R + 4u * RW_K, base + OFF_R + 4u * (RW_K + 8), L.lane, zlo, zhi);
             } else {
                 zlo = KKT ? kkt_pinned_word(p, tb, 0) : zero_mask_word(p, tb, 0);
                 zhi = KKT ? kkt_pinned_word(p, tb, 1) : zero_mask_word(p, tb, 1);
@@ -1206,7 +1232,7 @@ MPC_DEV double sweep_wave(const P &p, float *Kout, float *kout, double *w0_out =
             }
             // the free block of Quu, identity elsewhere, factorised spread over lanes (k rides in the K solve below)
 #pragma unroll
-            for (int v = 0; v < 4; ++v) wv::rows01(Qd[2][2][v], col1[v], col1[4 + v]);
+            for (int v = 0; v < 4; ++v) wv::rows01(Qd[XT][XT][v], col1[v], col1[4 + v]);
             float diagv = 0.f;
 #pragma unroll
             for (int a = 0; a < 8; ++a) diagv = pick(L.r == a, col1[a], diagv);
@@ -1218,19 +1244,19 @@ MPC_DEV double sweep_wave(const P &p, float *Kout, float *kout, double *w0_out =
             // the QP's data spread over lanes (pnqp8v): H's columns by two row swaps per accumulator register
             float col0[8];
 #pragma unroll
-            for (int v = 0; v < 4; ++v) wv::rows01(Qd[2][2][v], col0[v], col0[4 + v]);
+            for (int v = 0; v < 4; ++v) wv::rows01(Qd[XT][XT][v], col0[v], col0[4 + v]);
             float diagv = 0.f;
 #pragma unroll
             for (int a = 0; a < 8; ++a) diagv = pick(L.r == a, col0[a], diagv);
             const bool r8 = L.r < 8;
-            const float uav = wv::lds_f32(base + OFF_R + 288 + 4u * (unsigned)(r8 ? L.r : 0));
+            const float uav = wv::lds_f32(base + OFF_R + 4 * RW_U + 4u * (unsigned)(r8 ? L.r : 0));
             float lov = p.lo_s, hiv = p.hi_s;
             if (PADK) {
                 // (round 6) this lane's own bounds: scalars, or the record's words 80.. / 88.. (rec_init); a control beyond n_ctrl is unbounded
                 const unsigned rr = 4u * (unsigned)(r8 ? L.r : 0);
                 if (p.bound_mode != MPC_BOUND_SCALAR) {
-                    lov = wv::lds_f32(base + OFF_R + 320 + rr);
-                    hiv = wv::lds_f32(base + OFF_R + 352 + rr);
+                    lov = wv::lds_f32(base + OFF_R + 4 * RW_F + rr);
+                    hiv = wv::lds_f32(base + OFF_R + 4 * RW_F + 32 + rr);
                 }
                 lov = L.r < p.nc ? lov : -3e38f;
                 hiv = L.r < p.nc ? hiv : 3e38f;
@@ -1257,7 +1283,7 @@ MPC_DEV double sweep_wave(const P &p, float *Kout, float *kout, double *w0_out =
                 // store further down.)
                 // it rode in with the record (stream_init: lanes 28..29; padded instantiation: rec_init's words 112..), entry r in lane (q, r)
                 // like the nominal control
-                xv = wv::lds_f32(base + OFF_R + 448 + 4u * (unsigned)(r8 ? L.r : 0));
+                xv = wv::lds_f32(base + OFF_R + 4 * RW_K + 4u * (unsigned)(r8 ? L.r : 0));
                 xv = (r8 && (!PADK || L.r < p.nc)) ? xv : 0.f;
                 xv = (xv == xv) ? xv : 0.f;              // (a NaN would survive the clamp)
             } else if (!MPC_MFMA40_QP_WARM || !warm) {
@@ -1294,11 +1320,11 @@ MPC_DEV double sweep_wave(const P &p, float *Kout, float *kout, double *w0_out =
             frq_v = mv;
         }
         PROF40_MARK(3);
-        f32x4 Kd[2];                    // K, B layout of the value update: register v of lane (q,r) = K[4q+v][16J+r]
-        float Kp[2][2];                 // ... its registers 2h, 2h + 1 packed into one full-k MFMA operand (see below)
-        f32x4 Md[2];                    // M = Qux + Quu K in the same layout (constrained modes)
+        f32x4 Kd[XT];                   // K, B layout of the value update: register v of lane (q,r) = K[4q+v][16J+r]
+        float Kp[XT][2];                // ... its registers 2h, 2h + 1 packed into one full-k MFMA operand (see below)
+        f32x4 Md[XT];                   // M = Qux + Quu K in the same layout (constrained modes)
         Md[0] = zero4;
-        Md[1] = zero4;
+        if (XT > 1) Md[XT - 1] = zero4;
         {
             // ONE solve for all 32 columns of Qux (and qu): lane row 0 takes column r of tile 0, row 1 column r of tile 1 --
             // a column's eight entries are registers v of rows 0 and 1 of its tile, and one row swap per register
@@ -1308,7 +1334,8 @@ MPC_DEV double sweep_wave(const P &p, float *Kout, float *kout, double *w0_out =
             // two passes of 64 dependent multiply-adds instead of one.)
             float rhs[8], sol[8];
 #pragma unroll
-            for (int v = 0; v < 4; ++v) wv::swap16(Qd[2][0][v], Qd[2][1][v], rhs[v], rhs[4 + v]);
+            // (one state tile: lane row 1 has no column of its own and solves row 0's over again)
+            for (int v = 0; v < 4; ++v) wv::swap16(Qd[XT][0][v], Qd[XT][XT - 1][v], rhs[v], rhs[4 + v]);
             if (MODE != 0) {
                 // (u_zero_I mode: lane row 2 carries qu, as in the unconstrained mode; the box QP has its k already)
 #pragma unroll
@@ -1362,7 +1389,7 @@ MPC_DEV double sweep_wave(const P &p, float *Kout, float *kout, double *w0_out =
                 float k0, k1;
                 wv::swap16(Kc[v], Kc[4 + v], k0, k1);
                 Kd[0][v] = L.q < 2 ? k0 : 0.f;
-                Kd[1][v] = L.q < 2 ? k1 : 0.f;
+                if (XT > 1) Kd[XT - 1][v] = L.q < 2 ? k1 : 0.f;
             }
 #ifndef MPC_MFMA40_KPAD
             // (round 4) A contraction over the eight controls is register v of the operand tiles for v = 0..3, and in each only
@@ -1371,63 +1398,63 @@ MPC_DEV double sweep_wave(const P &p, float *Kout, float *kout, double *w0_out =
             // M = Qux + Quu K (constrained modes) and V = Qxx + Qxu K, all their operands packed first, then the MFMAs in one
             // run (vector instructions between MFMAs cost more than they hide: profiles/r04_ab_mfma_shadow.log).
 #pragma unroll
-            for (int J = 0; J < 2; ++J)
+            for (int J = 0; J < XT; ++J)
 #pragma unroll
                 for (int h = 0; h < 2; ++h) Kp[J][h] = wv::lower_halves(Kd[J][2 * h], Kd[J][2 * h + 1]);
-            float Qp[2] = {0.f, 0.f}, Ap[2][2];
+            float Qp[2] = {0.f, 0.f}, Ap[XT][2];
             if (MODE != 0) {
 #pragma unroll
-                for (int h = 0; h < 2; ++h) Qp[h] = wv::lower_halves(Qd[2][2][2 * h], Qd[2][2][2 * h + 1]);
+                for (int h = 0; h < 2; ++h) Qp[h] = wv::lower_halves(Qd[XT][XT][2 * h], Qd[XT][XT][2 * h + 1]);
             }
 #pragma unroll
-            for (int I = 0; I < 2; ++I)
+            for (int I = 0; I < XT; ++I)
 #pragma unroll
-                for (int h = 0; h < 2; ++h) Ap[I][h] = wv::lower_halves(Qd[2][I][2 * h], Qd[2][I][2 * h + 1]);
+                for (int h = 0; h < 2; ++h) Ap[I][h] = wv::lower_halves(Qd[XT][I][2 * h], Qd[XT][I][2 * h + 1]);
             wv::sched_fence();
             if (MODE != 0) {
                 // M = Qux + Quu K: the Quu tile of Q is, by symmetry, its own A operand, the Qux tiles the accumulators
 #pragma unroll
-                for (int J = 0; J < 2; ++J) Md[J] = Qd[2][J];
+                for (int J = 0; J < XT; ++J) Md[J] = Qd[XT][J];
 #pragma unroll
                 for (int h = 0; h < 2; ++h)
 #pragma unroll
-                    for (int J = 0; J < 2; ++J) Md[J] = wv::mfma(Qp[h], Kp[J][h], Md[J]);
+                    for (int J = 0; J < XT; ++J) Md[J] = wv::mfma(Qp[h], Kp[J][h], Md[J]);
             }
             // ---- V = Qxx + Qxu K   (:155-158 with K'(Qux + Quu K) = 0; v follows below)
 #pragma unroll
-            for (int I = 0; I < 2; ++I)
+            for (int I = 0; I < XT; ++I)
 #pragma unroll
-                for (int J = 0; J < 2; ++J) Vd[I][J] = Qd[I][J];
+                for (int J = 0; J < XT; ++J) Vd[I][J] = Qd[I][J];
 #pragma unroll
             for (int h = 0; h < 2; ++h)
 #pragma unroll
-                for (int I = 0; I < 2; ++I)
+                for (int I = 0; I < XT; ++I)
 #pragma unroll
-                    for (int J = 0; J < 2; ++J) Vd[I][J] = wv::mfma(Ap[I][h], Kp[J][h], Vd[I][J]);
+                    for (int J = 0; J < XT; ++J) Vd[I][J] = wv::mfma(Ap[I][h], Kp[J][h], Vd[I][J]);
             wv::sched_fence();
 #else
             if (MODE != 0) {
 #pragma unroll
-                for (int J = 0; J < 2; ++J) {
-                    Md[J] = Qd[2][J];
+                for (int J = 0; J < XT; ++J) {
+                    Md[J] = Qd[XT][J];
 #pragma unroll
-                    for (int v = 0; v < 4; ++v) Md[J] = wv::mfma(Qd[2][2][v], Kd[J][v], Md[J]);
+                    for (int v = 0; v < 4; ++v) Md[J] = wv::mfma(Qd[XT][XT][v], Kd[J][v], Md[J]);
                 }
             }
 #pragma unroll
-            for (int I = 0; I < 2; ++I)
+            for (int I = 0; I < XT; ++I)
 #pragma unroll
-                for (int J = 0; J < 2; ++J) Vd[I][J] = Qd[I][J];
+                for (int J = 0; J < XT; ++J) Vd[I][J] = Qd[I][J];
 #pragma unroll
             for (int v = 0; v < 4; ++v)
 #pragma unroll
-                for (int I = 0; I < 2; ++I)
+                for (int I = 0; I < XT; ++I)
 #pragma unroll
-                    for (int J = 0; J < 2; ++J) Vd[I][J] = wv::mfma(Qd[2][I][v], Kd[J][v], Vd[I][J]);
+                    for (int J = 0; J < XT; ++J) Vd[I][J] = wv::mfma(Qd[XT][I][v], Kd[J][v], Vd[I][J]);
 #endif
             if (L.q < 2) {
 #pragma unroll
-                for (int J = 0; J < 2; ++J)
+                for (int J = 0; J < XT; ++J)
 #pragma unroll
                     for (int v = 0; v < 4; ++v) Kout[(tb * NC + 4 * L.q + v) * NS + 16 * J + L.r] = Kd[J][v];
 #ifdef MPC_MFMA40_PAD
@@ -1435,7 +1462,7 @@ MPC_DEV double sweep_wave(const P &p, float *Kout, float *kout, double *w0_out =
                 if (p.K_user) {
                     // (rows of K_t [nc,ns] through a raw buffer over the block: entries beyond the true shape fall outside it)
 #pragma unroll
-                    for (int J = 0; J < 2; ++J)
+                    for (int J = 0; J < XT; ++J)
 #pragma unroll
                         for (int v = 0; v < 4; ++v) {
                             const bool in = 4 * L.q + v < p.nc && 16 * J + L.r < p.ns;
@@ -1476,53 +1503,54 @@ MPC_DEV double sweep_wave(const P &p, float *Kout, float *kout, double *w0_out =
             float *rec = p.Kk + tb * (long)PREC;
             if (L.q < 2) {
 #pragma unroll
-                for (int J = 0; J < 2; ++J)
+                for (int J = 0; J < XT; ++J)
 #pragma unroll
                     for (int v = 0; v < 4; ++v) rec[(4 * L.q + v) * NS + 16 * J + L.r] = Md[J][v];
                 if (L.r < NC) {
 #pragma unroll
-                    for (int v = 0; v < 4; ++v) rec[256 + (4 * L.q + v) * NC + L.r] = Qd[2][2][v];
+                    for (int v = 0; v < 4; ++v) rec[NC * NS + (4 * L.q + v) * NC + L.r] = Qd[XT][XT][v];
                 }
             }
-            if (L.lane < NC) rec[320 + L.lane] = mkv;
+            if (L.lane < NC) rec[NC * NS + NC * NC + L.lane] = mkv;
             const float kv = kprev_v;                                     // (k spread over lanes)
             w0 += 0.5 * (double)wv::row_sum(kv * (mkv + (L.r < NC ? qrow2 : 0.f)));
         }
-        float vrow[2], lrow[2] = {0.f, 0.f}, grow[2] = {0.f, 0.f};
+        float vrow[XT], lrow[XT] = {0.f}, grow[XT] = {0.f};
         float kq4[8] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
         if (MODE == 2) Pnqp8vSpread<0>::run(kqp_v, kq4);
 #pragma unroll
-        for (int J = 0; J < 2; ++J) {
+        for (int J = 0; J < XT; ++J) {
             float s = 0.f;
 #pragma unroll
             for (int v = 0; v < 4; ++v) {
                 const float ka = MODE == 2 ? pick(L.q == 0, kq4[v], pick(L.q == 1, kq4[4 + v], 0.f))
                                            : pick(L.q == 0, kk[v], pick(L.q == 1, kk[4 + v], 0.f));
-                s = fmaf(Qd[2][J][v], ka, s);
+                s = fmaf(Qd[XT][J][v], ka, s);
                 if (MODE != 0) s = fmaf(Kd[J][v], mq[v], s);      // + K'(qu + Quu k)
             }
             // v = q_x + Qxu k (+ K'(qu + Quu k)): c_back's, F'v's and this step's shares reduced together
             vrow[J] = crow[J] + sum_q(qpart[J] + s);
             if (KKT) {
-                lrow[J] = sum_q(lpart[J]) + wv::lds_f32(base + OFF_R + 320 + 4u * (unsigned)(16 * J + L.r));
+                lrow[J] = sum_q(lpart[J]) + wv::lds_f32(base + OFF_R + 4 * RW_F + 4u * (unsigned)(16 * J + L.r));
                 grow[J] = sum_q(gpart[J] - s);              // g_t = F_x' g_{t+1} - Qxu k_t: what v just took on
             }
         }
         // row -> column layout through the scratch words
         wv::lds_sync();
         if (L.q == 0) {
+            // (tile J's sixteen words at 64 J; written out, not looped: the unrolled loop moved the two-tile kernels' schedule)
             wv::lds_store_f32(OFF_SCR + 4u * (unsigned)L.r, vrow[0]);
-            wv::lds_store_f32(OFF_SCR + 64 + 4u * (unsigned)L.r, vrow[1]);
+            if (XT > 1) wv::lds_store_f32(OFF_SCR + 64 + 4u * (unsigned)L.r, vrow[XT - 1]);
             if (KKT) {
                 wv::lds_store_f32(OFF_SCR + 128 + 4u * (unsigned)L.r, lrow[0]);
-                wv::lds_store_f32(OFF_SCR + 192 + 4u * (unsigned)L.r, lrow[1]);
+                if (XT > 1) wv::lds_store_f32(OFF_SCR + 192 + 4u * (unsigned)L.r, lrow[XT - 1]);
                 wv::lds_store_f32(OFF_SCR + 256 + 4u * (unsigned)L.r, grow[0]);
-                wv::lds_store_f32(OFF_SCR + 320 + 4u * (unsigned)L.r, grow[1]);
+                if (XT > 1) wv::lds_store_f32(OFF_SCR + 320 + 4u * (unsigned)L.r, grow[XT - 1]);
             }
         }
         wv::lds_sync();
 #pragma unroll
-        for (int I = 0; I < 2; ++I) {
+        for (int I = 0; I < XT; ++I) {
             const f32x4 w = wv::lds_f32x4(OFF_SCR + 64u * (unsigned)I + 16u * (unsigned)L.q);
 #pragma unroll
             for (int v = 0; v < 4; ++v) vcol[I][v] = w[v];
@@ -1535,11 +1563,16 @@ MPC_DEV double sweep_wave(const P &p, float *Kout, float *kout, double *w0_out =
         }
         if (KKT && t == 0) {
             kkt_store_vvg(*kx, tb, L, Vd, vcol, gcol);
-            if (v0g0) { v0g0[0] = vrow[0]; v0g0[1] = vrow[1]; v0g0[2] = grow[0]; v0g0[3] = grow[1]; }
+            if (v0g0) {
+                v0g0[0] = vrow[0];
+                if (XT > 1) v0g0[1] = vrow[XT - 1];
+                v0g0[2] = grow[0];
+                if (XT > 1) v0g0[3] = grow[XT - 1];
+            }
         }
         if (verify) {
 #pragma unroll
-            for (int I = 0; I < 2; ++I)
+            for (int I = 0; I < XT; ++I)
 #pragma unroll
                 for (int v = 0; v < 4; ++v) xnext[I][v] = tcol[I][v];
         }
@@ -1551,7 +1584,7 @@ MPC_DEV double sweep_wave(const P &p, float *Kout, float *kout, double *w0_out =
         if (verify) {
             // the rollout starts from x_init: the nominal (xnext holds x_0 now) has to as well
 #pragma unroll
-            for (int I = 0; I < 2; ++I)
+            for (int I = 0; I < XT; ++I)
 #pragma unroll
                 for (int v = 0; v < 4; ++v) {
                     const float x0 = ld_xinit(p, L.b, 16 * I + 4 * L.q + v);
@@ -1653,6 +1686,13 @@ MPC_DEV void rstream_init(RStream &d, const P &p, const Lane &L, const float *Ki
     }
 }
 
+// this lane's 16 bytes of a gain block K_t (or M_t) [8][NS]: 1 KiB, every lane -- or the 512 B of one state tile, lanes 0..31
+MPC_DEV void dma_gain(int lane, const char *g, unsigned off)
+{
+    if (XT == 2) wv::dma16(g, off);
+    else wv::dma16_if(lane < (int)(KBYTES / 16), g, off);
+}
+
 MPC_DEV void rstage_issue(const P &p, const RStream &d, const Lane &L, int t, int slot)
 {
     const unsigned base = (unsigned)slot * RSTAGE_BYTES;
@@ -1662,7 +1702,7 @@ MPC_DEV void rstage_issue(const P &p, const RStream &d, const Lane &L, int t, in
     if (PADK) {
         gather_C(d.g, d.Cb + tl * p.C_st, base + OFF_C, L.lane);
         gather_F(d.g, p.T > 1 ? d.Fb + tf * p.F_st : d.Cb, p.T > 1 ? d.g.fbytes : 0u, base + OFF_F);
-        wv::dma16(d.k_ptr + tl * d.k_step + d.lo, base + ROFF_K);
+        dma_gain(L.lane, d.k_ptr + tl * d.k_step + d.lo, base + ROFF_K);
         rec_issue(d.rm, tl, tf, tx, base + ROFF_R);
         return;
     }
@@ -1680,9 +1720,9 @@ MPC_DEV void rollout_pass(const P &p, const RStream &d, const Lane &L, float alp
 {
     const int T = p.T;
     const f32x4 zero4 = {0.f, 0.f, 0.f, 0.f};
-    f32x4 Xd[2], DXd[2];
+    f32x4 Xd[XT], DXd[XT];
 #pragma unroll
-    for (int I = 0; I < 2; ++I) {
+    for (int I = 0; I < XT; ++I) {
 #pragma unroll
         for (int v = 0; v < 4; ++v) Xd[I][v] = ld_xinit(p, L.b, 16 * I + 4 * L.q + v);
         DXd[I] = zero4;
@@ -1705,21 +1745,21 @@ MPC_DEV void rollout_pass(const P &p, const RStream &d, const Lane &L, float alp
         // tools/ubench/mfma16_turn.hip)
         f32x4 Ud = zero4;
         {
-            float a[8];
+            float a[4 * XT];
 #pragma unroll
-            for (int J = 0; J < 2; ++J) {        // four consecutive words of K's row r per lane and state tile: one 16-byte LDS read
+            for (int J = 0; J < XT; ++J) {       // four consecutive words of K's row r per lane and state tile: one 16-byte LDS read
                 const f32x4 x = wv::lds_f32x4(base + ROFF_K + 4u * (unsigned)((L.r < NC ? L.r : 0) * NS + 16 * J + 4 * L.q));
 #pragma unroll
                 for (int i = 0; i < 4; ++i) a[4 * J + i] = L.r < NC ? x[i] : 0.f;
             }
             wv::sched_fence();
 #pragma unroll
-            for (int k = 0; k < 8; ++k) Ud = wv::mfma(a[k], DXd[k >> 2][k & 3], Ud);
+            for (int k = 0; k < 4 * XT; ++k) Ud = wv::mfma(a[k], DXd[k >> 2][k & 3], Ud);
             wv::sched_fence();
         }
         {
             const unsigned qo = 16u * (unsigned)(L.q < 2 ? L.q : 0);
-            const f32x4 ub = wv::lds_f32x4(rec + 288 + qo), kb = wv::lds_f32x4(rec + 448 + qo);
+            const f32x4 ub = wv::lds_f32x4(rec + 4 * RW_U + qo), kb = wv::lds_f32x4(rec + 4 * RW_K + qo);
             float s = 0.f;
             unsigned zw = 0u;                    // the zero flags of controls 4q .. 4q+3
             if (MODE == 1) {
@@ -1744,36 +1784,36 @@ MPC_DEV void rollout_pass(const P &p, const RStream &d, const Lane &L, float alp
         {
             float part = 0.f;
 #pragma unroll
-            for (int I = 0; I < 3; ++I) {
+            for (int I = 0; I < NT; ++I) {
                 f32x4 G = zero4;
                 const int col = 16 * I + L.r;
                 const bool cin = col < N;
                 {
-                    float a[12];
+                    float a[4 * XT + 4];
 #pragma unroll
-                    for (int k = 0; k < 8; ++k) {
+                    for (int k = 0; k < 4 * XT; ++k) {
                         const float x = wv::lds_f32(base + OFF_C + 4u * (unsigned)((16 * (k >> 2) + 4 * L.q + (k & 3)) * N + (cin ? col : 0)));
                         a[k] = cin ? x : 0.f;
                     }
 #pragma unroll
                     for (int v = 0; v < 4; ++v) {
                         const bool in = cin && L.q < 2;
-                        const float x = wv::lds_f32(base + OFF_C + 4u * (unsigned)((in ? 32 + 4 * L.q + v : 0) * N + (cin ? col : 0)));
-                        a[8 + v] = in ? x : 0.f;
+                        const float x = wv::lds_f32(base + OFF_C + 4u * (unsigned)((in ? NS + 4 * L.q + v : 0) * N + (cin ? col : 0)));
+                        a[4 * XT + v] = in ? x : 0.f;
                     }
                     wv::sched_fence();
 #pragma unroll
-                    for (int k = 0; k < 8; ++k) G = wv::mfma(a[k], Xd[k >> 2][k & 3], G);
+                    for (int k = 0; k < 4 * XT; ++k) G = wv::mfma(a[k], Xd[k >> 2][k & 3], G);
 #pragma unroll
-                    for (int v = 0; v < 4; ++v) G = wv::mfma(a[8 + v], Ud[v], G);
+                    for (int v = 0; v < 4; ++v) G = wv::mfma(a[4 * XT + v], Ud[v], G);
                     wv::sched_fence();
                 }
                 // rows 16I + 4q + v of (C tau') against the same entries of tau' and c
-                const bool rin = I < 2 || L.q < 2;
+                const bool rin = I < XT || L.q < 2;
                 const f32x4 cv = wv::lds_f32x4(rec + 4u * (unsigned)(rin ? 16 * I + 4 * L.q : 0));
 #pragma unroll
                 for (int v = 0; v < 4; ++v) {
-                    const float tv = I < 2 ? Xd[I][v] : Ud[v];
+                    const float tv = I < XT ? Xd[I < XT ? I : 0][v] : Ud[v];
                     part = fmaf(rin ? tv : 0.f, fmaf(0.5f, G[v], cv[v]), part);
                 }
             }
@@ -1783,33 +1823,33 @@ MPC_DEV void rollout_pass(const P &p, const RStream &d, const Lane &L, float alp
         if (t < T - 1) {
             const long tb1 = (long)(t + 1) * p.B + L.b;
 #pragma unroll
-            for (int Im = 0; Im < 2; ++Im) {
+            for (int Im = 0; Im < XT; ++Im) {
                 f32x4 acc = zero4;
-                if (p.f) acc = wv::lds_f32x4(rec + 320 + 4u * (unsigned)(16 * Im + 4 * L.q));
+                if (p.f) acc = wv::lds_f32x4(rec + 4 * RW_F + 4u * (unsigned)(16 * Im + 4 * L.q));
                 const int row = 16 * Im + L.r;
                 {
-                    float a[12];
+                    float a[4 * XT + 4];
 #pragma unroll
-                    for (int k = 0; k < 8; ++k)
+                    for (int k = 0; k < 4 * XT; ++k)
                         a[k] = wv::lds_f32(base + OFF_F + 4u * (unsigned)(row * N + 16 * (k >> 2) + 4 * L.q + (k & 3)));
 #pragma unroll
                     for (int v = 0; v < 4; ++v) {
-                        const float x = wv::lds_f32(base + OFF_F + 4u * (unsigned)(row * N + (L.q < 2 ? 32 + 4 * L.q + v : 0)));
-                        a[8 + v] = L.q < 2 ? x : 0.f;
+                        const float x = wv::lds_f32(base + OFF_F + 4u * (unsigned)(row * N + (L.q < 2 ? NS + 4 * L.q + v : 0)));
+                        a[4 * XT + v] = L.q < 2 ? x : 0.f;
                     }
                     wv::sched_fence();
 #pragma unroll
-                    for (int k = 0; k < 8; ++k) acc = wv::mfma(a[k], Xd[k >> 2][k & 3], acc);
+                    for (int k = 0; k < 4 * XT; ++k) acc = wv::mfma(a[k], Xd[k >> 2][k & 3], acc);
 #pragma unroll
-                    for (int v = 0; v < 4; ++v) acc = wv::mfma(a[8 + v], Ud[v], acc);
+                    for (int v = 0; v < 4; ++v) acc = wv::mfma(a[4 * XT + v], Ud[v], acc);
                     wv::sched_fence();
                 }
                 if (store && L.r == 0) st_x4(p, tb1, 16 * Im + 4 * L.q, acc);
                 DXd[Im] = acc;      // parked here until both tiles are done (the second product still reads Xd)
             }
 #pragma unroll
-            for (int Im = 0; Im < 2; ++Im) {
-                const f32x4 xb = wv::lds_f32x4(rec + 160 + 4u * (unsigned)(16 * Im + 4 * L.q));
+            for (int Im = 0; Im < XT; ++Im) {
+                const f32x4 xb = wv::lds_f32x4(rec + 4 * RW_X + 4u * (unsigned)(16 * Im + 4 * L.q));
                 Xd[Im] = DXd[Im];
 #pragma unroll
                 for (int v = 0; v < 4; ++v) DXd[Im][v] = Xd[Im][v] - xb[v];
@@ -1899,7 +1939,7 @@ template <int MODE> MPC_DEV void rollout_wave(const P &p, const float *Kin, cons
 // four slots in the same LDS, the DMA three steps ahead.  Column r still rolls out alpha = decay^r (column 0 gives
 // full_du_norm, :243-245); the winner's column stores.
 // ---------------------------------------------------------------------------------------------
-constexpr unsigned LOFF_F = 0, LOFF_K = 5120, LOFF_R = 6144, LSTAGE_BYTES = 6656;
+constexpr unsigned LOFF_F = 0, LOFF_K = 4 * NS * N, LOFF_R = LOFF_K + KBYTES, LSTAGE_BYTES = LOFF_R + 512;      // 5120, 6144, 6656
 constexpr int LSLOTS = 4, LDMA_PER_STAGE = CH_F + 1 + CH_R;    // 7 = 5 (F) + 1 (K) + 1 (record) in the exact kernel
 static_assert((LSLOTS - 2) * LDMA_PER_STAGE < 64, "vmcnt is 6 bits");
 static_assert(LSLOTS * LSTAGE_BYTES <= LDS_TOTAL, "lean rollout ring exceeds the wave's LDS");
@@ -1912,7 +1952,7 @@ MPC_DEV void lstage_issue(const P &p, const RStream &d, const Lane &L, int t, in
     const long tx = t + 1 < p.T ? t + 1 : t;                         // x_{t+1}
     if (PADK) {
         gather_F(d.g, p.T > 1 ? d.Fb + tf * p.F_st : d.Cb, p.T > 1 ? d.g.fbytes : 0u, base + LOFF_F);
-        wv::dma16(d.k_ptr + tl * d.k_step + d.lo, base + LOFF_K);
+        dma_gain(L.lane, d.k_ptr + tl * d.k_step + d.lo, base + LOFF_K);
         rec_issue(d.rm, tl, tf, tx, base + LOFF_R, true, L.lane);        // (no c in this pass)
         return;
     }
@@ -1952,9 +1992,9 @@ MPC_DEV void rollout_lean(const P &p, const Lane &L, const float *Kin, const flo
     }
     const bool store = L.r == win;
     const f32x4 zero4 = {0.f, 0.f, 0.f, 0.f};
-    f32x4 Xd[2], DXd[2];
+    f32x4 Xd[XT], DXd[XT];
 #pragma unroll
-    for (int I = 0; I < 2; ++I) {
+    for (int I = 0; I < XT; ++I) {
 #pragma unroll
         for (int v = 0; v < 4; ++v) Xd[I][v] = ld_xinit(p, L.b, 16 * I + 4 * L.q + v);
         DXd[I] = zero4;
@@ -1973,31 +2013,34 @@ MPC_DEV void rollout_lean(const P &p, const Lane &L, const float *Kin, const flo
         const unsigned rec = base + LOFF_R;
         // ---- u' = K dx + u + alpha k   (:192)
         f32x4 Ud = zero4;
-        float a[8];
+        float a[4 * XT];
 #pragma unroll
-        for (int J = 0; J < 2; ++J) {        // four consecutive words of K's row r per lane and state tile: one 16-byte LDS read
+        for (int J = 0; J < XT; ++J) {       // four consecutive words of K's row r per lane and state tile: one 16-byte LDS read
             const f32x4 x = wv::lds_f32x4(base + LOFF_K + 4u * (unsigned)((L.r < NC ? L.r : 0) * NS + 16 * J + 4 * L.q));
 #pragma unroll
             for (int i = 0; i < 4; ++i) a[4 * J + i] = L.r < NC ? x[i] : 0.f;
         }
         const unsigned qo = 16u * (unsigned)(L.q < 2 ? L.q : 0);
-        const f32x4 ub = wv::lds_f32x4(rec + 288 + qo), kb = wv::lds_f32x4(rec + 448 + qo);
+        const f32x4 ub = wv::lds_f32x4(rec + 4 * RW_U + qo), kb = wv::lds_f32x4(rec + 4 * RW_K + qo);
         {
             const int tn = t + LSLOTS - 1;
             lstage_issue(p, d, L, tn < T ? tn : T - 1, tn % LSLOTS);
         }
         wv::sched_fence();
         {
-            // two half-length accumulation chains side by side (dependent MFMAs issue every 40 clocks, independent 32)
+            // two half-length accumulation chains side by side (dependent MFMAs issue every 40 clocks, independent 32); one state
+            // tile has the first chain alone
             f32x4 U2 = zero4;
 #pragma unroll
             for (int k = 0; k < 4; ++k) {
                 Ud = wv::mfma(a[k], DXd[0][k], Ud);
-                U2 = wv::mfma(a[4 + k], DXd[1][k], U2);
+                if (XT > 1) U2 = wv::mfma(a[4 * (XT - 1) + k], DXd[XT - 1][k], U2);
             }
             wv::sched_fence();
+            if (XT > 1) {
 #pragma unroll
-            for (int v = 0; v < 4; ++v) Ud[v] += U2[v];
+                for (int v = 0; v < 4; ++v) Ud[v] += U2[v];
+            }
         }
         {
             float s = 0.f;
@@ -2024,43 +2067,43 @@ MPC_DEV void rollout_lean(const P &p, const Lane &L, const float *Kin, const flo
         if (t < T - 1) {
             const long tb1 = (long)(t + 1) * p.B + L.b;
             // both output tiles at once: operands of the two first, then their accumulation chains interleaved
-            f32x4 acc[2];
-            float fa[2][12];
+            f32x4 acc[XT];
+            float fa[XT][4 * XT + 4];
 #pragma unroll
-            for (int Im = 0; Im < 2; ++Im) {
+            for (int Im = 0; Im < XT; ++Im) {
                 acc[Im] = zero4;
-                if (p.f) acc[Im] = wv::lds_f32x4(rec + 320 + 4u * (unsigned)(16 * Im + 4 * L.q));
+                if (p.f) acc[Im] = wv::lds_f32x4(rec + 4 * RW_F + 4u * (unsigned)(16 * Im + 4 * L.q));
                 const int row = 16 * Im + L.r;
 #pragma unroll
-                for (int J = 0; J < 2; ++J) {    // (rows of F are 160 B: every such quadruple is 16-byte aligned)
+                for (int J = 0; J < XT; ++J) {   // (rows of F are 160 B: every such quadruple is 16-byte aligned)
                     const f32x4 x = wv::lds_f32x4(base + LOFF_F + 4u * (unsigned)(row * N + 16 * J + 4 * L.q));
 #pragma unroll
                     for (int i = 0; i < 4; ++i) fa[Im][4 * J + i] = x[i];
                 }
 #pragma unroll
                 for (int h = 0; h < 2; ++h)        // the control columns as two full-k operands (uctl)
-                    fa[Im][8 + h] = wv::lds_f32(base + LOFF_F + 4u * (unsigned)(row * N + 32 + uctl(L.q) + 2 * h));
+                    fa[Im][4 * XT + h] = wv::lds_f32(base + LOFF_F + 4u * (unsigned)(row * N + NS + uctl(L.q) + 2 * h));
             }
             wv::sched_fence();
 #pragma unroll
-            for (int k = 0; k < 8; ++k)
+            for (int k = 0; k < 4 * XT; ++k)
 #pragma unroll
-                for (int Im = 0; Im < 2; ++Im) acc[Im] = wv::mfma(fa[Im][k], Xd[k >> 2][k & 3], acc[Im]);
+                for (int Im = 0; Im < XT; ++Im) acc[Im] = wv::mfma(fa[Im][k], Xd[k >> 2][k & 3], acc[Im]);
 #pragma unroll
             for (int h = 0; h < 2; ++h) {
                 const float up = wv::lower_halves(Ud[2 * h], Ud[2 * h + 1]);
 #pragma unroll
-                for (int Im = 0; Im < 2; ++Im) acc[Im] = wv::mfma(fa[Im][8 + h], up, acc[Im]);
+                for (int Im = 0; Im < XT; ++Im) acc[Im] = wv::mfma(fa[Im][4 * XT + h], up, acc[Im]);
             }
             wv::sched_fence();
 #pragma unroll
-            for (int Im = 0; Im < 2; ++Im) {
+            for (int Im = 0; Im < XT; ++Im) {
                 if (store) st_x4(p, tb1, 16 * Im + 4 * L.q, acc[Im]);
                 DXd[Im] = acc[Im];
             }
 #pragma unroll
-            for (int Im = 0; Im < 2; ++Im) {
-                const f32x4 xb = wv::lds_f32x4(rec + 160 + 4u * (unsigned)(16 * Im + 4 * L.q));
+            for (int Im = 0; Im < XT; ++Im) {
+                const f32x4 xb = wv::lds_f32x4(rec + 4 * RW_X + 4u * (unsigned)(16 * Im + 4 * L.q));
                 Xd[Im] = DXd[Im];
 #pragma unroll
                 for (int v = 0; v < 4; ++v) DXd[Im][v] = Xd[Im][v] - xb[v];
@@ -2100,7 +2143,10 @@ MPC_DEV void rollout_lean(const P &p, const Lane &L, const float *Kin, const flo
 // against the 13 KiB of the pass that reads C), 12 more MFMAs per timestep than the lean pass (M dx: 8, Quu e: 4) against 36.
 // The sweep leaves (M, Quu, m) in the record p.Kk [T,B,328].  Trial 0 stores as it goes, another winner is replayed (lean).
 // ---------------------------------------------------------------------------------------------
-constexpr unsigned POFF_F = 0, POFF_K = 5120, POFF_R = 6144, POFF_M = 6656, POFF_Q = 7680, PSTAGE_BYTES = 8000;
+constexpr unsigned POFF_F = 0, POFF_K = 4 * NS * N, POFF_R = POFF_K + KBYTES, POFF_M = POFF_R + 512, POFF_Q = POFF_M + KBYTES,
+                   PSTAGE_BYTES = POFF_Q + 320;                                   // 5120, 6144, 6656, 7680, 8000
+// (the rollouts' rings are cut out of ALL of LDS_TOTAL: on one state tile the fourth slot of this one ends exactly at LDS_TOTAL, over the
+// 512 layout-turn bytes at OFF_SCR.  Those are the SWEEP's alone, and every rollout pass starts with dma_wait<0> + pad_clear)
 constexpr int PSLOTS = LDS_TOTAL / PSTAGE_BYTES >= 4 ? 4 : 3, PDMA_PER_STAGE = CH_F + 1 + CH_R + 2;   // 9 = 5 (F) + K + record + M + (Quu | m)
 static_assert((PSLOTS - 2) * PDMA_PER_STAGE < 64, "vmcnt is 6 bits");
 static_assert(PSLOTS * PSTAGE_BYTES <= LDS_TOTAL && PSLOTS >= 3, "priced rollout ring exceeds the wave's LDS");
@@ -2113,7 +2159,7 @@ MPC_DEV void pstage_issue(const P &p, const RStream &d, const Lane &L, const cha
     const long tx = t + 1 < p.T ? t + 1 : t;                         // x_{t+1}
     if (PADK) {
         gather_F(d.g, p.T > 1 ? d.Fb + tf * p.F_st : d.Cb, p.T > 1 ? d.g.fbytes : 0u, base + POFF_F);
-        wv::dma16(d.k_ptr + tl * d.k_step + d.lo, base + POFF_K);
+        dma_gain(L.lane, d.k_ptr + tl * d.k_step + d.lo, base + POFF_K);
         rec_issue(d.rm, tl, tf, tx, base + POFF_R, true, L.lane);
     } else {
     dma_kib<5>(d.f_ptr + tf * d.f_step + d.lo, base + POFF_F);
@@ -2121,8 +2167,8 @@ MPC_DEV void pstage_issue(const P &p, const RStream &d, const Lane &L, const cha
     wv::dma16_if(d.r_active && L.lane >= 10, d.r_ptr + rec_off(d.r_is_f ? tf : (d.r_is_x ? tx : tl), d.r_step), base + POFF_R);
     }
     const char *rec = m_ptr + tl * ((long)p.B * PREC * 4) + d.lo;
-    wv::dma16(rec, base + POFF_M);
-    wv::dma16_if(L.lane < 18, rec + 1024, base + POFF_Q);
+    dma_gain(L.lane, rec, base + POFF_M);
+    wv::dma16_if(L.lane < 18, rec + KBYTES, base + POFF_Q);
 }
 
 template <int MODE>
@@ -2146,9 +2192,9 @@ MPC_DEV void rollout_priced(const P &p, const Lane &L, const float *Kin, const f
     const long xst = L.r == 0 ? (long)p.B * NS : (long)p.B * PSCR;
     const long ust = L.r == 0 ? (long)p.B * NC : (long)p.B * PSCR;
     const f32x4 zero4 = {0.f, 0.f, 0.f, 0.f};
-    f32x4 Xd[2], DXd[2];
+    f32x4 Xd[XT], DXd[XT];
 #pragma unroll
-    for (int I = 0; I < 2; ++I) {
+    for (int I = 0; I < XT; ++I) {
 #pragma unroll
         for (int v = 0; v < 4; ++v) Xd[I][v] = ld_xinit(p, L.b, 16 * I + 4 * L.q + v);
         DXd[I] = zero4;
@@ -2170,10 +2216,10 @@ MPC_DEV void rollout_priced(const P &p, const Lane &L, const float *Kin, const f
         const unsigned rec = base + POFF_R;
         // ---- operands of the timestep out of its stage: rows of K and of M (A operands), Quu's columns, m, u, k
         // (the price e'(m + M dx + Quu e / 2) cannot be skipped where e = 0: e = (alpha - 1) k in every column but the first)
-        float a[8], am[8], aq[2];
+        float a[4 * XT], am[4 * XT], aq[2];
         const unsigned krow = 4u * (unsigned)((L.r < NC ? L.r : 0) * NS + 4 * L.q);
 #pragma unroll
-        for (int J = 0; J < 2; ++J) {        // (16-byte LDS reads: four consecutive words of row r of K, of M, per state tile)
+        for (int J = 0; J < XT; ++J) {       // (16-byte LDS reads: four consecutive words of row r of K, of M, per state tile)
             const f32x4 x = wv::lds_f32x4(base + POFF_K + krow + 64u * (unsigned)J);
             const f32x4 y = wv::lds_f32x4(base + POFF_M + krow + 64u * (unsigned)J);
 #pragma unroll
@@ -2189,7 +2235,7 @@ MPC_DEV void rollout_priced(const P &p, const Lane &L, const float *Kin, const f
             aq[h] = L.r < NC ? x : 0.f;                           // A[i = r][k = q] = Quu[r][uctl(q) + 2h]
         }
         const unsigned qo = 16u * (unsigned)(uq ? L.q : 0);
-        const f32x4 ub = wv::lds_f32x4(rec + 288 + qo), kb = wv::lds_f32x4(rec + 448 + qo);
+        const f32x4 ub = wv::lds_f32x4(rec + 4 * RW_U + qo), kb = wv::lds_f32x4(rec + 4 * RW_K + qo);
         const f32x4 mm = wv::lds_f32x4(base + POFF_Q + 256 + qo);
         {
             const int tn = t + PSLOTS - 1;
@@ -2204,13 +2250,15 @@ MPC_DEV void rollout_priced(const P &p, const Lane &L, const float *Kin, const f
 #pragma unroll
             for (int k = 0; k < 4; ++k) {
                 Ud = wv::mfma(a[k], DXd[0][k], Ud);
-                U2 = wv::mfma(a[4 + k], DXd[1][k], U2);
+                if (XT > 1) U2 = wv::mfma(a[4 * (XT - 1) + k], DXd[XT - 1][k], U2);
                 G = wv::mfma(am[k], DXd[0][k], G);
-                G2 = wv::mfma(am[4 + k], DXd[1][k], G2);
+                if (XT > 1) G2 = wv::mfma(am[4 * (XT - 1) + k], DXd[XT - 1][k], G2);
             }
             wv::sched_fence();
+            if (XT > 1) {
 #pragma unroll
-            for (int v = 0; v < 4; ++v) { Ud[v] += U2[v]; G[v] += G2[v]; }
+                for (int v = 0; v < 4; ++v) { Ud[v] += U2[v]; G[v] += G2[v]; }
+            }
         }
 #ifdef MPC_MFMA40_PROF
         asm volatile("" :: "v"(Ud[0]), "v"(G[0]));
@@ -2245,42 +2293,42 @@ MPC_DEV void rollout_priced(const P &p, const Lane &L, const float *Kin, const f
         // ---- x+ = F tau' + f   (:216-222)  and  Quu e
         f32x4 H = zero4;
         if (t < T - 1) {
-            f32x4 acc[2];
-            float fa[2][12];
+            f32x4 acc[XT];
+            float fa[XT][4 * XT + 4];
 #pragma unroll
-            for (int Im = 0; Im < 2; ++Im) {
+            for (int Im = 0; Im < XT; ++Im) {
                 acc[Im] = zero4;
-                if (p.f) acc[Im] = wv::lds_f32x4(rec + 320 + 4u * (unsigned)(16 * Im + 4 * L.q));
+                if (p.f) acc[Im] = wv::lds_f32x4(rec + 4 * RW_F + 4u * (unsigned)(16 * Im + 4 * L.q));
                 const int row = 16 * Im + L.r;
 #pragma unroll
-                for (int J = 0; J < 2; ++J) {    // (rows of F are 160 B: every such quadruple is 16-byte aligned)
+                for (int J = 0; J < XT; ++J) {   // (rows of F are 160 B: every such quadruple is 16-byte aligned)
                     const f32x4 x = wv::lds_f32x4(base + POFF_F + 4u * (unsigned)(row * N + 16 * J + 4 * L.q));
 #pragma unroll
                     for (int i = 0; i < 4; ++i) fa[Im][4 * J + i] = x[i];
                 }
 #pragma unroll
                 for (int h = 0; h < 2; ++h)        // the control columns as two full-k operands (uctl)
-                    fa[Im][8 + h] = wv::lds_f32(base + POFF_F + 4u * (unsigned)(row * N + 32 + uctl(L.q) + 2 * h));
+                    fa[Im][4 * XT + h] = wv::lds_f32(base + POFF_F + 4u * (unsigned)(row * N + NS + uctl(L.q) + 2 * h));
             }
             wv::sched_fence();
 #pragma unroll
             for (int h = 0; h < 2; ++h) H = wv::mfma(aq[h], wv::lower_halves(e[2 * h], e[2 * h + 1]), H);
 #pragma unroll
-            for (int k = 0; k < 8; ++k)
+            for (int k = 0; k < 4 * XT; ++k)
 #pragma unroll
-                for (int Im = 0; Im < 2; ++Im) acc[Im] = wv::mfma(fa[Im][k], Xd[k >> 2][k & 3], acc[Im]);
+                for (int Im = 0; Im < XT; ++Im) acc[Im] = wv::mfma(fa[Im][k], Xd[k >> 2][k & 3], acc[Im]);
 #pragma unroll
             for (int h = 0; h < 2; ++h) {
                 const float up = wv::lower_halves(Ud[2 * h], Ud[2 * h + 1]);
 #pragma unroll
-                for (int Im = 0; Im < 2; ++Im) acc[Im] = wv::mfma(fa[Im][8 + h], up, acc[Im]);
+                for (int Im = 0; Im < XT; ++Im) acc[Im] = wv::mfma(fa[Im][4 * XT + h], up, acc[Im]);
             }
             wv::sched_fence();
 #pragma unroll
-            for (int Im = 0; Im < 2; ++Im) {
+            for (int Im = 0; Im < XT; ++Im) {
                 if (PADK && L.r == 0) st_x4(p, (long)(t + 1) * p.B + L.b, 16 * Im + 4 * L.q, acc[Im]);
                 else if (store) wv::store_f32x4(xo + (long)(t + 1) * xst + 16 * Im + 4 * L.q, acc[Im]);
-                const f32x4 xb = wv::lds_f32x4(rec + 160 + 4u * (unsigned)(16 * Im + 4 * L.q));
+                const f32x4 xb = wv::lds_f32x4(rec + 4 * RW_X + 4u * (unsigned)(16 * Im + 4 * L.q));
                 Xd[Im] = acc[Im];
 #pragma unroll
                 for (int v = 0; v < 4; ++v) DXd[Im][v] = acc[Im][v] - xb[v];
@@ -2292,7 +2340,7 @@ MPC_DEV void rollout_priced(const P &p, const Lane &L, const float *Kin, const f
             wv::sched_fence();
         }
 #ifdef MPC_MFMA40_PROF
-        asm volatile("" :: "v"(DXd[0][0]), "v"(DXd[1][0]), "v"(H[0]));
+        asm volatile("" :: "v"(DXd[0][0]), "v"(DXd[XT - 1][0]), "v"(H[0]));
         PROF40_MARK(13);
 #endif
         // (G was formed with the dx this timestep STARTED from: DXd above is already the next one's)
@@ -2417,7 +2465,7 @@ MPC_DEV void kstage_issue(const P &p, const RStream &d, const char *v_ptr, long 
     // (padded instantiation: the caller's F by the rollout's gather; K, the record and V are the workspace's own padded layout)
     if (PADK) gather_F(d.g, p.T > 1 ? d.Fb + tf * p.F_st : d.Cb, p.T > 1 ? d.g.fbytes : 0u, base + KOFF_F);
     else dma_kib<5>(d.f_ptr + tf * d.f_step + d.lo, base + KOFF_F);
-    wv::dma16(d.k_ptr + tl * d.k_step + d.lo, base + KOFF_K);
+    dma_gain((int)(d.lo >> 4), d.k_ptr + tl * d.k_step + d.lo, base + KOFF_K);
     wv::dma16_if(d.r_active, d.r_ptr + rec_off(d.r_is_x ? tx : tl, d.r_step), base + KOFF_R);
     if (PADK) {
         // u*_t | u_lower_t | u_upper_t (tensor bounds; u* again otherwise: the instruction count of a stage is fixed), lane a < n_ctrl
@@ -2436,9 +2484,10 @@ MPC_DEV void kstage_issue(const P &p, const RStream &d, const char *v_ptr, long 
     {
         // tiles (0,0), (1,0), (1,1): KiB 0, 2, 3 of the record (the slot keeps its 4 KiB; KiB 1 is never written nor read)
         const char *vp = v_ptr + tx * v_step + d.lo;
+        // (one state tile: V is tile (0,0) alone -- fetched three times over, the stage's instruction count is KDMA_PER_STAGE at every XT)
         wv::dma16_at<0>(vp, base + KOFF_V);
-        wv::dma16_at<2048>(vp, base + KOFF_V);
-        wv::dma16_at<3072>(vp, base + KOFF_V);
+        wv::dma16_at<(XT > 1 ? 2048 : 0)>(vp, base + KOFF_V);
+        wv::dma16_at<(XT > 1 ? 3072 : 0)>(vp, base + KOFF_V);
     }
 #endif
 }
@@ -2498,17 +2547,19 @@ MPC_DEV void kkt_pass2(const P &p, const Lane &L, const float *Kin, const float 
         for (int i = 0; i < win; ++i) wa *= p.ls_decay;
         if (L.q == 0) {
 #pragma unroll
-            for (int J = 0; J < 2; ++J)
+            for (int J = 0; J < XT; ++J)
                 if (!PADK || 16 * J + L.r < ns_o) kx.dx_init[(long)L.b * ns_o + 16 * J + L.r] = -fmaf(1.f - wa, v0g0[2 + J], v0g0[J]);
         }
     }
-    f32x4 Xd[2];                     // dx_t, D layout: column r = trial r (dx_0 = 0: the nested x_init, :327, 338)
+    f32x4 Xd[XT];                    // dx_t, D layout: column r = trial r (dx_0 = 0: the nested x_init, :327, 338)
     Xd[0] = zero4;
-    Xd[1] = zero4;
-    f32x4 pU = zero4, pDL[2] = {zero4, zero4};     // du_{t-1}, dlambda_t: stored one timestep late (below)
+    if (XT > 1) Xd[XT - 1] = zero4;
+    f32x4 pU = zero4, pDL[XT];       // du_{t-1}, dlambda_t: stored one timestep late (below)
+    pDL[0] = zero4;
+    if (XT > 1) pDL[XT - 1] = zero4;
     if (store) {
 #pragma unroll
-        for (int I = 0; I < 2; ++I) st_x4(p, L.b, 16 * I + 4 * L.q, zero4);
+        for (int I = 0; I < XT; ++I) st_x4(p, L.b, 16 * I + 4 * L.q, zero4);
     }
     wv::dma_wait<0>();          // nothing of the sweep may still land in the ring
 #pragma unroll
@@ -2520,50 +2571,52 @@ MPC_DEV void kkt_pass2(const P &p, const Lane &L, const float *Kin, const float 
         const unsigned rec = base + KOFF_R;
         // ---- du = K dx + alpha k   (:192 around the zero nominal)
         f32x4 Ud = zero4;
-        float a[8];
+        float a[4 * XT];
 #pragma unroll
-        for (int J = 0; J < 2; ++J) {        // four consecutive words of K's row r per lane and state tile: one 16-byte LDS read
+        for (int J = 0; J < XT; ++J) {       // four consecutive words of K's row r per lane and state tile: one 16-byte LDS read
             const f32x4 x = wv::lds_f32x4(base + KOFF_K + 4u * (unsigned)((L.r < NC ? L.r : 0) * NS + 16 * J + 4 * L.q));
 #pragma unroll
             for (int i = 0; i < 4; ++i) a[4 * J + i] = L.r < NC ? x[i] : 0.f;
         }
         const unsigned qo = 16u * (unsigned)(L.q < 2 ? L.q : 0);
-        const f32x4 kb = wv::lds_f32x4(rec + 448 + qo);
+        const f32x4 kb = wv::lds_f32x4(rec + 448 + qo);          // (this pass's record keeps the 32/8 lanes at every XT: see kkt_store_vvg)
         // every operand of this timestep out of its stage first (F's rows as A operands, V_{t+1}'s tiles, v and g), then the
         // matrix-core blocks undivided
-        float fa[2][12];
+        float fa[XT][4 * XT + 4];
 #pragma unroll
-        for (int Im = 0; Im < 2; ++Im) {
+        for (int Im = 0; Im < XT; ++Im) {
             const int row = 16 * Im + L.r;
 #pragma unroll
-            for (int J = 0; J < 2; ++J) {    // (rows of F are 160 B: every such quadruple is 16-byte aligned)
+            for (int J = 0; J < XT; ++J) {   // (rows of F are 160 B: every such quadruple is 16-byte aligned)
                 const f32x4 x = wv::lds_f32x4(base + KOFF_F + 4u * (unsigned)(row * N + 16 * J + 4 * L.q));
 #pragma unroll
                 for (int i = 0; i < 4; ++i) fa[Im][4 * J + i] = x[i];
             }
 #pragma unroll
             for (int h = 0; h < 2; ++h)        // the control columns as two full-k operands (uctl)
-                fa[Im][8 + h] = wv::lds_f32(base + KOFF_F + 4u * (unsigned)(row * N + 32 + uctl(L.q) + 2 * h));
+                fa[Im][4 * XT + h] = wv::lds_f32(base + KOFF_F + 4u * (unsigned)(row * N + NS + uctl(L.q) + 2 * h));
         }
-        f32x4 Vt[2][2];
+        f32x4 Vt[XT][XT];
 #pragma unroll
-        for (int I = 0; I < 2; ++I)
+        for (int I = 0; I < XT; ++I)
 #pragma unroll
-            for (int J = 0; J < 2; ++J) {
+            for (int J = 0; J < XT; ++J) {
 #ifndef MPC_KF40_VFULL
                 if (I == 0 && J == 1) continue;
 #endif
-                Vt[I][J] = wv::lds_f32x4(base + KOFF_V + 1024u * (unsigned)(2 * I + J) + 16u * (unsigned)L.lane);
+                Vt[I][J] = wv::lds_f32x4(base + KOFF_V + 1024u * (unsigned)(XT * I + J) + 16u * (unsigned)L.lane);
             }
 #ifndef MPC_KF40_VFULL
         // tile (0,1), register v of lane (q,r) = V[4q+v][16+r] = V[16+r][4q+v] = register r & 3 of lane (r >> 2, 4q + v) of tile (1,0)
+        if (XT > 1) {
 #pragma unroll
-        for (int v = 0; v < 4; ++v)
-            Vt[0][1][v] = wv::lds_f32(base + KOFF_V + 2048u + 16u * (unsigned)(16 * (L.r >> 2) + 4 * L.q + v) + 4u * (unsigned)(L.r & 3));
+            for (int v = 0; v < 4; ++v)
+                Vt[0][XT - 1][v] = wv::lds_f32(base + KOFF_V + 2048u + 16u * (unsigned)(16 * (L.r >> 2) + 4 * L.q + v) + 4u * (unsigned)(L.r & 3));
+        }
 #endif
-        f32x4 DL[2];
+        f32x4 DL[XT];
 #pragma unroll
-        for (int Im = 0; Im < 2; ++Im) {
+        for (int Im = 0; Im < XT; ++Im) {
             const f32x4 v1 = wv::lds_f32x4(rec + 160 + 4u * (unsigned)(16 * Im + 4 * L.q));
             const f32x4 g1 = wv::lds_f32x4(rec + 320 + 4u * (unsigned)(16 * Im + 4 * L.q));
 #pragma unroll
@@ -2580,7 +2633,7 @@ MPC_DEV void kkt_pass2(const P &p, const Lane &L, const float *Kin, const float 
             const long tbp = tb - p.B;
             if (L.q < 2) st_u4(p, tbp, 4 * L.q, pU);
 #pragma unroll
-            for (int Im = 0; Im < 2; ++Im) {
+            for (int Im = 0; Im < XT; ++Im) {
                 st_x4(p, tb, 16 * Im + 4 * L.q, Xd[Im]);
                 st_row4(kx.dF + tbp * (long)dfb + ns_o, ns_o, 16 * Im + 4 * L.q, pDL[Im]);
                 if (kx.df) st_row4(kx.df + tbp * ns_o, ns_o, 16 * Im + 4 * L.q, f32x4{-pDL[Im][0], -pDL[Im][1], -pDL[Im][2], -pDL[Im][3]});   // :397-400
@@ -2592,11 +2645,13 @@ MPC_DEV void kkt_pass2(const P &p, const Lane &L, const float *Kin, const float 
 #pragma unroll
             for (int k = 0; k < 4; ++k) {
                 Ud = wv::mfma(a[k], Xd[0][k], Ud);
-                U2 = wv::mfma(a[4 + k], Xd[1][k], U2);
+                if (XT > 1) U2 = wv::mfma(a[4 * (XT - 1) + k], Xd[XT - 1][k], U2);
             }
             wv::sched_fence();
+            if (XT > 1) {
 #pragma unroll
-            for (int v = 0; v < 4; ++v) Ud[v] += U2[v];
+                for (int v = 0; v < 4; ++v) Ud[v] += U2[v];
+            }
         }
         {
             unsigned zw = 0u;                    // the pinned flags of controls 4q .. 4q+3
@@ -2620,30 +2675,32 @@ MPC_DEV void kkt_pass2(const P &p, const Lane &L, const float *Kin, const float 
         }
         // ---- dx_{t+1} = F dtau   (f = None, :333), dlambda_{t+1} = V_{t+1} dx_{t+1} + v_{t+1} + (1 - alpha) g_{t+1}
         if (t < T - 1) {
-            f32x4 acc[2] = {zero4, zero4};
+            f32x4 acc[XT];
+            acc[0] = zero4;
+            if (XT > 1) acc[XT - 1] = zero4;
             wv::sched_fence();
 #pragma unroll
-            for (int k = 0; k < 8; ++k)
+            for (int k = 0; k < 4 * XT; ++k)
 #pragma unroll
-                for (int Im = 0; Im < 2; ++Im) acc[Im] = wv::mfma(fa[Im][k], Xd[k >> 2][k & 3], acc[Im]);
+                for (int Im = 0; Im < XT; ++Im) acc[Im] = wv::mfma(fa[Im][k], Xd[k >> 2][k & 3], acc[Im]);
 #pragma unroll
             for (int h = 0; h < 2; ++h) {
                 const float up = wv::lower_halves(Ud[2 * h], Ud[2 * h + 1]);
 #pragma unroll
-                for (int Im = 0; Im < 2; ++Im) acc[Im] = wv::mfma(fa[Im][8 + h], up, acc[Im]);
+                for (int Im = 0; Im < XT; ++Im) acc[Im] = wv::mfma(fa[Im][4 * XT + h], up, acc[Im]);
             }
             // (A operand = V through its symmetry: register v of tile (I', Im), exactly as Y = V F in the sweep)
 #pragma unroll
-            for (int Ip = 0; Ip < 2; ++Ip)
+            for (int Ip = 0; Ip < XT; ++Ip)
 #pragma unroll
                 for (int v = 0; v < 4; ++v)
 #pragma unroll
-                    for (int Im = 0; Im < 2; ++Im) DL[Im] = wv::mfma(Vt[Ip][Im][v], acc[Ip][v], DL[Im]);
+                    for (int Im = 0; Im < XT; ++Im) DL[Im] = wv::mfma(Vt[Ip][Im][v], acc[Ip][v], DL[Im]);
             wv::sched_fence();
             Xd[0] = acc[0];
-            Xd[1] = acc[1];
+            if (XT > 1) Xd[XT - 1] = acc[XT - 1];
             pDL[0] = DL[0];
-            pDL[1] = DL[1];
+            if (XT > 1) pDL[XT - 1] = DL[XT - 1];
         }
     }
     if (store && L.q < 2) st_u4(p, (long)(T - 1) * p.B + L.b, 4 * L.q, pU);

@@ -18,6 +18,7 @@ MPC_F32, MPC_F64 = 0, 1
 BOUND_NONE, BOUND_SCALAR, BOUND_TENSOR = 0, 1, 2
 ST_PNQP_UNCONVERGED, ST_NONFINITE, ST_NOMINAL_OFF_DYNAMICS, ST_C_ASYMMETRIC, ST_QUU_SINGULAR, ST_C_TESTED = 1, 2, 4, 8, 16, 32
 IMPL_AUTO, IMPL_GENERIC, IMPL_MFMA16, IMPL_DPP16, IMPL_TINY, IMPL_MFMA40, IMPL_WAVE1, IMPL_MFMA40_PAD, IMPL_DPP16_PAD = 0, 1, 2, 3, 4, 5, 6, 7, 8
+IMPL_MFMA40_NARROW = 9      # the padded 32/8 kernel on one 16-row state tile (n_state <= 16); forced only, IMPL_AUTO never picks it
 
 ABI_VERSION = 9      # include/mpc_lqr.h: MPC_LQR_ABI_VERSION
 
@@ -1045,7 +1046,7 @@ class HipBackend:
                                     ctypes.byref(out), ws.data_ptr(), nbytes, _stream(dev)), "mpc_mlp_param_grad")
         return grads
 
-    def plan_network_iteration(self, x_init, C, c, net, opts, nominals, scratch=None):
+    def plan_network_iteration(self, x_init, C, c, net, opts, nominals, scratch=None, impl=IMPL_AUTO):
         """One iLQR iteration on an NNDynamics network (mpc/mpc.py:245-306 with dx a module: util.get_traj is the previous
         rollout's own new_x, then MPC.linearize_dynamics(ANALYTIC) :495-512, lqr_backward :52-160, lqr_forward through the
         network :164-261) bound ONCE per solve: three C calls on the stream per iteration -- mpc_mlp_linearize, mpc_lqr_step
@@ -1055,7 +1056,8 @@ class HipBackend:
         sweeps with MPC_OPT_C_SYMMETRIC once the first sweep has reported C symmetric.
         A `net` with `ctrl_carry` (MlpSpec.augmented(): the slew-rate augmentation, x_init / C / c / nominals at n_state + n_ctrl
         states) linearises with mpc_mlp_linearize_carry on `net.inner`, the network itself, with a packed-weights workspace of
-        its own; sweep and rollout are the same calls on the augmented sizes and the augmented spec."""
+        its own; sweep and rollout are the same calls on the augmented sizes and the augmented spec.
+        impl: the kernel of the sweep's mpc_lqr_step (IMPL_AUTO, or a forced one that can stop after its sweep)."""
         dev = _require_device(x_init, C, c, nominals[0][0], nominals[0][1])
         L = load()
         T, B, n = C.shape[0], C.shape[1], C.shape[2]
@@ -1123,7 +1125,7 @@ class HipBackend:
             rp, rout, _, cxp, cup = rolls[j]
             rc = lin_fn(lep, lin_ns, nc, N, cxp, cup, Fp, fp, lwsp, lbytes, st)
             if rc == 0:
-                rc = step_fn(ctypes.byref(sp), ctypes.byref(so_), ctypes.byref(sout), wsp, nbytes, IMPL_AUTO, st)
+                rc = step_fn(ctypes.byref(sp), ctypes.byref(so_), ctypes.byref(sout), wsp, nbytes, impl, st)
             if rc == 0:
                 rc = roll_fn(ctypes.byref(rp), rop, ep, Kp, kp, outs[j]["old_costs"].data_ptr(), ctypes.byref(rout), mwsp, mbytes, st)
             if rc != 0:

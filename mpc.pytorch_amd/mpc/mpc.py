@@ -175,7 +175,7 @@ class MPC(Module):
                  back_eps=1e-7, n_batch=None, linesearch_decay=0.2, max_linesearch_iter=10,
                  exit_unconverged=True, detach_unconverged=True, backprop=True, slew_rate_penalty=None,
                  prev_ctrl=None, not_improved_lim=5, best_cost_eps=1e-4, reference_du_norm=False,
-                 shared_grad_kernel=False, weight_grad_kernel=False, planned_network_slew=False):
+                 narrow_step_kernel=False, shared_grad_kernel=False, weight_grad_kernel=False, planned_network_slew=False):
         super().__init__()
         assert (u_lower is None) == (u_upper is None)
         assert max_linesearch_iter > 0
@@ -214,6 +214,20 @@ class MPC(Module):
         # test_slew_rate_penalty_on_a_wide_network pin the general route by spying on HipBackend.mlp_rollout, a method a pre-bound
         # iteration never goes through (it calls mpc_mlp_rollout itself), and existing tests are the yardstick of every change
         self.planned_network_slew = bool(planned_network_slew)
+        # OPT-IN: the pre-bound loops (`_iterate_planned`, through it `_iterate_slew`, and `_iterate_network`) bind their step plans
+        # with _native.IMPL_MFMA40_NARROW -- the padded 32/8 kernel on one 16-row state tile -- instead of IMPL_AUTO.  The
+        # criterion (`_narrow_impl_kw`), at the sizes the loop runs at (n_state + n_ctrl states on the slew route: 12/4 becomes
+        # 16/4): the backend's `impl_supported` takes them for impl 9 AND does not take them for IMPL_DPP16_PAD -- shapes up to
+        # 12/4 have faster kernels of their own and stay auto's.  Everywhere else IMPL_AUTO, as ever.
+        # A forced kernel reads C through its symmetry and only FLAGS a C that is not symmetric, where impl 0 solves such a
+        # problem again: a narrow-bound loop whose first step reports the bit starts over on IMPL_AUTO plans (`_drive`), so x, u
+        # and costs are the flag-off solve's for every C.  The price: iteration 1 is launched after the flags of iteration 0 are
+        # in, not before.
+        # Off by default: the kernel auto picks for these shapes is pinned by existing tests
+        # (tests/golden/step_route_expect.json, tests/test_gpu_step_route.py), which are the yardstick of every change, and the
+        # narrow kernel's time against the padded one is a measurement of docs/history/r16.md, not a promise.  The
+        # differentiable ending and the KKT backward do not look at the flag
+        self.narrow_step_kernel = bool(narrow_step_kernel)
         # OPT-IN: a QuadCost / LinDx given in batch-shared form (C [T,n,n] or [n,n], c [T,n] or [n], F [T-1,ns,n] or [ns,n], f
         # likewise) reaches the final no-op step UN-expanded, whose backward then sums the gradients over the batch inside the
         # kernels (lqr_step._LQRStepSharedFn, mpc_lqr_kkt_grads_shared) instead of writing one [n,n] block per problem for
@@ -382,22 +396,29 @@ class MPC(Module):
             # every nominal of this loop obeys (F, f) by construction: get_traj above, then each step's own rollout
             opts.nominal_on_dynamics = True
         xb, ub = torch.empty_like(xa), torch.empty_like(ua)
-        pa = be.plan_step(xi, cost.C, cost.c, F, f, xa, ua, opts, out_x=xb, out_u=ub)
-        r = pa()                  # the first step is on its way before anything else of the loop is set up (host time hidden)
+        # (`narrow_step_kernel`: the forced kernel rides in the plan; its variants below keep it)
+        kwi = self._narrow_impl_kw(be, xi.shape[1], ua.shape[2], xi.dtype, opts)
         variant = getattr(be, "plan_variant", None)      # (the test backends build every plan from scratch)
-        if variant is not None:
-            pb = variant(pa, cur_x=xb, cur_u=ub, out_x=xa, out_u=ua)
-        else:
-            pb = be.plan_step(xi, cost.C, cost.c, F, f, xb, ub, opts, out_x=xa, out_u=ua)
-        plans = (pa, pb)
+        # the raw stream handle, looked up once (torch.cuda.current_stream costs 4 us a call, two calls an iteration)
+        stream = torch.cuda.current_stream(xa.device).cuda_stream if xa.is_cuda and variant is not None else None
+        plans = [None, None]
+
+        def bind(kw):
+            """the two ping-pong plans with the impl of `kw`; iteration 0 launched in between -> its outputs"""
+            plans[0] = be.plan_step(xi, cost.C, cost.c, F, f, xa, ua, opts, out_x=xb, out_u=ub, **kw)
+            # the first step is on its way before anything else of the loop is set up (host time hidden)
+            r0 = plans[0]() if stream is None else plans[0](stream)
+            if variant is not None:
+                plans[1] = variant(plans[0], cur_x=xb, cur_u=ub, out_x=xa, out_u=ua)
+            else:
+                plans[1] = be.plan_step(xi, cost.C, cost.c, F, f, xb, ub, opts, out_x=xa, out_u=ua, **kw)
+            return r0, ((plans[0].outputs, plans[1].outputs) if variant is not None else None)
+        r, outputs = bind(kwi)
         # C does not change during the solve: once the first step has reported that it is symmetric (no
         # MPC_ST_C_ASYMMETRIC in its status, read back with the convergence flags), the remaining steps run with the
         # promise MPC_OPT_C_SYMMETRIC -- no symmetry test in the kernel, no gated second launch behind it
         self._c_symmetric = False
         sym_plans = None
-
-        # the raw stream handle, looked up once (torch.cuda.current_stream costs 4 us a call, two calls an iteration)
-        stream = torch.cuda.current_stream(xa.device).cuda_stream if xa.is_cuda and variant is not None else None
 
         def launch(i):
             plan = (sym_plans if sym_plans is not None else plans)[i % 2]
@@ -412,11 +433,27 @@ class MPC(Module):
                 so = copy.copy(opts)
                 so.c_symmetric = True
                 if variant is not None:          # the same structs with one more option bit: no walk, no allocation
-                    sym_plans = (variant(pa, opts=so), variant(pb, opts=so))
+                    sym_plans = (variant(plans[0], opts=so), variant(plans[1], opts=so))
                 else:
-                    sym_plans = (be.plan_step(xi, cost.C, cost.c, F, f, xa, ua, so, out_x=xb, out_u=ub),
-                                 be.plan_step(xi, cost.C, cost.c, F, f, xb, ub, so, out_x=xa, out_u=ua))
-        return self._drive(be, launch, (pa.outputs, pb.outputs) if variant is not None else None, r, xa, ua, n_batch, stream, on_symmetric)
+                    sym_plans = (be.plan_step(xi, cost.C, cost.c, F, f, xa, ua, so, out_x=xb, out_u=ub, **kwi),
+                                 be.plan_step(xi, cost.C, cost.c, F, f, xb, ub, so, out_x=xa, out_u=ua, **kwi))
+        # A FORCED kernel reads C through its symmetry and only flags a problem whose C is not symmetric; it is impl 0 that solves
+        # such a problem again on the generic kernel inside the call (include/mpc_lqr.h, MPC_ST_C_ASYMMETRIC).  So a loop bound to
+        # the narrow kernel whose first step reports the bit starts over on IMPL_AUTO plans: the nominal of iteration 0 is still
+        # in (xa, ua) -- `_drive` holds iteration 1 back until the flags are in -- and the solve is the flag-off solve from there on
+        return self._drive(be, launch, outputs, r, xa, ua, n_batch, stream, on_symmetric,
+                           on_asymmetric=(lambda: bind({})) if kwi else None)
+
+    def _narrow_impl_kw(self, be, ns, nc, dtype, opts):
+        """`narrow_step_kernel`: dict(impl=IMPL_MFMA40_NARROW) where the backend's narrow kernel takes a step of these sizes and
+        options, else {} -- the plan is bound as ever, with IMPL_AUTO."""
+        if (self.narrow_step_kernel and hasattr(be, "impl_supported")
+                and be.impl_supported(int(ns), int(nc), dtype, _native.IMPL_MFMA40_NARROW, opts)
+                # (up to 12/4 the 4-problems-per-wave kernels are auto's choice and stay it: the narrow kernel is for the shapes
+                # auto gives to the padded 32/8 kernel)
+                and not be.impl_supported(int(ns), int(nc), dtype, _native.IMPL_DPP16_PAD, opts)):
+            return dict(impl=_native.IMPL_MFMA40_NARROW)
+        return {}
 
     def _slew_plan(self, cost, dx, be, x_init):
         """Does this slew-rate solve run on the device-side loop (`_iterate_slew`)?  None = no: `_iterate_general`, as before
@@ -479,7 +516,7 @@ class MPC(Module):
         best["x"] = best["x"][:, :, nc:].contiguous()
         return best
 
-    def _drive(self, be, launch, outputs, r, xa, ua, n_batch, stream, on_symmetric):
+    def _drive(self, be, launch, outputs, r, xa, ua, n_batch, stream, on_symmetric, on_asymmetric=None):
         """The loop of mpc/mpc.py:245-306 around pre-bound iterations: launch(i) enqueues iteration i and returns its output
         dict (`outputs`: the two dicts the iterations alternate between, for the pre-bound select call; None = the test
         backends' general entry), `r` = the outputs of iteration 0, already on its way.  Best-iterate tracking on the device
@@ -489,9 +526,11 @@ class MPC(Module):
                     full_du_norm=torch.empty(n_batch, dtype=xa.dtype, device=xa.device))
         reader = _FlagReader(xa.device, xa.dtype, be)
         # (the HIP backend binds the select call's arguments once per solve; the test stand-ins take the general entry)
-        sel = None
-        if reader.direct and hasattr(be, "plan_select") and outputs is not None:
-            sel = be.plan_select(self.best_cost_eps, outputs, best, reader.device_flags, host=reader._host)
+        def bind_select(outs_):
+            if reader.direct and hasattr(be, "plan_select") and outs_ is not None:
+                return be.plan_select(self.best_cost_eps, outs_, best, reader.device_flags, host=reader._host)
+            return None
+        sel = bind_select(outputs)
         n_not_improved, i = 0, 0
         while True:
             # best-iterate tracking, :271-285 -- on the device
@@ -501,8 +540,20 @@ class MPC(Module):
                 be.select_best(i == 0, self.best_cost_eps, r["new_x"], r["new_u"], r["costs"], r["full_du_norm"],
                                best, flags=reader.device_flags, status=r["status"] if i == 0 else None, **reader.select_kw())
             reader.start()
-            nxt = launch(i + 1) if i + 1 < self.lqr_iter else None        # overlaps the read-back
+            # `on_asymmetric` (a loop bound to a FORCED kernel): iteration 1 would overwrite the nominal iteration 0 started from,
+            # which a solve that has to start over still needs -- it waits for the flags of iteration 0, this once
+            hold = i == 0 and on_asymmetric is not None
+            nxt = launch(i + 1) if i + 1 < self.lqr_iter and not hold else None        # overlaps the read-back
             bits, max_du_norm = reader.wait()
+            if hold:
+                if bits & 2:
+                    # the forced kernel met a C that is not symmetric: the plans again on IMPL_AUTO, iteration 0 again
+                    r, outputs = on_asymmetric()
+                    sel, on_asymmetric = bind_select(outputs), None
+                    on_symmetric = lambda: None          # (C is known not to be symmetric: no MPC_OPT_C_SYMMETRIC plans)
+                    continue
+                on_asymmetric = None
+                nxt = launch(i + 1) if i + 1 < self.lqr_iter else None
             any_improved = (bits & 1) != 0
             if i == 0 and not (bits & 2):
                 self._c_symmetric = True
@@ -543,15 +594,24 @@ class MPC(Module):
         else:
             xa = util.get_traj(T, ua, x_init=xi, dynamics=dx).contiguous()
         xb, ub = torch.empty_like(xa), torch.empty_like(ua)
-        run, outs, vouch_c = be.plan_network_iteration(xi, cost.C, cost.c, net, self._step_options(), ((xa, ua), (xb, ub)))
+        nopts = self._step_options()
+        kwi = self._narrow_impl_kw(be, xi.shape[1], ua.shape[2], xi.dtype, nopts)
         stream = torch.cuda.current_stream(xa.device).cuda_stream if xa.is_cuda else None
-        r = run(0, stream)
+        bound = [None, None]
+
+        def bind(kw):
+            bound[0], outs_, bound[1] = be.plan_network_iteration(xi, cost.C, cost.c, net, nopts, ((xa, ua), (xb, ub)), **kw)
+            return bound[0](0, stream), outs_
+        r, outs = bind(kwi)
         self._c_symmetric = False
 
         def on_symmetric():
             if self.lqr_iter > 2:
-                vouch_c()
-        return self._drive(be, lambda i: run(i % 2, stream), outs, r, xa, ua, n_batch, stream, on_symmetric)
+                bound[1]()
+        # (a sweep forced onto the narrow kernel that reports a non-symmetric C: the loop starts over on IMPL_AUTO, see
+        # `_iterate_planned`)
+        return self._drive(be, lambda i: bound[0](i % 2, stream), outs, r, xa, ua, n_batch, stream, on_symmetric,
+                           on_asymmetric=(lambda: bind({})) if kwi else None)
 
     def _iterate_general(self, be, x_init, u, cost, dx):
         """The same loop with module-valued cost / dynamics or a slew penalty: linearisation and cost
