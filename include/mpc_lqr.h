@@ -44,9 +44,29 @@ enum {
 /* per-problem status word bits (status[B]) */
 enum {
     MPC_ST_PNQP_UNCONVERGED = 1,   /* "pnqp warning: Did not converge" (mpc/pnqp.py:81) at some timestep   */
-    MPC_ST_NONFINITE = 2,          /* the returned cost is NaN / inf                                        */
+    MPC_ST_NONFINITE = 2,          /* the returned cost is NaN / inf: set exactly when out->costs of the problem is not finite,
+                                      whatever in the problem's data or nominal made it so; the other problems of the batch are
+                                      not touched.  Tested with non-finite batches on the 12/4, 32/8, one-problem-per-wavefront,
+                                      lane- and row-per-problem kernels (impl 2..9); the generic kernels (impl 1) and the network
+                                      rollout carry the same line, read but NOT tested with such input.  Inputs that are not finite
+                                      and still come back finite and UNFLAGGED: a NaN in a tensor bound (every kernel: a comparison
+                                      with it is false, in the box QP and in the rollout's clamp, so that bound never binds -- the
+                                      reference's util.eclamp does the same); a NaN in current_u under a SCALAR box on the 32/8
+                                      kernels (impl 5, 7, 9: their clamp is max / min, which drop a NaN operand and return the bound,
+                                      where util.eclamp keeps the NaN; a tensor box or delta_u with such a nominal is not tested). */
     MPC_ST_NOMINAL_OFF_DYNAMICS = 4,/* informational (the 12/4 and 32/8 kernels): current_x is not the rollout of current_u
-                                      from x_init, the trajectory cost was evaluated from a second pass over C */
+                                      from x_init -- x_0 = x_init included: current_x[0] != x_init is off the nominal -- and the
+                                      trajectory cost was evaluated from a second pass over C.  By tolerance, 1e-5 (1 + |x|) (the
+                                      comparison is written so that a NaN in current_x fails it; only the 32/8 kernel has a test
+                                      with one).  Set on a call WITHOUT MPC_OPT_NOMINAL_ON_DYNAMICS only:
+                                      by the 12/4 kernels (impl 3, 8) in every mode (unbounded, scalar / tensor box, delta_u,
+                                      zero mask), by the 32/8 kernels (impl 5, 7, 9) in the unconstrained step alone -- their
+                                      constrained bare call prices every trial from C, which needs no premise and reports none.
+                                      The one-problem-per-wavefront kernel (impl 2, float32 and float64), the lane- and
+                                      row-per-problem kernels (impl 4, 6), the generic kernels (impl 1) and the network rollout
+                                      price from C always and never set it.  Flagged or not, every kernel returns the reference's
+                                      trajectory for such a nominal: dx_0 = 0, new_x[0] = x_init (mpc/lqr_step.py:181-182),
+                                      old_costs the cost of the nominal as given (:169).                                      */
     MPC_ST_C_ASYMMETRIC = 8,       /* some C_t of this problem is not symmetric (max |C - C'| > 1e-5 max |C|).  The
                                       reference uses C as given (mpc/lqr_step.py:68 Q = C + F'VF, :294 C tau); the fused
                                       kernels (impl 2..5) read it through its symmetry.  impl = 0 re-solves exactly these

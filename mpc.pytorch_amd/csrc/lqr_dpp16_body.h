@@ -1905,7 +1905,34 @@ MPC_DEV void step_wave(const P &p)
         line_search<MODE, false, true>(p, L, d, wave, G, rs, old_cost, old_cost_d + ss.w0, full2 PROF_PASS);
         // a nominal that does not obey the dynamics voids the identity the pass was priced with: price the
         // rollout the reference's way, from a second stream of C
-        const bool off = wv::row_sum(rs.viol > 0.f ? 1.f : 0.f) > 0.f;
+        bool off = wv::row_sum(rs.viol > 0.f ? 1.f : 0.f) > 0.f;
+        // ... and does it start where the rollout does, x_0 = x_init?  The reference rolls out from x_init with dx_0 = 0 whatever
+        // current_x[0] holds (new_x = [x_init], dx = [zeros_like(x_init)], :181-182); the passes here take dx_0 = x_init - current_x[0],
+        // the same 0 only when the two agree (same tolerance as the dynamics test).  A row that fails is off its nominal like any other
+        // -- bit 4, priced from C below -- and K_0 dx_0 must vanish from that pass: K_0 of the row's record is zeroed (the wave's own
+        // scratch, or the register-resident copy; the caller's out->K was written by the sweep and keeps the gains).  The passes
+        // themselves stay as they are.  The record stays that way after the call: its readers are this kernel's own passes and
+        // mpc_lqr_qp_record, which views lane 12 (k) of every block and none of the K columns zeroed here; the fused backward
+        // runs a sweep of its own.
+        {
+            const long o0 = L.isu ? 0 : (long)(L.out0 - p.new_x);          // (new_x[0] and x_init share their layout)
+            const float xi = p.x_init[o0], n0 = p.cur_x[o0];
+            float r = fabsf(xi - n0) - 1e-5f * (1.f + fabsf(n0));
+            r = (r == r) ? r : 1.f;
+            const bool mine = !L.isu && (!PADK || L.ovalid) && r > 0.f;
+            const bool off0 = wv::row_sum(mine ? 1.f : 0.f) > 0.f;
+            if (wv::any(off0)) {
+                const f32x4 zero4 = {0.f, 0.f, 0.f, 0.f};
+                if (rgm(MODE)) {
+                    const f32x4 g = gain_get(G, 0);
+                    gain_put(G, 0, (off0 && L.j < 12) ? zero4 : g);
+                } else {
+                    if (off0 && L.j < 12) wv::store_f32x4(p.Kk + (long)L.pb * 64 + 4 * L.j, zero4);
+                    wv::fence_own_stores();
+                }
+            }
+            off = off || off0;
+        }
         // (round 5) ... and so is a problem one of whose box QPs did not converge -- in practice a Quu that is not positive definite:
         // V then grows to 1e5 times the cost, J_nominal + w0 is what is left of two float32 sums that size, and the identity's price
         // was seen 3 % off the cost of the very trajectory it belongs to (a positive definite problem: 1e-7).  The call that makes

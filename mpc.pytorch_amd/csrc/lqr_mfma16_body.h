@@ -603,7 +603,8 @@ MPC_DEV void rollout_step(const P &p, const Lane &L, const RoStage &s, RoState &
     // new_u = K dx + u + alpha k   (mpc/lqr_step.py:192)
     rx4 Uacc = zero4;
 #pragma unroll
-    for (int kb = 1; kb < 4; ++kb) Uacc = wv::mfma(s.KA[kb - 1], st.xrow[kb - 1] - s.xbar[kb - 1], Uacc);
+    // (dx_0 = 0 whatever current_x[0] is: the reference starts its pass from dx = [zeros_like(x_init)], :182)
+    for (int kb = 1; kb < 4; ++kb) Uacc = wv::mfma(s.KA[kb - 1], t == 0 ? (real)0 : st.xrow[kb - 1] - s.xbar[kb - 1], Uacc);
     // x_{t+1} = F [x;u] + f  (:216-222): the x part does not wait for u
     rx4 Xacc = zero4;
     Xacc[1] = s.frow[0]; Xacc[2] = s.frow[1]; Xacc[3] = s.frow[2];

@@ -101,18 +101,23 @@ MPC_DEV int pnqp1_fast(float H, float q, float lb, float ub, float &x, float &Hf
     const float dx1 = -((fr1 ? g1 : 0.f) * env_inv(Hf1));
     const bool done1 = !(tiny::absr<float>(dx1) >= 1e-4f);
     const bool simple = n_iter >= 2 && H > 0 && (done0 || ((inside || arm > 0.1f) && done1));
-    int ret;
-    if (wv::any(!simple)) {                                        // (wavefront-uniform and rare: the loop, for everybody)
+    // (wavefront-uniform and rare: the loop runs for everybody, and only the lanes that need it take its answer.  The two forms
+    // agree to rounding, not to the bit once the compiler contracts them differently: a problem's result must not depend on
+    // whether one of the three problems that share its wavefront -- a non-finite one, say -- sent the wavefront through the loop.)
+    float xl = x, Hfl = Hfree;
+    bool isfl = is_free, convl = conv;
+    int retl = 0;
+    if (wv::any(!simple)) {
         MPC_STAT(14);
-        ret = tiny::pnqp1<float>(H, q, lb, ub, x, Hfree, is_free, n_iter, conv);
+        retl = tiny::pnqp1<float>(H, q, lb, ub, xl, Hfl, isfl, n_iter, convl);
     } else {
         MPC_STAT(15);
-        ret = done0 ? 0 : 1;
-        x = done0 ? x0 : x1;
-        is_free = done0 ? fr0 : fr1;
-        Hfree = done0 ? Hf0 : Hf1;
-        conv = true;
     }
+    const int ret = simple ? (done0 ? 0 : 1) : retl;
+    x = simple ? (done0 ? x0 : x1) : xl;
+    is_free = simple ? (done0 ? fr0 : fr1) : isfl;
+    Hfree = simple ? (done0 ? Hf0 : Hf1) : Hfl;
+    conv = simple ? true : convl;
     return ret;
 }
 

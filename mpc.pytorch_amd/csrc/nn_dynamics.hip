@@ -244,7 +244,8 @@ __device__ __forceinline__ void rollout_tiles(StepParams<float> p, MlpDesc m, in
                     const float *Kr = p.K + (tb * nc + i) * ns;
                     float s = 0.f;
                     for (int j = 0; j < ns; ++j) s = fmaf(Kr[j], dxS[r * TS + j], s);
-                    un = s + u + alpha * p.k[tb * nc + i];                                  // :192
+                    // (dx_0 = 0 whatever current_x[0] is, :182; dxS keeps tau' - tau_nominal for the cost difference below)
+                    un = (t == 0 ? 0.f : s) + u + alpha * p.k[tb * nc + i];                 // :192
                     if (p.zero_mask && p.zero_mask[tb * nc + i]) un = 0.f;                  // :197-198
                     if (p.bound_mode != MPC_BOUND_NONE) {                                   // :200-213
                         float lo = p.bound_mode == MPC_BOUND_SCALAR ? p.lo_s : p.lo[tb * nc + i];
@@ -814,7 +815,8 @@ __global__ void __launch_bounds__(64) nn_rollout_fast_kernel(StepParams<float> p
                         s0 = fmaf(o.Kr[g][2], d[2], s0);
                         s1 = fmaf(o.Kr[g][3], d[3], s1);
                     }
-                    un = (s0 + s1) + uq + alpha * o.kq;                                     // :192
+                    // (dx_0 = 0 whatever current_x[0] is, :182; dxS keeps tau' - tau_nominal for the cost difference below)
+                    un = (t == 0 ? 0.f : s0 + s1) + uq + alpha * o.kq;                      // :192
                     if (p.zero_mask && p.zero_mask[tb * nc + q]) un = 0.f;                  // :197-198
                     if (p.bound_mode != MPC_BOUND_NONE) {                                   // :200-213
                         float lo = p.bound_mode == MPC_BOUND_SCALAR ? p.lo_s : p.lo[tb * nc + q];
