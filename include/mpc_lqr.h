@@ -273,6 +273,14 @@ int mpc_lqr_kkt_grads(const mpc_lqr_problem *p, /* C,c,F (+strides); cur_x/cur_u
                       const void *dx, const void *du, const void *dl_dx, const void *dl_du,
                       void *dC, void *dc, void *dF, void *df, void *dx_init, void *stream);
 
+/* (ABI 9, additive) Which of its kernels (4) would launch for exactly these arguments, nothing launched: the 4-problems-per-wave
+ * kernel (float32, 12/4, every block and dx, du, dl_dx, dC, dF on 16 bytes), the wavefront-per-problem kernels (float32, n_state +
+ * n_ctrl <= 64) or the generic kernel (everything else, float64 always).  The argument checks of (4): where that call is refused, its
+ * negative code with the same text in mpc_lqr_last_error().  0: B = 0.  No pointer is dereferenced: no device is needed to ask. */
+enum { MPC_KKT_GRADS_DPP16 = 1, MPC_KKT_GRADS_WAVE = 2, MPC_KKT_GRADS_GENERIC = 3 };
+int mpc_lqr_kkt_grads_route(const mpc_lqr_problem *p, const void *dx, const void *du, const void *dl_dx, const void *dl_du,
+                            const void *dC, const void *dc, const void *dF, const void *df, const void *dx_init);
+
 /* (4b) r -> -r packing and the active-bound mask of mpc/lqr_step.py:316-326:
  *     negr [T,B,n] = -[dl_dx; dl_du];  mask [T,B,nc] = |u*-lo|<=1e-8 | |u*-hi|<=1e-8
  *     (mask may be NULL when unbounded). */
@@ -300,6 +308,18 @@ int64_t mpc_lqr_kkt_fused_workspace_bytes(const mpc_lqr_problem *p);
 int mpc_lqr_kkt_fused(const mpc_lqr_problem *p, const mpc_lqr_options *o, const void *dl_dx, const void *dl_du,
                       void *dC, void *dc, void *dF, void *df, void *dx_init, void *dx_out, void *du_out, int32_t *status,
                       void *workspace, int64_t workspace_bytes, void *stream);
+
+/* (ABI 9, additive) Which fused kernel (4c) would launch for exactly these arguments, nothing launched.  They are tried in this order:
+ * exact 12/4, its padded instantiation; beyond 12/4 exact 32/8, the padded instantiation with 16-byte gathers (n_state, n_ctrl
+ * multiples of 4, C and F on 16 bytes), the one with dword gathers.  MPC_KKT_NONE (0): the call is legal but no fused kernel takes
+ * these sizes, this dtype, these flags or exactly these views -- where (4c) fails with MPC_E_DIMS and the three calls (4b), (1), (4)
+ * are the way -- or B = 0.  Negative: what (4c) refuses for any other reason (a NULL argument, df without f, a short or NULL
+ * workspace, bad sizes or options), its code, with the same text in mpc_lqr_last_error().  Every pointer is inspected for NULL and
+ * alignment only, never dereferenced: no device is needed to ask. */
+enum { MPC_KKT_NONE = 0, MPC_KKT_DPP16 = 1, MPC_KKT_DPP16_PAD = 2, MPC_KKT_MFMA40 = 3, MPC_KKT_MFMA40_PAD16 = 4, MPC_KKT_MFMA40_PAD4 = 5 };
+int mpc_lqr_kkt_fused_route(const mpc_lqr_problem *p, const mpc_lqr_options *o, const void *dl_dx, const void *dl_du,
+                            const void *dC, const void *dc, const void *dF, const void *df, const void *dx_init, const void *dx_out,
+                            const void *du_out, const int32_t *status, const void *workspace, int64_t workspace_bytes);
 
 /* (4d) The closed-form part (4) for a cost and a linear model that the whole batch SHARES -- C [T,n,n] or [n,n], c, F, f
  *     likewise, handed to the kernels as stride-0 views: the gradient of a shared tensor is the SUM over the batch of (4)'s

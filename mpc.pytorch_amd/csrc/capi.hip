@@ -1,5 +1,6 @@
 // capi.hip -- extern "C" entry points of libmpc_lqr_hip.so (declared in include/mpc_lqr.h).
 // Argument validation + dtype / kernel dispatch; no computation happens on the host.
+#include <algorithm>
 #include <cmath>
 #include <cstdio>
 #include <cstdlib>
@@ -532,6 +533,135 @@ static int route_query(const mpc_lqr_problem *p, const mpc_lqr_options *o, const
     if (ring) *ring = r.ring;
     return r.kernel;
 }
+
+// ---------------------------------------------------------------------------------------------------------------------
+// The kernels behind the KKT backward (MPC_KKT_*, MPC_KKT_GRADS_*, include/mpc_lqr.h): what each one takes, the workspace it lives
+// in, and -- kkt_fused_route, kkt_grads_route -- which of them takes a call.  mpc_lqr_kkt_fused, its two queries and
+// mpc_lqr_kkt_fused_route, mpc_lqr_kkt_grads and mpc_lqr_kkt_grads_route all ask here.
+// ---------------------------------------------------------------------------------------------------------------------
+
+// Does fused kernel `kernel` take this call, by its own rule (lqr_dpp16.hip, lqr_mfma40.hip)?  query: the form
+// mpc_lqr_kkt_fused_supported asks -- sizes, dtype (the caller's: these kernels are float32) and flags; the rules are then asked
+// with no tensors, so every block counts as aligned.
+static bool kkt_kernel_takes(int kernel, const StepParams<float> &sp, const KktPointers &a, bool query = false)
+{
+    // (u_zero_I and delta_u of the FORWARD are not inputs of the backward: the reference's nested solve is built from the bounds
+    // alone, `u_zero_I = I` from u* and the bounds, `delta_u = None`, mpc/lqr_step.py:322-340 -- the launchers drop them; rounds
+    // 1-3 refused such options here and the caller fell to three launches for nothing)
+    if (!sp.c_symmetric || sp.env.kind) return false;
+    if (query) {
+        StepParams<float> s = sizes_only(sp);
+        s.c_symmetric = 1;
+        return kkt_kernel_takes(kernel, s, KktPointers());
+    }
+    const float *gx = (const float *)a.dl_dx, *gu = (const float *)a.dl_du, *dC = (const float *)a.dC, *dF = (const float *)a.dF,
+                *ws = (const float *)a.workspace;
+    switch (kernel) {
+    case MPC_KKT_DPP16: return kkt_fused_dpp16_supported(sp, gx, gu, dC, dF, ws);
+    // every other shape up to 12/4, and 12/4 itself where a block is not 16-byte aligned: the padded instantiation (round 6)
+    case MPC_KKT_DPP16_PAD: return kkt_fused_dpp16_pad_supported(sp, ws);
+    // config 5's shape: the nested step with the costates riding along, then the outer-product kernel (two launches); what the
+    // kernel stores through 16-byte rows is the caller's here, not the rule's
+    case MPC_KKT_MFMA40:
+        return kkt_fused_mfma40_supported(sp, gx, gu, dC, dF, ws) && !(a.dx_out && (((uintptr_t)a.dx_out | (uintptr_t)a.du_out) & 15)) &&
+               !((uintptr_t)a.dx_init & 15) && !(a.df && ((uintptr_t)a.df & 15));
+    // every other shape up to 32/8, and 32/8 itself off the 16-byte grid: the padded instantiations (round 6)
+    case MPC_KKT_MFMA40_PAD16: return kkt_fused_mfma40_pad16_supported(sp, ws);
+    case MPC_KKT_MFMA40_PAD4: return kkt_fused_mfma40_pad_supported(sp, ws);
+    }
+    return false;
+}
+
+// The fused kernels in the order they are tried, each with its launcher, the workspace it lives in and what a call that heads for it
+// and is taken by nobody is told.  Exact before padded; beyond 12/4 the 16-byte gathers before the dword ones.
+typedef int (*KktLaunch)(const StepParams<float> &, const float *, const float *, float *, float *, float *, float *, float *, float *, float *,
+                         float *, float, int, hipStream_t);
+struct KktKernel {
+    int code;
+    KktLaunch launch;
+    int64_t (*ws_bytes)(int T, int B);       // (a padded instantiation pads to the exact kernel's layout: the same workspace)
+    const char *nobody;
+};
+static const char kkt_nobody12[] = "mpc_lqr_kkt_fused: the workspace must be 16-byte aligned";
+static const char kkt_nobody40[] = "mpc_lqr_kkt_fused: the workspace must be 16-byte aligned (tensor bounds 4-byte aligned)";
+static const KktKernel kkt_order[] = {
+    {MPC_KKT_DPP16, launch_kkt_fused_dpp16, kkt_fused_dpp16_workspace_bytes, kkt_nobody12},
+    {MPC_KKT_DPP16_PAD, launch_kkt_fused_dpp16_pad, kkt_fused_dpp16_workspace_bytes, kkt_nobody12},
+    {MPC_KKT_MFMA40, launch_kkt_fused_mfma40, kkt_fused_mfma40_workspace_bytes, kkt_nobody40},
+    {MPC_KKT_MFMA40_PAD16, launch_kkt_fused_mfma40_pad16, kkt_fused_mfma40_workspace_bytes, kkt_nobody40},
+    {MPC_KKT_MFMA40_PAD4, launch_kkt_fused_mfma40_pad, kkt_fused_mfma40_workspace_bytes, kkt_nobody40},
+};
+static_assert(MPC_KKT_DPP16 == 1 && MPC_KKT_DPP16_PAD == 2 && MPC_KKT_MFMA40 == 3 && MPC_KKT_MFMA40_PAD16 == 4 && MPC_KKT_MFMA40_PAD4 == 5,
+              "kkt_order[code - 1] is the row of `code`");
+
+// the first kernel of the order that takes the call (query: its sizes, dtype and flags), or NULL
+static const KktKernel *kkt_first(const mpc_lqr_problem *p, const StepParams<float> &sp, const KktPointers &a, bool query = false)
+{
+    if (p->dtype != MPC_F32) return nullptr;
+    for (const KktKernel &k : kkt_order)
+        if (kkt_kernel_takes(k.code, sp, a, query)) return &k;
+    return nullptr;
+}
+
+// Which fused kernel takes this backward.  Launches nothing, sets no error state, allocates nothing; never cached.  The refusals
+// are mpc_lqr_kkt_fused's, in its order (behind check_kkt_fused); no_kernel marks the two that say "legal, but no fused kernel".
+KktRoute kkt_fused_route(const StepParams<float> &sp, const mpc_lqr_problem *p, const KktPointers &a, int64_t workspace_bytes)
+{
+    KktRoute r = {0, nullptr, false, MPC_KKT_NONE, 0};
+    const auto refuse = [&r](int code, const char *msg, bool no_kernel = false) { r.code = code; r.msg = msg; r.no_kernel = no_kernel; return r; };
+    // A kernel that takes the views takes their sizes, so the call that somebody takes asks every rule at most once.  Only the call
+    // nobody takes asks a second time, on the sizes alone, for the kernel it was heading for: that one names the workspace and the text.
+    const KktKernel *const taker = kkt_first(p, sp, a), *const heading = taker ? taker : kkt_first(p, sp, a, true);
+    if (!heading)
+        return refuse(MPC_E_DIMS, "mpc_lqr_kkt_fused: needs fp32, n_state <= 32, n_ctrl <= 8, and "
+                                  "MPC_OPT_C_SYMMETRIC (otherwise: mpc_lqr_kkt_prepare + mpc_lqr_step + mpc_lqr_kkt_grads)", true);
+    if (p->B == 0) return r;                     // (the entry succeeds and launches nothing)
+    if (!a.dl_dx || !a.dl_du || !a.dC || !a.dc || !a.dx_init) return refuse(MPC_E_NULL, "kkt_fused: NULL argument");
+    if (p->T > 1 && !a.dF) return refuse(MPC_E_NULL, "kkt_fused: dF is NULL");
+    if ((a.df != nullptr) != (p->f != nullptr && p->T > 1)) return refuse(MPC_E_NULL, "kkt_fused: df goes with f");
+    if ((a.dx_out == nullptr) != (a.du_out == nullptr)) return refuse(MPC_E_NULL, "kkt_fused: pass both dx_out and du_out, or neither");
+    r.bytes = heading->ws_bytes(p->T, p->B);
+    if (!a.workspace || workspace_bytes < r.bytes) return refuse(MPC_E_ARG, "workspace too small (see mpc_lqr_kkt_fused_workspace_bytes)");
+    if (!taker) return refuse(MPC_E_DIMS, heading->nobody, true);
+    r.kernel = taker->code;
+    return r;
+}
+
+// the argument checks of mpc_lqr_kkt_fused, and of mpc_lqr_kkt_fused_route, which answers for the same arguments
+static int check_kkt_fused(const mpc_lqr_problem *p, const mpc_lqr_options *o)
+{
+    const int rc = check_problem(p, true, true);
+    return rc ? rc : check_options(p, o);
+}
+
+static StepParams<float> kkt_fused_params(const mpc_lqr_problem *p, const mpc_lqr_options *o, int32_t *status)
+{
+    mpc_lqr_outputs out;
+    memset(&out, 0, sizeof(out));
+    out.status = status;
+    return make_params<float>(p, o, &out);
+}
+
+// Which kernel takes the closed-form part of the three-call route (mpc_lqr_kkt_grads): the first of this order that takes the views.
+static int kkt_grads_route(const StepParams<float> &sp, const float *dx, const float *du, const float *dl_dx, const float *dC, const float *dF)
+{
+    // headline shape: the 4-problems-per-wave DPP kernel (lqr_dpp16_body.h: kkt_wave)
+    if (kkt_dpp16_supported(sp, dx, du, dl_dx, dC, dF)) return MPC_KKT_GRADS_DPP16;
+    // other shapes up to n = 64: costate recursion per wavefront + fully parallel outer products
+    if (kkt_wave_supported(sp, dx, du, dl_dx, dC, dF)) return MPC_KKT_GRADS_WAVE;
+    return MPC_KKT_GRADS_GENERIC;
+}
+
+// the argument checks of mpc_lqr_kkt_grads and mpc_lqr_kkt_grads_route (an empty batch passes them: nothing is launched)
+static int check_kkt_grads(const mpc_lqr_problem *p, const void *dx, const void *du, const void *dl_dx, const void *dl_du, const void *dC,
+                           const void *dc, const void *dF, const void *dx_init)
+{
+    const int rc = check_problem(p, true, true);
+    if (rc || p->B == 0) return rc;
+    if (!dx || !du || !dl_dx || !dl_du || !dC || !dc || !dx_init) return fail(MPC_E_NULL, "kkt_grads: NULL argument");
+    if (p->T > 1 && !dF) return fail(MPC_E_NULL, "kkt_grads: dF is NULL");
+    return MPC_OK;
+}
 }  // namespace mpclqr
 
 using namespace mpclqr;
@@ -631,34 +761,34 @@ int mpc_lqr_rollout(const mpc_lqr_problem *p, const mpc_lqr_options *o, const mp
                                : step_impl<double>(p, o, out, nullptr, 0, 1, 2, old_costs_in, st);
 }
 
-int mpc_lqr_kkt_grads(const mpc_lqr_problem *p, const void *dx, const void *du, const void *dl_dx,
-                      const void *dl_du, void *dC, void *dc, void *dF, void *df, void *dx_init, void *stream)
+int mpc_lqr_kkt_grads(const mpc_lqr_problem *p, const void *dx_, const void *du_, const void *dl_dx_,
+                      const void *dl_du, void *dC_, void *dc_, void *dF_, void *df_, void *dx_init_, void *stream)
 {
-    int rc = check_problem(p, true, true);
-    if (rc) return rc;
-    if (p->B == 0) return MPC_OK;
-    if (!dx || !du || !dl_dx || !dl_du || !dC || !dc || !dx_init) return fail(MPC_E_NULL, "kkt_grads: NULL argument");
-    if (p->T > 1 && !dF) return fail(MPC_E_NULL, "kkt_grads: dF is NULL");
+    const int rc = check_kkt_grads(p, dx_, du_, dl_dx_, dl_du, dC_, dc_, dF_, dx_init_);
+    if (rc || p->B == 0) return rc;
     hipStream_t st = (hipStream_t)stream;
-    if (p->dtype == MPC_F32) {
-        StepParams<float> sp = make_params<float>(p, nullptr, nullptr);
-        // headline shape: the 4-problems-per-wave DPP kernel (lqr_dpp16_body.h: kkt_wave)
-        if (kkt_dpp16_supported(sp, (const float *)dx, (const float *)du, (const float *)dl_dx, (const float *)dC,
-                                (const float *)dF))
-            return launch_kkt_dpp16(sp, (const float *)dx, (const float *)du, (const float *)dl_dx, (float *)dC,
-                                    (float *)dc, (float *)dF, (float *)df, (float *)dx_init, st);
-        // other shapes up to n = 64: costate recursion per wavefront + fully parallel outer products
-        if (kkt_wave_supported(sp, (const float *)dx, (const float *)du, (const float *)dl_dx, (const float *)dC, (const float *)dF))
-            return launch_kkt_wave(sp, (const float *)dx, (const float *)du, (const float *)dl_dx, (float *)dC,
-                                   (float *)dc, (float *)dF, (float *)df, (float *)dx_init, st);
-        return launch_kkt_grads<float>(sp, (const float *)dx, (const float *)du, (const float *)dl_dx,
-                                       (const float *)dl_du, (float *)dC, (float *)dc, (float *)dF, (float *)df,
-                                       (float *)dx_init, st);
+    if (p->dtype != MPC_F32)                     // float64: always the generic kernel
+        return launch_kkt_grads<double>(make_params<double>(p, nullptr, nullptr), (const double *)dx_, (const double *)du_,
+                                        (const double *)dl_dx_, (const double *)dl_du, (double *)dC_, (double *)dc_, (double *)dF_,
+                                        (double *)df_, (double *)dx_init_, st);
+    const StepParams<float> sp = make_params<float>(p, nullptr, nullptr);
+    const float *dx = (const float *)dx_, *du = (const float *)du_, *dl_dx = (const float *)dl_dx_;
+    float *dC = (float *)dC_, *dc = (float *)dc_, *dF = (float *)dF_, *df = (float *)df_, *dx_init = (float *)dx_init_;
+    switch (kkt_grads_route(sp, dx, du, dl_dx, dC, dF)) {
+    case MPC_KKT_GRADS_DPP16: return launch_kkt_dpp16(sp, dx, du, dl_dx, dC, dc, dF, df, dx_init, st);
+    case MPC_KKT_GRADS_WAVE: return launch_kkt_wave(sp, dx, du, dl_dx, dC, dc, dF, df, dx_init, st);
     }
-    StepParams<double> sp = make_params<double>(p, nullptr, nullptr);
-    return launch_kkt_grads<double>(sp, (const double *)dx, (const double *)du, (const double *)dl_dx,
-                                    (const double *)dl_du, (double *)dC, (double *)dc, (double *)dF, (double *)df,
-                                    (double *)dx_init, st);
+    return launch_kkt_grads<float>(sp, dx, du, dl_dx, (const float *)dl_du, dC, dc, dF, df, dx_init, st);
+}
+
+int mpc_lqr_kkt_grads_route(const mpc_lqr_problem *p, const void *dx, const void *du, const void *dl_dx, const void *dl_du,
+                            const void *dC, const void *dc, const void *dF, const void *df, const void *dx_init)
+{
+    const int rc = check_kkt_grads(p, dx, du, dl_dx, dl_du, dC, dc, dF, dx_init);
+    if (rc || p->B == 0) return rc;          // (0: mpc_lqr_kkt_grads succeeds and launches nothing)
+    if (p->dtype != MPC_F32) return MPC_KKT_GRADS_GENERIC;
+    return kkt_grads_route(make_params<float>(p, nullptr, nullptr), (const float *)dx, (const float *)du, (const float *)dl_dx,
+                           (const float *)dC, (const float *)dF);
 }
 
 int mpc_lqr_kkt_shared_supported(const mpc_lqr_problem *p)
@@ -698,67 +828,46 @@ int mpc_lqr_kkt_fused_supported(const mpc_lqr_problem *p, const mpc_lqr_options 
     if (!p || check_problem(p, false, false) != MPC_OK || check_options(p, o) != MPC_OK) return 0;
     // (12/4: any horizon since round 4; every shape UP TO 12/4 since round 6: the padded instantiation, lqr_dpp16.hip -DMPC_DPP16_PAD_KKT)
     // ... and every shape up to 32/8: the padded instantiation of the 32/8 kernel's fused backward, lqr_mfma40.hip -DMPC_MFMA40_KKT -DMPC_MFMA40_PAD=4
-    const bool s12 = p->ns >= 1 && p->ns <= 12 && p->nc >= 1 && p->nc <= 4, s32 = p->ns >= 1 && p->ns <= 32 && p->nc >= 1 && p->nc <= 8;
-    if (p->dtype != MPC_F32 || !(s12 || s32)) return 0;
-    if (!o || !(o->flags & MPC_OPT_C_SYMMETRIC)) return 0;
-    // (u_zero_I and delta_u of the FORWARD are not inputs of the backward: the reference's nested solve is built from the bounds
-    // alone, `u_zero_I = I` from u* and the bounds, `delta_u = None`, mpc/lqr_step.py:322-340 -- the launchers drop them; rounds
-    // 1-3 refused such options here and the caller fell to three launches for nothing)
-    if (o->true_dynamics) return 0;
-    return 1;
+    return kkt_first(p, make_params<float>(p, o, nullptr), KktPointers(), true) ? 1 : 0;
 }
 
 int64_t mpc_lqr_kkt_fused_workspace_bytes(const mpc_lqr_problem *p)
 {
     if (!p) return 0;
-    return (p->ns > 12 || p->nc > 4) ? kkt_fused_mfma40_workspace_bytes(p->T, p->B) : kkt_fused_dpp16_workspace_bytes(p->T, p->B);
+    // The workspace of the kernel a float32 backward of these sizes heads for under MPC_OPT_C_SYMMETRIC; where there is none (a larger
+    // shape) the last of the order answers, and sizes below 1, which every entry refuses, answer as 1 does -- as they always have.
+    const mpc_lqr_problem q = sizes_only(1, 1, std::max(p->ns, 1), std::max(p->nc, 1), MPC_F32);
+    StepParams<float> s = make_params<float>(&q, nullptr, nullptr);
+    s.c_symmetric = 1;
+    const KktKernel *heading = kkt_first(&q, s, KktPointers(), true);
+    return (heading ? heading : &kkt_order[sizeof(kkt_order) / sizeof(kkt_order[0]) - 1])->ws_bytes(p->T, p->B);
 }
 
 int mpc_lqr_kkt_fused(const mpc_lqr_problem *p, const mpc_lqr_options *o, const void *dl_dx, const void *dl_du,
                       void *dC, void *dc, void *dF, void *df, void *dx_init, void *dx_out, void *du_out, int32_t *status,
                       void *workspace, int64_t workspace_bytes, void *stream)
 {
-    int rc = check_problem(p, true, true);
+    const int rc = check_kkt_fused(p, o);
     if (rc) return rc;
-    if ((rc = check_options(p, o))) return rc;
-    if (!mpc_lqr_kkt_fused_supported(p, o))
-        return fail(MPC_E_DIMS, "mpc_lqr_kkt_fused: needs fp32, n_state <= 32, n_ctrl <= 8, and "
-                                "MPC_OPT_C_SYMMETRIC (otherwise: mpc_lqr_kkt_prepare + mpc_lqr_step + mpc_lqr_kkt_grads)");
-    if (p->B == 0) return MPC_OK;
-    if (!dl_dx || !dl_du || !dC || !dc || !dx_init) return fail(MPC_E_NULL, "kkt_fused: NULL argument");
-    if (p->T > 1 && !dF) return fail(MPC_E_NULL, "kkt_fused: dF is NULL");
-    if ((df != nullptr) != (p->f != nullptr && p->T > 1)) return fail(MPC_E_NULL, "kkt_fused: df goes with f");
-    if ((dx_out == nullptr) != (du_out == nullptr)) return fail(MPC_E_NULL, "kkt_fused: pass both dx_out and du_out, or neither");
-    if (!workspace || workspace_bytes < mpc_lqr_kkt_fused_workspace_bytes(p))
-        return fail(MPC_E_ARG, "workspace too small (see mpc_lqr_kkt_fused_workspace_bytes)");
-    mpc_lqr_outputs out;
-    memset(&out, 0, sizeof(out));
-    out.status = status;
-    StepParams<float> sp = make_params<float>(p, o, &out);
-    const float *gx = (const float *)dl_dx, *gu = (const float *)dl_du, *ws = (const float *)workspace;
-    int (*launch)(const StepParams<float> &, const float *, const float *, float *, float *, float *, float *, float *, float *, float *,
-                  float *, float, int, hipStream_t);
-    if (p->ns > 12 || p->nc > 4) {
-        // config 5's shape: the nested step with the costates riding along, then the outer-product kernel (two launches)
-        launch = launch_kkt_fused_mfma40;
-        if (!kkt_fused_mfma40_supported(sp, gx, gu, (const float *)dC, (const float *)dF, ws) ||
-            (dx_out && (((uintptr_t)dx_out | (uintptr_t)du_out) & 15)) || ((uintptr_t)dx_init & 15) || (df && ((uintptr_t)df & 15))) {
-            // every other shape up to 32/8, and 32/8 itself off the 16-byte grid: the padded instantiation (round 6)
-            if (!kkt_fused_mfma40_pad_supported(sp, ws))
-                return fail(MPC_E_DIMS, "mpc_lqr_kkt_fused: the workspace must be 16-byte aligned (tensor bounds 4-byte aligned)");
-            launch = kkt_fused_mfma40_pad16_supported(sp, ws) ? launch_kkt_fused_mfma40_pad16 : launch_kkt_fused_mfma40_pad;
-        }
-    } else {
-        launch = launch_kkt_fused_dpp16;
-        if (!kkt_fused_dpp16_supported(sp, gx, gu, (const float *)dC, (const float *)dF, ws)) {
-            // every other shape up to 12/4, and 12/4 itself where a block is not 16-byte aligned: the padded instantiation (round 6)
-            if (!kkt_fused_dpp16_pad_supported(sp, ws)) return fail(MPC_E_DIMS, "mpc_lqr_kkt_fused: the workspace must be 16-byte aligned");
-            launch = launch_kkt_fused_dpp16_pad;
-        }
-    }
+    const StepParams<float> sp = kkt_fused_params(p, o, status);
+    const KktRoute r = kkt_fused_route(sp, p, KktPointers{dl_dx, dl_du, dC, dc, dF, df, dx_init, dx_out, du_out, workspace}, workspace_bytes);
+    if (r.code) return fail(r.code, r.msg);
+    if (!r.kernel) return MPC_OK;                // (an empty batch)
     // the nested solve is a plain LQRStep(...) in the reference (:328-338): linesearch_decay 0.2, max_linesearch_iter 10
-    return launch(sp, gx, gu, (float *)dC, (float *)dc, (float *)dF, (float *)df, (float *)dx_init, (float *)dx_out, (float *)du_out,
-                  (float *)workspace, 0.2f, 10, (hipStream_t)stream);
+    return kkt_order[r.kernel - 1].launch(sp, (const float *)dl_dx, (const float *)dl_du, (float *)dC, (float *)dc, (float *)dF, (float *)df,
+                                          (float *)dx_init, (float *)dx_out, (float *)du_out, (float *)workspace, 0.2f, 10, (hipStream_t)stream);
+}
+
+int mpc_lqr_kkt_fused_route(const mpc_lqr_problem *p, const mpc_lqr_options *o, const void *dl_dx, const void *dl_du,
+                            const void *dC, const void *dc, const void *dF, const void *df, const void *dx_init, const void *dx_out,
+                            const void *du_out, const int32_t *status, const void *workspace, int64_t workspace_bytes)
+{
+    const int rc = check_kkt_fused(p, o);
+    if (rc) return rc;
+    const KktRoute r = kkt_fused_route(kkt_fused_params(p, o, (int32_t *)status), p,
+                                       KktPointers{dl_dx, dl_du, dC, dc, dF, df, dx_init, dx_out, du_out, workspace}, workspace_bytes);
+    if (r.code && !r.no_kernel) return fail(r.code, r.msg);
+    return r.kernel;                             // (MPC_KKT_NONE: a legal call that no fused kernel takes, or an empty batch)
 }
 
 int mpc_env_traj_cost(const mpc_lqr_problem *p, const mpc_env_dynamics *env, void *x, void *cost, void *stream)

@@ -38,6 +38,19 @@ template <typename real>
 StepRoute step_route(const StepParams<real> &sp, const mpc_lqr_problem *p, int impl, int phase_mask, const void *workspace,
                      int64_t workspace_bytes);
 
+// Which fused kernel takes one KKT backward (capi.hip: kkt_fused_route decides, mpc_lqr_kkt_fused executes, mpc_lqr_kkt_fused_route
+// and the entry's two queries read it off).  Host only.
+struct KktPointers {               // the entry's pointers: inspected for NULL and alignment, never dereferenced
+    const void *dl_dx, *dl_du, *dC, *dc, *dF, *df, *dx_init, *dx_out, *du_out, *workspace;
+};
+struct KktRoute {
+    int code; const char *msg;     // code != 0: refused, with mpc_lqr_kkt_fused's code and text (a string literal) ...
+    bool no_kernel;                // ... because no fused kernel takes these sizes, flags or views: the three-call route's case
+    int kernel;                    // MPC_KKT_* (include/mpc_lqr.h); MPC_KKT_NONE with code 0: an empty batch
+    int64_t bytes;                 // the workspace that kernel needs
+};
+KktRoute kkt_fused_route(const StepParams<float> &sp, const mpc_lqr_problem *p, const KktPointers &a, int64_t workspace_bytes);
+
 // generic path (lqr_generic.hip)
 template <typename real> int launch_step_generic(const StepParams<real> &p, int phase_mask, hipStream_t st);
 template <typename real> int launch_pnqp(int B, int n, const real *H, const real *q, const real *lo,

@@ -20,6 +20,9 @@ ST_PNQP_UNCONVERGED, ST_NONFINITE, ST_NOMINAL_OFF_DYNAMICS, ST_C_ASYMMETRIC, ST_
 IMPL_AUTO, IMPL_GENERIC, IMPL_MFMA16, IMPL_DPP16, IMPL_TINY, IMPL_MFMA40, IMPL_WAVE1, IMPL_MFMA40_PAD, IMPL_DPP16_PAD = 0, 1, 2, 3, 4, 5, 6, 7, 8
 IMPL_MFMA40_NARROW = 9      # the padded 32/8 kernel on one 16-row state tile (n_state <= 16); forced only, IMPL_AUTO never picks it
 
+KKT_NONE, KKT_DPP16, KKT_DPP16_PAD, KKT_MFMA40, KKT_MFMA40_PAD16, KKT_MFMA40_PAD4 = 0, 1, 2, 3, 4, 5      # mpc_lqr_kkt_fused_route (MPC_KKT_*)
+KKT_GRADS_DPP16, KKT_GRADS_WAVE, KKT_GRADS_GENERIC = 1, 2, 3                                            # mpc_lqr_kkt_grads_route
+
 ABI_VERSION = 9      # include/mpc_lqr.h: MPC_LQR_ABI_VERSION
 
 _vp, _i32, _i64, _f64 = ctypes.c_void_p, ctypes.c_int32, ctypes.c_int64, ctypes.c_double
@@ -218,7 +221,8 @@ EXPORTS = ("mpc_lqr_abi_version", "mpc_lqr_build_info", "mpc_lqr_last_error", "m
            "mpc_mlp_param_grad_workspace_bytes", "mpc_mlp_param_grad",
            "mpc_mlp_supported", "mpc_lqr_kkt_fused_supported", "mpc_lqr_kkt_fused_workspace_bytes", "mpc_lqr_kkt_fused",
            "mpc_du_norm_reference", "mpc_slew_augment",
-           "mpc_lqr_kkt_shared_supported", "mpc_lqr_kkt_shared_workspace_bytes", "mpc_lqr_kkt_grads_shared")
+           "mpc_lqr_kkt_shared_supported", "mpc_lqr_kkt_shared_workspace_bytes", "mpc_lqr_kkt_grads_shared",
+           "mpc_lqr_kkt_fused_route", "mpc_lqr_kkt_grads_route")
 
 _lib = None
 
@@ -262,6 +266,8 @@ def load():
     L.mpc_lqr_kkt_fused_workspace_bytes.restype = _i64
     L.mpc_lqr_kkt_fused_workspace_bytes.argtypes = [PP]
     L.mpc_lqr_kkt_fused.argtypes = [PP, OP] + [_vp] * 11 + [_i64, _vp]
+    L.mpc_lqr_kkt_fused_route.argtypes = [PP, OP] + [_vp] * 11 + [_i64]
+    L.mpc_lqr_kkt_grads_route.argtypes = [PP] + [_vp] * 9
     L.mpc_lqr_kkt_shared_supported.argtypes = [PP]
     L.mpc_lqr_kkt_shared_workspace_bytes.restype = _i64
     L.mpc_lqr_kkt_shared_workspace_bytes.argtypes = [PP]
@@ -699,29 +705,33 @@ class HipBackend:
         sol = self.lqr_step(z0, C, negr, F, None, zx, zu, inner, impl=impl)
         return sol, negr, mask, keep
 
-    def kkt_backward(self, C, c, F, f, x_star, u_star, dl_dx, dl_du, opts, impl=IMPL_AUTO):
-        """dx_init, dC, dc, dF, df of mpc/lqr_step.py:312-407 (reference), all on device."""
+    def _open_kkt(self, C, c, F, f, x_star, u_star, dl_dx, dl_du, nominal=True, prepared=False):
+        """The opening of every backward-shaped call: device check, sizes, x*, u*, dl_dx, dl_du detached, of C's dtype and
+        contiguous (`prepared`: they are), has_f, and the problem struct over (C, c, F, f, x*, u*) with what it keeps alive; its
+        x_init is the zero nominal's where `nominal` (the three-call route), else x*[0] (the fused entry reads none).
+        -> (library, device, (T, B, ns, nc, n), kw, (x_star, u_star, dl_dx, dl_du), has_f, Problem, keep)"""
         dev = _require_device(C, c, F, x_star, u_star, dl_dx, dl_du)
-        L = load()
-        T, B, n = C.shape[0], C.shape[1], C.shape[2]
-        ns = x_star.shape[2]
+        T, B, n, ns = C.shape[0], C.shape[1], C.shape[2], x_star.shape[2]
         nc = n - ns
         kw = dict(device=dev, dtype=C.dtype)
-        st = _stream(dev)
-        dl_dx = dl_dx.detach().to(**kw).contiguous()
-        dl_du = dl_du.detach().to(**kw).contiguous()
-        x_star = x_star.detach().contiguous()
-        u_star = u_star.detach().contiguous()
+        if not prepared:
+            dl_dx = dl_dx.detach().to(**kw).contiguous()
+            dl_du = dl_du.detach().to(**kw).contiguous()
+            x_star = x_star.detach().contiguous()
+            u_star = u_star.detach().contiguous()
         has_f = f is not None and f.numel() > 0
+        p, keep = self._problem(self._zero_nominal(T, B, ns, nc, kw)[2] if nominal else x_star[0], C, c, F, f, x_star, u_star)
+        return load(), dev, (T, B, ns, nc, n), kw, (x_star, u_star, dl_dx, dl_du), has_f, p, keep
+
+    def kkt_backward(self, C, c, F, f, x_star, u_star, dl_dx, dl_du, opts, impl=IMPL_AUTO):
+        """dx_init, dC, dc, dF, df of mpc/lqr_step.py:312-407 (reference), all on device."""
         if impl == IMPL_AUTO:
-            # the whole backward in one launch where a kernel for it exists (12/4 or 32/8, fp32, C vouched symmetric)
-            plan = self.plan_kkt_backward(C, c, F, f, x_star, u_star, dl_dx, dl_du, opts, _prepared=True)
-            if plan is not None:
-                g = plan()
-                if g is not None:
-                    return g
+            # the whole backward in one call where a fused kernel takes it (up to 32/8, fp32, C vouched symmetric)
+            plan = self.plan_kkt_backward(C, c, F, f, x_star, u_star, dl_dx, dl_du, opts)
+            if plan is not None and plan.kernel != KKT_NONE:
+                return plan()
+        L, dev, (T, B, ns, nc, n), kw, (x_star, u_star, dl_dx, dl_du), has_f, p, keep = self._open_kkt(C, c, F, f, x_star, u_star, dl_dx, dl_du)
         sol, negr, mask, keep_o = self._nested_kkt_solve(C, F, dl_dx, dl_du, u_star, opts, impl)
-        p, keep = self._problem(self._zero_nominal(T, B, ns, nc, kw)[2], C, c, F, f, x_star, u_star)
         dC = torch.empty(T, B, n, n, **kw)
         dc = torch.empty(T, B, n, **kw)
         dF = torch.empty(F.shape, **kw)          # every kernel writes all of it (t < T-1 is all there is)
@@ -729,7 +739,7 @@ class HipBackend:
         dx_init = torch.empty(B, ns, **kw)
         _check(L.mpc_lqr_kkt_grads(ctypes.byref(p), sol["new_x"].data_ptr(), sol["new_u"].data_ptr(),
                                    dl_dx.data_ptr(), dl_du.data_ptr(), dC.data_ptr(), dc.data_ptr(),
-                                   dF.data_ptr(), _ptr(df), dx_init.data_ptr(), st), "mpc_lqr_kkt_grads")
+                                   dF.data_ptr(), _ptr(df), dx_init.data_ptr(), _stream(dev)), "mpc_lqr_kkt_grads")
         return dict(dx_init=dx_init, dC=dC, dc=dc, dF=dF, df=df, dx=sol["new_x"], du=sol["new_u"],
                     _keep=(keep, keep_o, negr, mask, sol))
 
@@ -741,30 +751,17 @@ class HipBackend:
         the fastest step kernel of the shape (as kkt_backward's three-call path), then mpc_lqr_kkt_grads_shared: no per-problem
         dC / dF is ever written.  Where that entry does not cover the problem (float64, n_state + n_ctrl > 64) the same dict
         comes from kkt_backward and a sum over the batch axis."""
-        dev = _require_device(C, c, F, x_star, u_star, dl_dx, dl_du)
-        L = load()
-        T, B, n = C.shape[0], C.shape[1], C.shape[2]
-        ns = x_star.shape[2]
-        nc = n - ns
-        has_f = f is not None and f.numel() > 0
+        L, dev, (T, B, ns, nc, n), kw, (x_star, u_star, dl_dx, dl_du), has_f, p, keep = self._open_kkt(C, c, F, f, x_star, u_star, dl_dx, dl_du)
         want = tuple(bool(w) for w in want)
         want = (want[0], want[1], want[2] and T > 1, want[3] and has_f and T > 1)
         names = ("sum_dC", "sum_dc", "sum_dF", "sum_df")
-        x_star = x_star.detach().contiguous()
-        u_star = u_star.detach().contiguous()
-        probe, keep_probe = self._problem(x_star[0], C, c, F, f, x_star, u_star)
-        if not L.mpc_lqr_kkt_shared_supported(ctypes.byref(probe)):
+        if not L.mpc_lqr_kkt_shared_supported(ctypes.byref(p)):
             g = self.kkt_backward(C, c, F, f, x_star, u_star, dl_dx, dl_du, opts)
             out = dict(dx_init=g["dx_init"], dx=g["dx"], du=g["du"])
             for name, src, w in zip(names, ("dC", "dc", "dF", "df"), want):
                 out[name] = g[src].sum(1) if (w and g[src] is not None) else None
             return out
-        kw = dict(device=dev, dtype=C.dtype)
-        st = _stream(dev)
-        dl_dx = dl_dx.detach().to(**kw).contiguous()
-        dl_du = dl_du.detach().to(**kw).contiguous()
         sol, negr, mask, keep_o = self._nested_kkt_solve(C, F, dl_dx, dl_du, u_star, opts, IMPL_AUTO)
-        p, keep = self._problem(self._zero_nominal(T, B, ns, nc, kw)[2], C, c, F, f, x_star, u_star)
         shapes = ((T, n, n), (T, n), (T - 1, ns, n), (T - 1, ns))
         sums = [torch.empty(shape, **kw) if w else None for shape, w in zip(shapes, want)]
         dx_init = torch.empty(B, ns, **kw)
@@ -772,8 +769,8 @@ class HipBackend:
         ws = torch.empty(nbytes, device=dev, dtype=torch.uint8)
         _check(L.mpc_lqr_kkt_grads_shared(ctypes.byref(p), sol["new_x"].data_ptr(), sol["new_u"].data_ptr(), dl_dx.data_ptr(),
                                           dl_du.data_ptr(), _ptr(sums[0]), _ptr(sums[1]), _ptr(sums[2]), _ptr(sums[3]),
-                                          dx_init.data_ptr(), ws.data_ptr(), nbytes, st), "mpc_lqr_kkt_grads_shared")
-        out = dict(dx_init=dx_init, dx=sol["new_x"], du=sol["new_u"], _keep=(keep, keep_o, keep_probe, negr, mask, sol, ws))
+                                          dx_init.data_ptr(), ws.data_ptr(), nbytes, _stream(dev)), "mpc_lqr_kkt_grads_shared")
+        out = dict(dx_init=dx_init, dx=sol["new_x"], du=sol["new_u"], _keep=(keep, keep_o, negr, mask, sol, ws))
         out.update(zip(names, sums))
         return out
 
@@ -782,21 +779,11 @@ class HipBackend:
         built once, `plan()` is then a single C call that overwrites the same outputs (clone what must survive) -- what a loop
         over many backward calls of one shape wants (bench.py; an allocation-per-call caller spends as long in the allocator
         as the GPU in the kernel).  Reads dl_dx / dl_du in place at every call.  None where no fused kernel covers the
-        problem; plan() returns None if the library refuses the views (misaligned): use kkt_backward then."""
-        dev = _require_device(C, c, F, x_star, u_star, dl_dx, dl_du)
-        L = load()
-        T, B, n = C.shape[0], C.shape[1], C.shape[2]
-        ns = x_star.shape[2]
-        nc = n - ns
-        kw = dict(device=dev, dtype=C.dtype)
-        if not _prepared:
-            dl_dx = dl_dx.detach().to(**kw).contiguous()
-            dl_du = dl_du.detach().to(**kw).contiguous()
-            x_star = x_star.detach().contiguous()
-            u_star = u_star.detach().contiguous()
+        problem (mpc_lqr_kkt_fused_supported).  The kernel is asked for once, here (mpc_lqr_kkt_fused_route -> plan.kernel); where
+        none takes exactly the views bound (KKT_NONE) plan() returns None: use kkt_backward then.  A code from the call raises."""
+        L, dev, (T, B, ns, nc, n), kw, (x_star, u_star, dl_dx, dl_du), has_f, pf, keep_f = \
+            self._open_kkt(C, c, F, f, x_star, u_star, dl_dx, dl_du, nominal=False, prepared=_prepared)
         o, keep_o = opts.to_struct(T, B, nc, C)
-        has_f = f is not None and f.numel() > 0
-        pf, keep_f = self._problem(x_star[0], C, c, F, f, x_star, u_star)
         if not L.mpc_lqr_kkt_fused_supported(ctypes.byref(pf), ctypes.byref(o)):
             return None
         g = dict(dC=torch.empty(T, B, n, n, **kw), dc=torch.empty(T, B, n, **kw), dF=torch.empty(F.shape, **kw),
@@ -809,16 +796,28 @@ class HipBackend:
         args = (ctypes.byref(pf), ctypes.byref(o), dl_dx.data_ptr(), dl_du.data_ptr(), g["dC"].data_ptr(), g["dc"].data_ptr(),
                 g["dF"].data_ptr(), _ptr(g["df"]) if (has_f and T > 1) else None, g["dx_init"].data_ptr(), g["dx"].data_ptr(),
                 g["du"].data_ptr(), None, ws.data_ptr(), nbytes)
+        kernel = int(L.mpc_lqr_kkt_fused_route(*args))
+        if kernel < 0:
+            _check(kernel, "mpc_lqr_kkt_fused_route")
 
         def run(stream=None):
-            rc = fn(*args, torch.cuda.current_stream(dev).cuda_stream if stream is None else stream)
-            if rc == -1:              # MPC_E_DIMS = misaligned views: kkt_backward's three calls take anything
+            if kernel == KKT_NONE:               # a legal call that no fused kernel takes: kkt_backward's three calls take anything
                 return None
+            rc = fn(*args, torch.cuda.current_stream(dev).cuda_stream if stream is None else stream)
             if rc != 0:
                 _check(rc, "mpc_lqr_kkt_fused")
             return g
-        run.outputs = g
+        run.outputs, run.kernel, run._bind = g, kernel, args
         return run
+
+    @staticmethod
+    def kkt_route(plan):
+        """The KKT_* code of the fused kernel that takes exactly what `plan` has bound, KKT_NONE where none does
+        (mpc_lqr_kkt_fused_route; nothing is launched)."""
+        kernel = int(load().mpc_lqr_kkt_fused_route(*plan._bind))
+        if kernel < 0:
+            _check(kernel, "mpc_lqr_kkt_fused_route")
+        return kernel
 
     # -- (5) pnqp -------------------------------------------------------------------------------
     def pnqp(self, H, q, lower, upper, x_init=None, n_iter=20, want_Hfree=True, want_lu=False):

@@ -296,6 +296,17 @@ def _step_forward(ctx, cfg, x_init, given, views):
     return new_x, new_u, n_qp, costs, full_du_norm, alphas.mean()
 
 
+def _open_backward(ctx, dl_dx, dl_du):
+    """What both backwards start from: the saved tensors, zero cotangents where autograd passes none, the forward's bounds and promise."""
+    x_init, C, c, F, f, new_x, new_u = ctx.saved_tensors
+    if dl_dx is None:
+        dl_dx = torch.zeros_like(new_x)
+    if dl_du is None:
+        dl_du = torch.zeros_like(new_u)
+    return (x_init, C, c, F, f, new_x, new_u, dl_dx, dl_du,
+            StepOptions(u_lower=ctx.u_lower, u_upper=ctx.u_upper, c_symmetric=ctx.c_symmetric))
+
+
 class _LQRStepFn(Function):
     """One autograd node type for every LQRStep.  (The reference defines a new Function class inside each
     LQRStep(...) call, mpc/lqr_step.py:275; a class object is only ever freed by the cyclic garbage collector,
@@ -309,14 +320,8 @@ class _LQRStepFn(Function):
 
     @staticmethod
     def backward(ctx, dl_dx, dl_du, *unused):
-        x_init, C, c, F, f, new_x, new_u = ctx.saved_tensors
-        if dl_dx is None:
-            dl_dx = torch.zeros_like(new_x)
-        if dl_du is None:
-            dl_du = torch.zeros_like(new_u)
-        g = _native.backend().kkt_backward(
-            C, c, F, None if _is_empty(f) else f, new_x, new_u, dl_dx, dl_du,
-            StepOptions(u_lower=ctx.u_lower, u_upper=ctx.u_upper, c_symmetric=ctx.c_symmetric))
+        x_init, C, c, F, f, new_x, new_u, dl_dx, dl_du, opts = _open_backward(ctx, dl_dx, dl_du)
+        g = _native.backend().kkt_backward(C, c, F, None if _is_empty(f) else f, new_x, new_u, dl_dx, dl_du, opts)
         df = g["df"] if g["df"] is not None else torch.Tensor()
         return None, g["dx_init"], g["dC"], g["dc"], g["dF"], df
 
@@ -364,17 +369,12 @@ class _LQRStepSharedFn(Function):
 
     @staticmethod
     def backward(ctx, dl_dx, dl_du, *unused):
-        x_init, C, c, F, f, new_x, new_u = ctx.saved_tensors
-        if dl_dx is None:
-            dl_dx = torch.zeros_like(new_x)
-        if dl_du is None:
-            dl_du = torch.zeros_like(new_u)
+        x_init, C, c, F, f, new_x, new_u, dl_dx, dl_du, opts = _open_backward(ctx, dl_dx, dl_du)
         T, B = ctx.T, x_init.shape[0]
         bases = (C, c, F, f)
         Ce, ce, Fe, fe = (_expand_shared(t, k, T, B) for k, t in enumerate(bases))
         fe = None if _is_empty(fe) else fe
         needs, shared = ctx.needs_input_grad[2:6], ctx.shared
-        opts = StepOptions(u_lower=ctx.u_lower, u_upper=ctx.u_upper, c_symmetric=ctx.c_symmetric)
         be = _native.backend()
         if hasattr(be, "kkt_backward_shared") and not any(n and not s for n, s in zip(needs, shared)):
             g = be.kkt_backward_shared(Ce, ce, Fe, fe, new_x, new_u, dl_dx, dl_du, opts, tuple(bool(n) for n in needs))
