@@ -321,6 +321,28 @@ int mpc_lqr_kkt_fused_route(const mpc_lqr_problem *p, const mpc_lqr_options *o, 
                             const void *dC, const void *dc, const void *dF, const void *df, const void *dx_init, const void *dx_out,
                             const void *du_out, const int32_t *status, const void *workspace, int64_t workspace_bytes);
 
+/* (ABI 9, additive) (4c) with the kernel named by the caller.  kernel = 0 (MPC_KKT_NONE): the three entries above, unchanged in code,
+ * text and result.  An exact MPC_KKT_* code: that kernel launches, or the call is refused with MPC_E_DIMS and a text that names the
+ * kernel and the first thing it misses (float32, MPC_OPT_C_SYMMETRIC, a linear model, its sizes, its alignments); nothing is launched,
+ * nothing else is tried.  MPC_KKT_PREFER_NARROW asks for a family: the padded 32/8 kernel on ONE 16-row state tile -- n_state <= 16,
+ * n_ctrl <= 8; MPC_KKT_MFMA40_NARROW16 where n_state, n_ctrl are multiples of 4 and C, F sit on 16 bytes, else MPC_KKT_MFMA40_NARROW4 --
+ * wherever it takes the call and neither 12/4 kernel takes the sizes (shapes up to 12/4 keep their faster kernels); every other call
+ * is routed as kernel = 0 routes it.  Codes 6 and 7 are never chosen by kernel = 0.  Any other code: MPC_E_ARG.  The shared checks
+ * (problem, options, NULL arguments, df with f, the workspace's size) come first, in (4c)'s order and with its texts; the workspace is
+ * the CHOSEN kernel's: mpc_lqr_kkt_fused_kernel_workspace_bytes(p, o, kernel) -- T B 448 floats + 64 bytes for the one-tile kernels
+ * (K [T,B,8,16] | k [T,B,8] | V [T,B,256] | v,g [T,B,32] | dx [T,B,16] | du [T,B,8]) against T B 1392 for the two-tile ones; o may be
+ * NULL there (sizes alone decide).  The route query launches nothing and sets no error state on a legal call. */
+#define MPC_KKT_MFMA40_NARROW16 6      /* forced only: one state tile, 16-byte gathers */
+#define MPC_KKT_MFMA40_NARROW4 7       /* forced only: one state tile, dword gathers */
+#define MPC_KKT_PREFER_NARROW 100      /* a family, not a kernel: 6, else 7, else the order of kernel 0 */
+int64_t mpc_lqr_kkt_fused_kernel_workspace_bytes(const mpc_lqr_problem *p, const mpc_lqr_options *o, int kernel);
+int mpc_lqr_kkt_fused_kernel(const mpc_lqr_problem *p, const mpc_lqr_options *o, int kernel, const void *dl_dx, const void *dl_du,
+                             void *dC, void *dc, void *dF, void *df, void *dx_init, void *dx_out, void *du_out, int32_t *status,
+                             void *workspace, int64_t workspace_bytes, void *stream);
+int mpc_lqr_kkt_fused_kernel_route(const mpc_lqr_problem *p, const mpc_lqr_options *o, int kernel, const void *dl_dx, const void *dl_du,
+                                   const void *dC, const void *dc, const void *dF, const void *df, const void *dx_init, const void *dx_out,
+                                   const void *du_out, const int32_t *status, const void *workspace, int64_t workspace_bytes);
+
 /* (4d) The closed-form part (4) for a cost and a linear model that the whole batch SHARES -- C [T,n,n] or [n,n], c, F, f
  *     likewise, handed to the kernels as stride-0 views: the gradient of a shared tensor is the SUM over the batch of (4)'s
  *     per-problem blocks, and this entry writes those sums without ever writing the blocks:

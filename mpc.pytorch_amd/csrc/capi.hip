@@ -568,6 +568,9 @@ static bool kkt_kernel_takes(int kernel, const StepParams<float> &sp, const KktP
     // every other shape up to 32/8, and 32/8 itself off the 16-byte grid: the padded instantiations (round 6)
     case MPC_KKT_MFMA40_PAD16: return kkt_fused_mfma40_pad16_supported(sp, ws);
     case MPC_KKT_MFMA40_PAD4: return kkt_fused_mfma40_pad_supported(sp, ws);
+    // the padded instantiations on one state tile (n_state <= 16), in a workspace packed for it: forced only (kkt_fused_route_kernel)
+    case MPC_KKT_MFMA40_NARROW16: return kkt_fused_mfma40_narrow16_supported(sp, ws);
+    case MPC_KKT_MFMA40_NARROW4: return kkt_fused_mfma40_narrow_supported(sp, ws);
     }
     return false;
 }
@@ -581,17 +584,35 @@ struct KktKernel {
     KktLaunch launch;
     int64_t (*ws_bytes)(int T, int B);       // (a padded instantiation pads to the exact kernel's layout: the same workspace)
     const char *nobody;
+    bool forced_only;                        // never proposed by kkt_first: asked for by code or by family (mpc_lqr_kkt_fused_kernel)
+    const char *name, *sizes, *views;        // what a call that names this kernel and is refused by it is told
 };
 static const char kkt_nobody12[] = "mpc_lqr_kkt_fused: the workspace must be 16-byte aligned";
 static const char kkt_nobody40[] = "mpc_lqr_kkt_fused: the workspace must be 16-byte aligned (tensor bounds 4-byte aligned)";
+static const char kkt_nobody_narrow[] = "mpc_lqr_kkt_fused_kernel: the workspace must be 16-byte aligned (tensor bounds 4-byte aligned)";
+static const char kkt_views12[] = "C, c, F, x*, u*, dl_dx, dl_du, dC, dF and the workspace 16-byte aligned, strides multiples of 4";
+static const char kkt_views_ws[] = "the workspace 16-byte aligned (tensor bounds 4-byte aligned)";
+static const char kkt_views40[] = "every block, output and the workspace 16-byte aligned, strides multiples of 4 (tensor bounds 4-byte aligned)";
+static const char kkt_views16[] = "C and F 16-byte aligned with strides multiples of 4, the workspace 16-byte aligned (tensor bounds 4-byte aligned)";
 static const KktKernel kkt_order[] = {
-    {MPC_KKT_DPP16, launch_kkt_fused_dpp16, kkt_fused_dpp16_workspace_bytes, kkt_nobody12},
-    {MPC_KKT_DPP16_PAD, launch_kkt_fused_dpp16_pad, kkt_fused_dpp16_workspace_bytes, kkt_nobody12},
-    {MPC_KKT_MFMA40, launch_kkt_fused_mfma40, kkt_fused_mfma40_workspace_bytes, kkt_nobody40},
-    {MPC_KKT_MFMA40_PAD16, launch_kkt_fused_mfma40_pad16, kkt_fused_mfma40_workspace_bytes, kkt_nobody40},
-    {MPC_KKT_MFMA40_PAD4, launch_kkt_fused_mfma40_pad, kkt_fused_mfma40_workspace_bytes, kkt_nobody40},
+    {MPC_KKT_DPP16, launch_kkt_fused_dpp16, kkt_fused_dpp16_workspace_bytes, kkt_nobody12, false,
+     "MPC_KKT_DPP16", "n_state = 12, n_ctrl = 4", kkt_views12},
+    {MPC_KKT_DPP16_PAD, launch_kkt_fused_dpp16_pad, kkt_fused_dpp16_workspace_bytes, kkt_nobody12, false,
+     "MPC_KKT_DPP16_PAD", "n_state <= 12, n_ctrl <= 4", kkt_views_ws},
+    {MPC_KKT_MFMA40, launch_kkt_fused_mfma40, kkt_fused_mfma40_workspace_bytes, kkt_nobody40, false,
+     "MPC_KKT_MFMA40", "n_state = 32, n_ctrl = 8", kkt_views40},
+    {MPC_KKT_MFMA40_PAD16, launch_kkt_fused_mfma40_pad16, kkt_fused_mfma40_workspace_bytes, kkt_nobody40, false,
+     "MPC_KKT_MFMA40_PAD16", "n_state <= 32, n_ctrl <= 8, both multiples of 4", kkt_views16},
+    {MPC_KKT_MFMA40_PAD4, launch_kkt_fused_mfma40_pad, kkt_fused_mfma40_workspace_bytes, kkt_nobody40, false,
+     "MPC_KKT_MFMA40_PAD4", "n_state <= 32, n_ctrl <= 8", kkt_views_ws},
+    // one state tile, in their own packed workspace (448 floats a problem-step).  Forced only: the recorded routes of kernel = 0 stay
+    {MPC_KKT_MFMA40_NARROW16, launch_kkt_fused_mfma40_narrow16, kkt_fused_mfma40_narrow_workspace_bytes, kkt_nobody_narrow, true,
+     "MPC_KKT_MFMA40_NARROW16", "n_state <= 16, n_ctrl <= 8, both multiples of 4", kkt_views16},
+    {MPC_KKT_MFMA40_NARROW4, launch_kkt_fused_mfma40_narrow4, kkt_fused_mfma40_narrow_workspace_bytes, kkt_nobody_narrow, true,
+     "MPC_KKT_MFMA40_NARROW4", "n_state <= 16, n_ctrl <= 8", kkt_views_ws},
 };
-static_assert(MPC_KKT_DPP16 == 1 && MPC_KKT_DPP16_PAD == 2 && MPC_KKT_MFMA40 == 3 && MPC_KKT_MFMA40_PAD16 == 4 && MPC_KKT_MFMA40_PAD4 == 5,
+static_assert(MPC_KKT_DPP16 == 1 && MPC_KKT_DPP16_PAD == 2 && MPC_KKT_MFMA40 == 3 && MPC_KKT_MFMA40_PAD16 == 4 && MPC_KKT_MFMA40_PAD4 == 5 &&
+              MPC_KKT_MFMA40_NARROW16 == 6 && MPC_KKT_MFMA40_NARROW4 == 7 && sizeof(kkt_order) / sizeof(kkt_order[0]) == 7,
               "kkt_order[code - 1] is the row of `code`");
 
 // the first kernel of the order that takes the call (query: its sizes, dtype and flags), or NULL
@@ -599,8 +620,27 @@ static const KktKernel *kkt_first(const mpc_lqr_problem *p, const StepParams<flo
 {
     if (p->dtype != MPC_F32) return nullptr;
     for (const KktKernel &k : kkt_order)
-        if (kkt_kernel_takes(k.code, sp, a, query)) return &k;
+        if (!k.forced_only && kkt_kernel_takes(k.code, sp, a, query)) return &k;
     return nullptr;
+}
+
+// What every route checks once it knows where the call is heading (the kernel whose workspace it must fit) and who takes its views:
+// mpc_lqr_kkt_fused's refusals in its order, then `nobody` where no taker is left (no_kernel: "legal, but no fused kernel").
+static KktRoute kkt_route_shared(const mpc_lqr_problem *p, const KktPointers &a, int64_t workspace_bytes, const KktKernel *taker,
+                                 const KktKernel *heading, const char *nobody, bool nobody_is_no_kernel)
+{
+    KktRoute r = {0, nullptr, false, MPC_KKT_NONE, 0};
+    const auto refuse = [&r](int code, const char *msg, bool no_kernel = false) { r.code = code; r.msg = msg; r.no_kernel = no_kernel; return r; };
+    if (p->B == 0) return r;                     // (the entry succeeds and launches nothing)
+    if (!a.dl_dx || !a.dl_du || !a.dC || !a.dc || !a.dx_init) return refuse(MPC_E_NULL, "kkt_fused: NULL argument");
+    if (p->T > 1 && !a.dF) return refuse(MPC_E_NULL, "kkt_fused: dF is NULL");
+    if ((a.df != nullptr) != (p->f != nullptr && p->T > 1)) return refuse(MPC_E_NULL, "kkt_fused: df goes with f");
+    if ((a.dx_out == nullptr) != (a.du_out == nullptr)) return refuse(MPC_E_NULL, "kkt_fused: pass both dx_out and du_out, or neither");
+    r.bytes = heading->ws_bytes(p->T, p->B);
+    if (!a.workspace || workspace_bytes < r.bytes) return refuse(MPC_E_ARG, "workspace too small (see mpc_lqr_kkt_fused_workspace_bytes)");
+    if (!taker) return refuse(MPC_E_DIMS, nobody, nobody_is_no_kernel);
+    r.kernel = taker->code;
+    return r;
 }
 
 // Which fused kernel takes this backward.  Launches nothing, sets no error state, allocates nothing; never cached.  The refusals
@@ -615,16 +655,46 @@ KktRoute kkt_fused_route(const StepParams<float> &sp, const mpc_lqr_problem *p, 
     if (!heading)
         return refuse(MPC_E_DIMS, "mpc_lqr_kkt_fused: needs fp32, n_state <= 32, n_ctrl <= 8, and "
                                   "MPC_OPT_C_SYMMETRIC (otherwise: mpc_lqr_kkt_prepare + mpc_lqr_step + mpc_lqr_kkt_grads)", true);
-    if (p->B == 0) return r;                     // (the entry succeeds and launches nothing)
-    if (!a.dl_dx || !a.dl_du || !a.dC || !a.dc || !a.dx_init) return refuse(MPC_E_NULL, "kkt_fused: NULL argument");
-    if (p->T > 1 && !a.dF) return refuse(MPC_E_NULL, "kkt_fused: dF is NULL");
-    if ((a.df != nullptr) != (p->f != nullptr && p->T > 1)) return refuse(MPC_E_NULL, "kkt_fused: df goes with f");
-    if ((a.dx_out == nullptr) != (a.du_out == nullptr)) return refuse(MPC_E_NULL, "kkt_fused: pass both dx_out and du_out, or neither");
-    r.bytes = heading->ws_bytes(p->T, p->B);
-    if (!a.workspace || workspace_bytes < r.bytes) return refuse(MPC_E_ARG, "workspace too small (see mpc_lqr_kkt_fused_workspace_bytes)");
-    if (!taker) return refuse(MPC_E_DIMS, heading->nobody, true);
-    r.kernel = taker->code;
-    return r;
+    return kkt_route_shared(p, a, workspace_bytes, taker, heading, heading->nobody, true);
+}
+
+// "<entry>: <kernel> needs <what>" for a call that names a kernel (thread-local: the text outlives the route that points at it)
+static const char *kkt_named_refusal(const KktKernel &k, const char *what)
+{
+    static thread_local std::string text;
+    text = std::string("mpc_lqr_kkt_fused_kernel: ") + k.name + " needs " + what;
+    return text.c_str();
+}
+
+// The same decision for a call that asks for a kernel (mpc_lqr_kkt_fused_kernel): 0 = nobody asked, kkt_fused_route itself; an exact
+// MPC_KKT_* code = that kernel or a refusal that names it and the first thing it misses (never "no kernel": the caller asked for one);
+// MPC_KKT_PREFER_NARROW = the one-tile kernels, 16-byte gathers first, where they take the call and no 12/4-family kernel takes its
+// sizes -- those are faster up to 12/4 -- and the order of kernel = 0 everywhere else.
+KktRoute kkt_fused_route_kernel(const StepParams<float> &sp, const mpc_lqr_problem *p, const KktPointers &a, int64_t workspace_bytes, int kernel)
+{
+    if (kernel == MPC_KKT_NONE) return kkt_fused_route(sp, p, a, workspace_bytes);
+    KktRoute r = {0, nullptr, false, MPC_KKT_NONE, 0};
+    const auto refuse = [&r](int code, const char *msg) { r.code = code; r.msg = msg; return r; };
+    const auto row = [](int code) { return &kkt_order[code - 1]; };
+    const bool f32 = p->dtype == MPC_F32;
+    if (kernel == MPC_KKT_PREFER_NARROW) {
+        const KktKernel *taker = nullptr;
+        if (!f32 || kkt_kernel_takes(MPC_KKT_DPP16, sp, a, true) || kkt_kernel_takes(MPC_KKT_DPP16_PAD, sp, a, true) ||
+            !kkt_kernel_takes(MPC_KKT_MFMA40_NARROW4, sp, a, true))
+            return kkt_fused_route(sp, p, a, workspace_bytes);
+        // (a view the dword kernel refuses -- the workspace, tensor bounds -- the two-tile kernels refuse as well: nobody takes it)
+        for (int code : {MPC_KKT_MFMA40_NARROW16, MPC_KKT_MFMA40_NARROW4})
+            if (!taker && kkt_kernel_takes(code, sp, a)) taker = row(code);
+        return kkt_route_shared(p, a, workspace_bytes, taker, taker ? taker : row(MPC_KKT_MFMA40_NARROW4), kkt_nobody_narrow, true);
+    }
+    if (kernel < 1 || kernel > (int)(sizeof(kkt_order) / sizeof(kkt_order[0])))
+        return refuse(MPC_E_ARG, "mpc_lqr_kkt_fused_kernel: unknown kernel code (MPC_KKT_*)");
+    const KktKernel &k = *row(kernel);
+    if (!f32) return refuse(MPC_E_DIMS, kkt_named_refusal(k, "float32"));
+    if (!sp.c_symmetric) return refuse(MPC_E_DIMS, kkt_named_refusal(k, "MPC_OPT_C_SYMMETRIC"));
+    if (sp.env.kind) return refuse(MPC_E_DIMS, kkt_named_refusal(k, "a linear model (no simulator)"));
+    if (!kkt_kernel_takes(kernel, sp, a, true)) return refuse(MPC_E_DIMS, kkt_named_refusal(k, k.sizes));
+    return kkt_route_shared(p, a, workspace_bytes, kkt_kernel_takes(kernel, sp, a) ? &k : nullptr, &k, kkt_named_refusal(k, k.views), false);
 }
 
 // the argument checks of mpc_lqr_kkt_fused, and of mpc_lqr_kkt_fused_route, which answers for the same arguments
@@ -673,7 +743,7 @@ int mpc_lqr_abi_version(void) { return MPC_LQR_ABI_VERSION; }
 const char *mpc_lqr_build_info(void)
 {
     return "libmpc_lqr_hip gfx950 (CDNA4) | kernels: lqr_step_generic<f32,f64>, lqr_step_mfma16<f32,f64>, lqr_step_dpp16<f32>, lqr_step_dpp16_padded<f32>, "
-           "lqr_step_tiny<f32,f64>, lqr_step_wave1<f32>, lqr_step_mfma40<f32>, lqr_step_mfma40_padded<f32>, lqr_step_mfma40_narrow<f32>, nn_rollout<f32>, nn_linearize<f32>, nn_param_grad<f32>, env_linearize, env_param_grad<f32,f64>, kkt_grads, kkt_grads_shared<f32>, kkt_fused<f32>, kkt_fused_padded<f32>, pnqp, traj_cost, select_best, slew_augment<f32,f64> | built " __DATE__ " " __TIME__;
+           "lqr_step_tiny<f32,f64>, lqr_step_wave1<f32>, lqr_step_mfma40<f32>, lqr_step_mfma40_padded<f32>, lqr_step_mfma40_narrow<f32>, nn_rollout<f32>, nn_linearize<f32>, nn_param_grad<f32>, env_linearize, env_param_grad<f32,f64>, kkt_grads, kkt_grads_shared<f32>, kkt_fused<f32>, kkt_fused_padded<f32>, kkt_fused_narrow<f32>, pnqp, traj_cost, select_best, slew_augment<f32,f64> | built " __DATE__ " " __TIME__;
 }
 
 const char *mpc_lqr_last_error(void) { return g_last_error.c_str(); }
@@ -840,7 +910,22 @@ int64_t mpc_lqr_kkt_fused_workspace_bytes(const mpc_lqr_problem *p)
     StepParams<float> s = make_params<float>(&q, nullptr, nullptr);
     s.c_symmetric = 1;
     const KktKernel *heading = kkt_first(&q, s, KktPointers(), true);
-    return (heading ? heading : &kkt_order[sizeof(kkt_order) / sizeof(kkt_order[0]) - 1])->ws_bytes(p->T, p->B);
+    return (heading ? heading : &kkt_order[MPC_KKT_MFMA40_PAD4 - 1])->ws_bytes(p->T, p->B);
+}
+
+int64_t mpc_lqr_kkt_fused_kernel_workspace_bytes(const mpc_lqr_problem *p, const mpc_lqr_options *o, int kernel)
+{
+    if (!p) return 0;
+    if (kernel >= 1 && kernel <= (int)(sizeof(kkt_order) / sizeof(kkt_order[0]))) return kkt_order[kernel - 1].ws_bytes(p->T, p->B);
+    if (kernel == MPC_KKT_PREFER_NARROW && p->dtype == MPC_F32 && check_problem(p, false, false) == MPC_OK && check_options(p, o) == MPC_OK) {
+        // where the family rule of kkt_fused_route_kernel heads for a one-tile kernel: sizes, dtype and flags (no options: as vouched)
+        StepParams<float> s = make_params<float>(p, o, nullptr);
+        if (!o) s.c_symmetric = 1;
+        if (!kkt_kernel_takes(MPC_KKT_DPP16, s, KktPointers(), true) && !kkt_kernel_takes(MPC_KKT_DPP16_PAD, s, KktPointers(), true) &&
+            kkt_kernel_takes(MPC_KKT_MFMA40_NARROW4, s, KktPointers(), true))
+            return kkt_order[MPC_KKT_MFMA40_NARROW4 - 1].ws_bytes(p->T, p->B);
+    }
+    return kernel == MPC_KKT_NONE || kernel == MPC_KKT_PREFER_NARROW ? mpc_lqr_kkt_fused_workspace_bytes(p) : 0;
 }
 
 int mpc_lqr_kkt_fused(const mpc_lqr_problem *p, const mpc_lqr_options *o, const void *dl_dx, const void *dl_du,
@@ -866,6 +951,37 @@ int mpc_lqr_kkt_fused_route(const mpc_lqr_problem *p, const mpc_lqr_options *o, 
     if (rc) return rc;
     const KktRoute r = kkt_fused_route(kkt_fused_params(p, o, (int32_t *)status), p,
                                        KktPointers{dl_dx, dl_du, dC, dc, dF, df, dx_init, dx_out, du_out, workspace}, workspace_bytes);
+    if (r.code && !r.no_kernel) return fail(r.code, r.msg);
+    return r.kernel;                             // (MPC_KKT_NONE: a legal call that no fused kernel takes, or an empty batch)
+}
+
+int mpc_lqr_kkt_fused_kernel(const mpc_lqr_problem *p, const mpc_lqr_options *o, int kernel, const void *dl_dx, const void *dl_du,
+                             void *dC, void *dc, void *dF, void *df, void *dx_init, void *dx_out, void *du_out, int32_t *status,
+                             void *workspace, int64_t workspace_bytes, void *stream)
+{
+    if (kernel == MPC_KKT_NONE)
+        return mpc_lqr_kkt_fused(p, o, dl_dx, dl_du, dC, dc, dF, df, dx_init, dx_out, du_out, status, workspace, workspace_bytes, stream);
+    const int rc = check_kkt_fused(p, o);
+    if (rc) return rc;
+    const StepParams<float> sp = kkt_fused_params(p, o, status);
+    const KktRoute r = kkt_fused_route_kernel(sp, p, KktPointers{dl_dx, dl_du, dC, dc, dF, df, dx_init, dx_out, du_out, workspace},
+                                              workspace_bytes, kernel);
+    if (r.code) return fail(r.code, r.msg);
+    if (!r.kernel) return MPC_OK;                // (an empty batch)
+    return kkt_order[r.kernel - 1].launch(sp, (const float *)dl_dx, (const float *)dl_du, (float *)dC, (float *)dc, (float *)dF, (float *)df,
+                                          (float *)dx_init, (float *)dx_out, (float *)du_out, (float *)workspace, 0.2f, 10, (hipStream_t)stream);
+}
+
+int mpc_lqr_kkt_fused_kernel_route(const mpc_lqr_problem *p, const mpc_lqr_options *o, int kernel, const void *dl_dx, const void *dl_du,
+                                   const void *dC, const void *dc, const void *dF, const void *df, const void *dx_init, const void *dx_out,
+                                   const void *du_out, const int32_t *status, const void *workspace, int64_t workspace_bytes)
+{
+    if (kernel == MPC_KKT_NONE)
+        return mpc_lqr_kkt_fused_route(p, o, dl_dx, dl_du, dC, dc, dF, df, dx_init, dx_out, du_out, status, workspace, workspace_bytes);
+    const int rc = check_kkt_fused(p, o);
+    if (rc) return rc;
+    const KktRoute r = kkt_fused_route_kernel(kkt_fused_params(p, o, (int32_t *)status), p,
+                                              KktPointers{dl_dx, dl_du, dC, dc, dF, df, dx_init, dx_out, du_out, workspace}, workspace_bytes, kernel);
     if (r.code && !r.no_kernel) return fail(r.code, r.msg);
     return r.kernel;                             // (MPC_KKT_NONE: a legal call that no fused kernel takes, or an empty batch)
 }

@@ -50,6 +50,9 @@ struct KktRoute {
     int64_t bytes;                 // the workspace that kernel needs
 };
 KktRoute kkt_fused_route(const StepParams<float> &sp, const mpc_lqr_problem *p, const KktPointers &a, int64_t workspace_bytes);
+// ... for a call that asks for a kernel: 0 = the line above, an exact MPC_KKT_* code, or the family MPC_KKT_PREFER_NARROW
+KktRoute kkt_fused_route_kernel(const StepParams<float> &sp, const mpc_lqr_problem *p, const KktPointers &a, int64_t workspace_bytes,
+                                int kernel);
 
 // generic path (lqr_generic.hip)
 template <typename real> int launch_step_generic(const StepParams<real> &p, int phase_mask, hipStream_t st);
@@ -165,6 +168,17 @@ int launch_kkt_fused_mfma40_pad(const StepParams<float> &p, const float *dl_dx, 
 int launch_kkt_fused_mfma40(const StepParams<float> &p, const float *dl_dx, const float *dl_du, float *dC, float *dc, float *dF,
                             float *df, float *dx_init, float *dx_out, float *du_out, float *ws, float decay, int max_ls,
                             hipStream_t st);
+// ... and the padded instantiation on ONE state tile (-DMPC_MFMA40_XT=1, lqr_mfma40_narrow4kkt.o / _narrow16kkt.o): the padded predicates with
+// n_state <= 16, and a workspace of their own -- K [T,B,8,16] | k | V [T,B,256] | v,g [T,B,32] | (dx [T,B,16] | du): 448 floats a problem-step
+bool kkt_fused_mfma40_narrow_supported(const StepParams<float> &p, const float *ws);
+bool kkt_fused_mfma40_narrow16_supported(const StepParams<float> &p, const float *ws);
+int64_t kkt_fused_mfma40_narrow_workspace_bytes(int T, int B);
+int launch_kkt_fused_mfma40_narrow16(const StepParams<float> &p, const float *dl_dx, const float *dl_du, float *dC, float *dc, float *dF,
+                                     float *df, float *dx_init, float *dx_out, float *du_out, float *ws, float decay, int max_ls,
+                                     hipStream_t st);
+int launch_kkt_fused_mfma40_narrow4(const StepParams<float> &p, const float *dl_dx, const float *dl_du, float *dC, float *dc, float *dF,
+                                    float *df, float *dx_init, float *dx_out, float *du_out, float *ws, float decay, int max_ls,
+                                    hipStream_t st);
 
 // NNDynamics inside the kernels: rollout / line search and Jacobian on MFMA, 16 problems per wave (nn_dynamics.hip)
 int nn_budget(const mpc_mlp_dynamics *net, int ns, int nc);     // bit 0: the rollout kernels take this network, bit 1: the linearisation ones

@@ -101,10 +101,11 @@ MPC_DEV unsigned load_uniform_u32(const unsigned *g)
 MPC_DEV void sched_fence() { __builtin_amdgcn_sched_barrier(0); }
 // an opaque register-to-register identity (see mfma40::pick)
 MPC_DEV void pin(float &x) { asm volatile("" : "+v"(x)); }
-// Compiled nine times (Makefile): the step kernels on the three-slot sweep ring (launch_step_mfma40), the same with
+// Compiled eleven times (Makefile): the step kernels on the three-slot sweep ring (launch_step_mfma40), the same with
 // -DMPC_MFMA40_SWEEP_NSTAGE=2 (launch_step_mfma40_ring2), with -DMPC_MFMA40_KKT the fused KKT backward (three slots); the padded
 // instantiation -DMPC_MFMA40_PAD=4 | 16 on two slots, as step kernels and as fused KKT backward (four objects); and the padded step
-// kernels on one state tile, -DMPC_MFMA40_XT=1 with either granule, on three slots (launch_step_mfma40_narrow4 / _narrow16).
+// kernels on one state tile, -DMPC_MFMA40_XT=1 with either granule, on three slots (launch_step_mfma40_narrow4 / _narrow16), and
+// that tile's fused KKT backward the same way (launch_kkt_fused_mfma40_narrow4 / _narrow16).
 #ifndef MPC_MFMA40_SWEEP_NSTAGE
 #define MPC_MFMA40_SWEEP_NSTAGE 3              // (lqr_mfma40_body.h: why the sweep looks two timesteps ahead)
 #endif
@@ -244,7 +245,22 @@ template <int MODE> __global__ void __launch_bounds__(64, 1) lqr_kkt_fused_mfma4
 }
 }  // namespace
 
-#ifdef MPC_MFMA40_PAD
+#if defined(MPC_MFMA40_PAD) && MPC_MFMA40_XT == 1
+// the NARROW instantiation of the padded fused backward (-DMPC_MFMA40_KKT -DMPC_MFMA40_PAD=4 | 16 -DMPC_MFMA40_XT=1 on three sweep slots,
+// lqr_mfma40_narrow4kkt.o / _narrow16kkt.o): n_state <= 16 on one state tile, in a workspace packed for it.  Forced only (capi.hip: kkt_order).
+#if MPC_MFMA40_PAD == 4
+bool kkt_fused_mfma40_narrow_supported(const StepParams<float> &p, const float *ws) { return kkt_fused_mfma40_pad_supported(p, ws) && p.ns <= 16; }
+bool kkt_fused_mfma40_narrow16_supported(const StepParams<float> &p, const float *ws) { return kkt_fused_mfma40_pad16_supported(p, ws) && p.ns <= 16; }
+// floats: K [T,B,8,16] | k [T,B,8] | V [T,B,256] | v,g [T,B,32] | (dx [T,B,16] | du [T,B,8] when the caller keeps none): 448 a problem-step
+int64_t kkt_fused_mfma40_narrow_workspace_bytes(int T, int B)
+{
+    return (int64_t)T * B * (8 * MPC_MFMA40_NS_ + 8 + 256 * MPC_MFMA40_XT * MPC_MFMA40_XT + 32 * MPC_MFMA40_XT + MPC_MFMA40_N_) * 4 + 64;
+}
+#define MPC_KF40_LAUNCH launch_kkt_fused_mfma40_narrow4
+#else
+#define MPC_KF40_LAUNCH launch_kkt_fused_mfma40_narrow16
+#endif
+#elif defined(MPC_MFMA40_PAD)
 // the PADDED instantiation (round 6; -DMPC_MFMA40_KKT -DMPC_MFMA40_PAD=4 on the two-slot sweep ring, lqr_mfma40_padkkt.o): any n_state <= 32,
 // n_ctrl <= 8, dword gathers -- nothing but 4-byte alignment asked of the caller's blocks; the workspace (the library's padded layout) on 16
 #if MPC_MFMA40_PAD == 4
@@ -292,7 +308,9 @@ int MPC_KF40_LAUNCH(const StepParams<float> &p_in, const float *dl_dx, const flo
 {
     StepParams<float> p = p_in;
     const long TB = (long)p.T * p.B;
-    float *K = ws, *k = K + TB * 256, *V = k + TB * 8, *vg = V + TB * 1024, *dx = vg + TB * 64, *du = dx + TB * 32;
+    // (two state tiles: 256 | 8 | 1024 | 64 | 32 | 8 words a problem-step; one: 128 | 8 | 256 | 32 | 16 | 8)
+    float *K = ws, *k = K + TB * (8 * MPC_MFMA40_NS_), *V = k + TB * 8, *vg = V + TB * (256 * MPC_MFMA40_XT * MPC_MFMA40_XT),
+          *dx = vg + TB * (32 * MPC_MFMA40_XT), *du = dx + TB * MPC_MFMA40_NS_;
     if (dx_out && du_out) { dx = dx_out; du = du_out; }
     p.new_x = dx;
     p.new_u = du;

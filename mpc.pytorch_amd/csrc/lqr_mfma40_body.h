@@ -163,9 +163,11 @@ struct KktArgs40 {
     const float *dl_dx, *dl_du;     // [T,B,32], [T,B,8]: the nested problem's linear term is c = -(dl_dx | dl_du)  (:315-320, :338)
     float *dF, *df, *dx_init;       // dF [T-1,B,32,40]: lambda_{t+1}, dlambda_{t+1} parked in the first 64 words of block t
                                     // (kkt_outer_kernel's convention, kkt_wave.hip); df [T-1,B,32] or NULL; dx_init [B,32]
-    float *Vws;                     // workspace [T,B,1024]: V_t as the sweep holds it (four D-layout tiles, 16 B per lane)
-    float *vgws;                    // workspace [T,B,64]: v_t | g_t
+    float *Vws;                     // workspace [T,B,256 XT^2]: V_t as the sweep holds it (XT^2 D-layout tiles, 16 B per lane)
+    float *vgws;                    // workspace [T,B,32 XT]: v_t | g_t
 };
+// words of a problem-step in those two: 1024 and 32 + 32 at two state tiles, 256 and 16 + 16 at one (the narrow workspace is packed)
+constexpr int VWS_WORDS = 256 * XT * XT, VGWS_WORDS = 32 * XT, VGWS_G = 16 * XT;
 // pass 2's stage: F | K_t | record (v_{t+1}, g_{t+1}, k_t) | V_{t+1}; three slots, the DMA two timesteps ahead
 constexpr unsigned KOFF_F = 0, KOFF_K = 4 * NS * N, KOFF_R = KOFF_K + KBYTES, KOFF_V = KOFF_R + 512, KSTAGE_BYTES = KOFF_V + 1024 * XT * XT;   // 5120, 6144, 6656, 10752
 #ifdef MPC_KF40_VFULL
@@ -175,8 +177,10 @@ constexpr int KSLOTS = 3, KDMA_PER_STAGE_EXACT = 10;           // 5 (F) + 1 (K) 
 #endif
 #ifndef MPC_KF40_VFULL
 // pass 2 of the fused backward: F (gathered in the padded instantiation: CH_F instructions) + K + record + three V tiles
-// (+ 3 in the padded instantiation: u*_t and its tensor bounds, words 0..23 of the record, for the pinned set -- kkt_pinned_lds)
-constexpr int KDMA_PER_STAGE = PADK ? CH_F + 5 + 3 : KDMA_PER_STAGE_EXACT;
+// (+ 3 in the padded instantiation: u*_t and its tensor bounds, words 0..23 of the record, for the pinned set -- kkt_pinned_lds);
+// one state tile has the one V tile (0,0)
+constexpr int KDMA_V = XT > 1 ? 3 : 1;
+constexpr int KDMA_PER_STAGE = PADK ? CH_F + 5 + KDMA_V : KDMA_PER_STAGE_EXACT;
 static_assert((KSLOTS - 2) * KDMA_PER_STAGE < 64, "vmcnt is 6 bits");
 #endif
 // the constrained modes' record for the rollout that prices without C (rollout_priced): floats per problem-step
@@ -899,14 +903,14 @@ MPC_DEV void kkt_store_vvg(const KktArgs40 &kx, long tb, const Lane &L, const wv
 #ifndef MPC_KF40_VFULL
             if (I == 0 && J == 1) continue;
 #endif
-            wv::store_f32x4(kx.Vws + tb * 1024 + (XT * I + J) * 256 + 4 * L.lane, Vd[I][J]);
+            wv::store_f32x4(kx.Vws + tb * VWS_WORDS + (XT * I + J) * 256 + 4 * L.lane, Vd[I][J]);
         }
     if (L.r == 0) {
-        // (the workspace keeps its 32/8 layout at every XT: V_t 1024 words, v_t | g_t 32 + 32 -- pass 2's record is fetched from it by lane)
+        // (V_t 256 XT^2 words, v_t | g_t 16 XT + 16 XT: pass 2's record is fetched from it by lane)
 #pragma unroll
         for (int I = 0; I < XT; ++I) {
-            wv::store_f32x4(kx.vgws + tb * 64 + 16 * I + 4 * L.q, wv::f32x4{vcol[I][0], vcol[I][1], vcol[I][2], vcol[I][3]});
-            wv::store_f32x4(kx.vgws + tb * 64 + 32 + 16 * I + 4 * L.q, wv::f32x4{gcol[I][0], gcol[I][1], gcol[I][2], gcol[I][3]});
+            wv::store_f32x4(kx.vgws + tb * VGWS_WORDS + 16 * I + 4 * L.q, wv::f32x4{vcol[I][0], vcol[I][1], vcol[I][2], vcol[I][3]});
+            wv::store_f32x4(kx.vgws + tb * VGWS_WORDS + VGWS_G + 16 * I + 4 * L.q, wv::f32x4{gcol[I][0], gcol[I][1], gcol[I][2], gcol[I][3]});
         }
     }
 }
@@ -2484,10 +2488,12 @@ MPC_DEV void kstage_issue(const P &p, const RStream &d, const char *v_ptr, long 
     {
         // tiles (0,0), (1,0), (1,1): KiB 0, 2, 3 of the record (the slot keeps its 4 KiB; KiB 1 is never written nor read)
         const char *vp = v_ptr + tx * v_step + d.lo;
-        // (one state tile: V is tile (0,0) alone -- fetched three times over, the stage's instruction count is KDMA_PER_STAGE at every XT)
+        // (one state tile: V is tile (0,0) alone, 1 KiB of a 1 KiB record -- KDMA_V)
         wv::dma16_at<0>(vp, base + KOFF_V);
-        wv::dma16_at<(XT > 1 ? 2048 : 0)>(vp, base + KOFF_V);
-        wv::dma16_at<(XT > 1 ? 3072 : 0)>(vp, base + KOFF_V);
+        if (XT > 1) {
+            wv::dma16_at<2048>(vp, base + KOFF_V);
+            wv::dma16_at<3072>(vp, base + KOFF_V);
+        }
     }
 #endif
 }
@@ -2497,7 +2503,7 @@ MPC_DEV void kkt_pass2(const P &p, const Lane &L, const float *Kin, const float 
                        const float (&v0g0)[4])
 {
     const int T = p.T;
-    // record: lanes 10..17 v_{t+1} | 20..27 g_{t+1} | 28..29 k_t
+    // record: lanes 10..17 v_{t+1} | 20..27 g_{t+1} | 28..29 k_t (one state tile: 10..13 | 20..23 | 28..29 -- the lanes that carry real words)
     RStream d;
     d.c_ptr = nullptr; d.c_step = 0;
     d.lo = 16u * (unsigned)L.lane;
@@ -2515,17 +2521,17 @@ MPC_DEV void kkt_pass2(const P &p, const Lane &L, const float *Kin, const float 
     d.k_step = (long)p.B * NC * NS * 4;
     d.r_is_f = false;
     d.r_is_x = L.lane < 28;
-    d.r_active = (L.lane >= 10 && L.lane < 18) || (L.lane >= 20 && L.lane < 30);
+    d.r_active = (L.lane >= 10 && L.lane < 10 + 4 * XT) || (L.lane >= 20 && L.lane < 20 + 4 * XT) || (L.lane >= 28 && L.lane < 30);
     if (L.lane >= 28) {
         d.r_ptr = (const char *)(kin + (long)L.b * NC) + 16 * ((L.lane < 30 ? L.lane : 28) - 28);
         d.r_step = (unsigned)((long)p.B * NC * 4);
     } else {
-        const int g = L.lane >= 20 ? 8 + (L.lane - 20) : (L.lane >= 10 && L.lane < 18 ? L.lane - 10 : 0);
-        d.r_ptr = (const char *)(kx.vgws + (long)L.b * 64) + 16 * g;
-        d.r_step = (unsigned)((long)p.B * 64 * 4);
+        const int g = L.lane >= 20 ? 4 * XT + (L.lane - 20) : (L.lane >= 10 && L.lane < 10 + 4 * XT ? L.lane - 10 : 0);
+        d.r_ptr = (const char *)(kx.vgws + (long)L.b * VGWS_WORDS) + 16 * g;
+        d.r_step = (unsigned)((long)p.B * VGWS_WORDS * 4);
     }
-    const char *v_ptr = (const char *)(kx.Vws + (long)L.b * 1024);
-    const long v_step = (long)p.B * 4096;
+    const char *v_ptr = (const char *)(kx.Vws + (long)L.b * VWS_WORDS);
+    const long v_step = (long)p.B * (4 * VWS_WORDS);
 
     float alpha = 1.f;
     for (int i = 0; i < L.r; ++i) alpha *= p.ls_decay;            // column r tries decay^r
@@ -2579,7 +2585,7 @@ MPC_DEV void kkt_pass2(const P &p, const Lane &L, const float *Kin, const float 
             for (int i = 0; i < 4; ++i) a[4 * J + i] = L.r < NC ? x[i] : 0.f;
         }
         const unsigned qo = 16u * (unsigned)(L.q < 2 ? L.q : 0);
-        const f32x4 kb = wv::lds_f32x4(rec + 448 + qo);          // (this pass's record keeps the 32/8 lanes at every XT: see kkt_store_vvg)
+        const f32x4 kb = wv::lds_f32x4(rec + 448 + qo);          // (this pass's record keeps the 32/8 slots in LDS at every XT: v at 160, g at 320, k at 448)
         // every operand of this timestep out of its stage first (F's rows as A operands, V_{t+1}'s tiles, v and g), then the
         // matrix-core blocks undivided
         float fa[XT][4 * XT + 4];

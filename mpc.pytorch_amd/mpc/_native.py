@@ -21,6 +21,8 @@ IMPL_AUTO, IMPL_GENERIC, IMPL_MFMA16, IMPL_DPP16, IMPL_TINY, IMPL_MFMA40, IMPL_W
 IMPL_MFMA40_NARROW = 9      # the padded 32/8 kernel on one 16-row state tile (n_state <= 16); forced only, IMPL_AUTO never picks it
 
 KKT_NONE, KKT_DPP16, KKT_DPP16_PAD, KKT_MFMA40, KKT_MFMA40_PAD16, KKT_MFMA40_PAD4 = 0, 1, 2, 3, 4, 5      # mpc_lqr_kkt_fused_route (MPC_KKT_*)
+KKT_MFMA40_NARROW16, KKT_MFMA40_NARROW4 = 6, 7     # forced only: the padded 32/8 backward on one state tile (mpc_lqr_kkt_fused_kernel)
+KKT_PREFER_NARROW = 100                            # ... asked for as a family: 6, else 7, where they take the call and no 12/4 kernel its sizes
 KKT_GRADS_DPP16, KKT_GRADS_WAVE, KKT_GRADS_GENERIC = 1, 2, 3                                            # mpc_lqr_kkt_grads_route
 
 ABI_VERSION = 9      # include/mpc_lqr.h: MPC_LQR_ABI_VERSION
@@ -222,7 +224,8 @@ EXPORTS = ("mpc_lqr_abi_version", "mpc_lqr_build_info", "mpc_lqr_last_error", "m
            "mpc_mlp_supported", "mpc_lqr_kkt_fused_supported", "mpc_lqr_kkt_fused_workspace_bytes", "mpc_lqr_kkt_fused",
            "mpc_du_norm_reference", "mpc_slew_augment",
            "mpc_lqr_kkt_shared_supported", "mpc_lqr_kkt_shared_workspace_bytes", "mpc_lqr_kkt_grads_shared",
-           "mpc_lqr_kkt_fused_route", "mpc_lqr_kkt_grads_route")
+           "mpc_lqr_kkt_fused_route", "mpc_lqr_kkt_grads_route",
+           "mpc_lqr_kkt_fused_kernel", "mpc_lqr_kkt_fused_kernel_route", "mpc_lqr_kkt_fused_kernel_workspace_bytes")
 
 _lib = None
 
@@ -268,6 +271,10 @@ def load():
     L.mpc_lqr_kkt_fused.argtypes = [PP, OP] + [_vp] * 11 + [_i64, _vp]
     L.mpc_lqr_kkt_fused_route.argtypes = [PP, OP] + [_vp] * 11 + [_i64]
     L.mpc_lqr_kkt_grads_route.argtypes = [PP] + [_vp] * 9
+    L.mpc_lqr_kkt_fused_kernel.argtypes = [PP, OP, ctypes.c_int] + [_vp] * 11 + [_i64, _vp]
+    L.mpc_lqr_kkt_fused_kernel_route.argtypes = [PP, OP, ctypes.c_int] + [_vp] * 11 + [_i64]
+    L.mpc_lqr_kkt_fused_kernel_workspace_bytes.restype = _i64
+    L.mpc_lqr_kkt_fused_kernel_workspace_bytes.argtypes = [PP, OP, ctypes.c_int]
     L.mpc_lqr_kkt_shared_supported.argtypes = [PP]
     L.mpc_lqr_kkt_shared_workspace_bytes.restype = _i64
     L.mpc_lqr_kkt_shared_workspace_bytes.argtypes = [PP]
@@ -723,11 +730,15 @@ class HipBackend:
         p, keep = self._problem(self._zero_nominal(T, B, ns, nc, kw)[2] if nominal else x_star[0], C, c, F, f, x_star, u_star)
         return load(), dev, (T, B, ns, nc, n), kw, (x_star, u_star, dl_dx, dl_du), has_f, p, keep
 
-    def kkt_backward(self, C, c, F, f, x_star, u_star, dl_dx, dl_du, opts, impl=IMPL_AUTO):
-        """dx_init, dC, dc, dF, df of mpc/lqr_step.py:312-407 (reference), all on device."""
+    def kkt_backward(self, C, c, F, f, x_star, u_star, dl_dx, dl_du, opts, impl=IMPL_AUTO, kernel=KKT_NONE):
+        """dx_init, dC, dc, dF, df of mpc/lqr_step.py:312-407 (reference), all on device.  kernel: a KKT_* code or KKT_PREFER_NARROW
+        for the fused call (plan_kkt_backward); where no fused kernel takes the call the three-call route does, as without it."""
         if impl == IMPL_AUTO:
             # the whole backward in one call where a fused kernel takes it (up to 32/8, fp32, C vouched symmetric)
-            plan = self.plan_kkt_backward(C, c, F, f, x_star, u_star, dl_dx, dl_du, opts)
+            if kernel != KKT_NONE:
+                plan = self.plan_kkt_backward(C, c, F, f, x_star, u_star, dl_dx, dl_du, opts, kernel=kernel)
+            else:
+                plan = self.plan_kkt_backward(C, c, F, f, x_star, u_star, dl_dx, dl_du, opts)
             if plan is not None and plan.kernel != KKT_NONE:
                 return plan()
         L, dev, (T, B, ns, nc, n), kw, (x_star, u_star, dl_dx, dl_du), has_f, p, keep = self._open_kkt(C, c, F, f, x_star, u_star, dl_dx, dl_du)
@@ -774,13 +785,16 @@ class HipBackend:
         out.update(zip(names, sums))
         return out
 
-    def plan_kkt_backward(self, C, c, F, f, x_star, u_star, dl_dx, dl_du, opts, _prepared=False):
+    def plan_kkt_backward(self, C, c, F, f, x_star, u_star, dl_dx, dl_du, opts, _prepared=False, kernel=KKT_NONE):
         """Pre-bind the fused KKT backward (mpc_lqr_kkt_fused): argument structs, the gradient buffers and the workspace are
         built once, `plan()` is then a single C call that overwrites the same outputs (clone what must survive) -- what a loop
         over many backward calls of one shape wants (bench.py; an allocation-per-call caller spends as long in the allocator
         as the GPU in the kernel).  Reads dl_dx / dl_du in place at every call.  None where no fused kernel covers the
         problem (mpc_lqr_kkt_fused_supported).  The kernel is asked for once, here (mpc_lqr_kkt_fused_route -> plan.kernel); where
-        none takes exactly the views bound (KKT_NONE) plan() returns None: use kkt_backward then.  A code from the call raises."""
+        none takes exactly the views bound (KKT_NONE) plan() returns None: use kkt_backward then.  A code from the call raises.
+        kernel: KKT_NONE (the library's order), an exact KKT_* code (that kernel or an MpcError that names what it misses) or
+        KKT_PREFER_NARROW (the one-state-tile kernels KKT_MFMA40_NARROW16 / _NARROW4 for 13..16 states and what else no 12/4 kernel
+        takes); non-zero, the plan binds mpc_lqr_kkt_fused_kernel and the workspace is the chosen kernel's."""
         L, dev, (T, B, ns, nc, n), kw, (x_star, u_star, dl_dx, dl_du), has_f, pf, keep_f = \
             self._open_kkt(C, c, F, f, x_star, u_star, dl_dx, dl_du, nominal=False, prepared=_prepared)
         o, keep_o = opts.to_struct(T, B, nc, C)
@@ -789,34 +803,40 @@ class HipBackend:
         g = dict(dC=torch.empty(T, B, n, n, **kw), dc=torch.empty(T, B, n, **kw), dF=torch.empty(F.shape, **kw),
                  df=torch.empty(T - 1, B, ns, **kw) if has_f and T > 1 else (torch.empty(0, B, ns, **kw) if has_f else None),
                  dx_init=torch.empty(B, ns, **kw), dx=torch.empty(T, B, ns, **kw), du=torch.empty(T, B, nc, **kw))
-        nbytes = int(L.mpc_lqr_kkt_fused_workspace_bytes(ctypes.byref(pf)))
+        asked = int(kernel)
+        if asked != KKT_NONE:
+            nbytes = int(L.mpc_lqr_kkt_fused_kernel_workspace_bytes(ctypes.byref(pf), ctypes.byref(o), asked))
+            fn, route, head = L.mpc_lqr_kkt_fused_kernel, L.mpc_lqr_kkt_fused_kernel_route, (ctypes.byref(pf), ctypes.byref(o), asked)
+        else:
+            nbytes = int(L.mpc_lqr_kkt_fused_workspace_bytes(ctypes.byref(pf)))
+            fn, route, head = L.mpc_lqr_kkt_fused, L.mpc_lqr_kkt_fused_route, (ctypes.byref(pf), ctypes.byref(o))
         ws = torch.empty(nbytes, device=dev, dtype=torch.uint8)
         g["_keep"] = (keep_f, keep_o, ws, dl_dx, dl_du, x_star, u_star, pf, o)
-        fn = L.mpc_lqr_kkt_fused
-        args = (ctypes.byref(pf), ctypes.byref(o), dl_dx.data_ptr(), dl_du.data_ptr(), g["dC"].data_ptr(), g["dc"].data_ptr(),
-                g["dF"].data_ptr(), _ptr(g["df"]) if (has_f and T > 1) else None, g["dx_init"].data_ptr(), g["dx"].data_ptr(),
-                g["du"].data_ptr(), None, ws.data_ptr(), nbytes)
-        kernel = int(L.mpc_lqr_kkt_fused_route(*args))
+        args = head + (dl_dx.data_ptr(), dl_du.data_ptr(), g["dC"].data_ptr(), g["dc"].data_ptr(),
+                       g["dF"].data_ptr(), _ptr(g["df"]) if (has_f and T > 1) else None, g["dx_init"].data_ptr(), g["dx"].data_ptr(),
+                       g["du"].data_ptr(), None, ws.data_ptr(), nbytes)
+        kernel = int(route(*args))
         if kernel < 0:
-            _check(kernel, "mpc_lqr_kkt_fused_route")
+            _check(kernel, route.__name__)
 
         def run(stream=None):
             if kernel == KKT_NONE:               # a legal call that no fused kernel takes: kkt_backward's three calls take anything
                 return None
             rc = fn(*args, torch.cuda.current_stream(dev).cuda_stream if stream is None else stream)
             if rc != 0:
-                _check(rc, "mpc_lqr_kkt_fused")
+                _check(rc, fn.__name__)
             return g
-        run.outputs, run.kernel, run._bind = g, kernel, args
+        run.outputs, run.kernel, run._bind, run._route = g, kernel, args, route
         return run
 
     @staticmethod
     def kkt_route(plan):
         """The KKT_* code of the fused kernel that takes exactly what `plan` has bound, KKT_NONE where none does
         (mpc_lqr_kkt_fused_route; nothing is launched)."""
-        kernel = int(load().mpc_lqr_kkt_fused_route(*plan._bind))
+        route = getattr(plan, "_route", None) or load().mpc_lqr_kkt_fused_route
+        kernel = int(route(*plan._bind))
         if kernel < 0:
-            _check(kernel, "mpc_lqr_kkt_fused_route")
+            _check(kernel, route.__name__)
         return kernel
 
     # -- (5) pnqp -------------------------------------------------------------------------------

@@ -266,7 +266,7 @@ def _host_scalar_async(dev_scalar):
 
 class _StepConfig:
     """What one LQRStep(...) call fixes for its autograd node (closure state of the reference's factory)."""
-    __slots__ = ("solve", "no_op_forward", "delta_space", "current_x", "current_u", "u_lower", "u_upper", "c_symmetric", "T")
+    __slots__ = ("solve", "no_op_forward", "delta_space", "current_x", "current_u", "u_lower", "u_upper", "c_symmetric", "T", "narrow_kkt_kernel")
 
 
 def _step_forward(ctx, cfg, x_init, given, views):
@@ -277,6 +277,7 @@ def _step_forward(ctx, cfg, x_init, given, views):
     # garbage collector cannot see -- every differentiated solve would pin its tensors forever.)
     ctx.u_lower, ctx.u_upper = cfg.u_lower, cfg.u_upper
     ctx.c_symmetric = cfg.c_symmetric
+    ctx.narrow_kkt_kernel = cfg.narrow_kkt_kernel
     if cfg.no_op_forward:
         ctx.save_for_backward(x_init, *given, cfg.current_x, cfg.current_u)
         return cfg.current_x, cfg.current_u
@@ -321,7 +322,9 @@ class _LQRStepFn(Function):
     @staticmethod
     def backward(ctx, dl_dx, dl_du, *unused):
         x_init, C, c, F, f, new_x, new_u, dl_dx, dl_du, opts = _open_backward(ctx, dl_dx, dl_du)
-        g = _native.backend().kkt_backward(C, c, F, None if _is_empty(f) else f, new_x, new_u, dl_dx, dl_du, opts)
+        # (the keyword only where the flag is on: a backend that knows none is never handed it)
+        kw = dict(kernel=_native.KKT_PREFER_NARROW) if ctx.narrow_kkt_kernel else {}
+        g = _native.backend().kkt_backward(C, c, F, None if _is_empty(f) else f, new_x, new_u, dl_dx, dl_du, opts, **kw)
         df = g["df"] if g["df"] is not None else torch.Tensor()
         return None, g["dx_init"], g["dC"], g["dc"], g["dF"], df
 
@@ -412,7 +415,8 @@ def LQRStep(n_state,
             no_op_forward=False,
             c_symmetric=False,
             reference_du_norm=False,
-            shared_grad_kernel=False):
+            shared_grad_kernel=False,
+            narrow_kkt_kernel=False):
     """A single step of the box-constrained iLQR solver.
 
     Required: n_state, n_ctrl, T.  The returned callable takes (x_init [B,ns], C [T,B,n,n],
@@ -437,6 +441,10 @@ def LQRStep(n_state,
     returns their gradients in those shapes, summed over the batch inside the kernels (`_LQRStepSharedFn`,
     mpc_lqr_kkt_grads_shared) when every argument that needs a gradient is shared.  `reference_du_norm` with a batch, and
     views the caller expanded themselves, keep the per-problem route.
+
+    narrow_kkt_kernel (not in the reference; off by default): the fused backward asks for the one-state-tile kernels
+    (`KKT_PREFER_NARROW`, mpc_lqr_kkt_fused_kernel) -- 13 to 16 states, and smaller shapes no 12/4 kernel takes, in float32 under
+    `c_symmetric`; every other backward is routed as without it.  The batch-shared backward keeps its route.
     """
     opts = StepOptions(u_lower=u_lower, u_upper=u_upper, u_zero_I=u_zero_I, delta_u=delta_u,
                        linesearch_decay=linesearch_decay, max_linesearch_iter=max_linesearch_iter,
@@ -508,6 +516,7 @@ def LQRStep(n_state,
     cfg.u_lower, cfg.u_upper = u_lower, u_upper
     cfg.c_symmetric = bool(c_symmetric)
     cfg.T = T
+    cfg.narrow_kkt_kernel = bool(narrow_kkt_kernel)
 
     def apply(x_init, C, c, F, f=None):
         if shared_grad_kernel and any(_is_shared(t, k) for k, t in enumerate((C, c, F, f))):

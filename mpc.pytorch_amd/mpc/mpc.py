@@ -175,7 +175,8 @@ class MPC(Module):
                  back_eps=1e-7, n_batch=None, linesearch_decay=0.2, max_linesearch_iter=10,
                  exit_unconverged=True, detach_unconverged=True, backprop=True, slew_rate_penalty=None,
                  prev_ctrl=None, not_improved_lim=5, best_cost_eps=1e-4, reference_du_norm=False,
-                 narrow_step_kernel=False, shared_grad_kernel=False, weight_grad_kernel=False, planned_network_slew=False):
+                 narrow_step_kernel=False, narrow_kkt_kernel=False, shared_grad_kernel=False, weight_grad_kernel=False,
+                 planned_network_slew=False):
         super().__init__()
         assert (u_lower is None) == (u_upper is None)
         assert max_linesearch_iter > 0
@@ -228,6 +229,14 @@ class MPC(Module):
         # narrow kernel's time against the padded one is a measurement of docs/history/r16.md, not a promise.  The
         # differentiable ending and the KKT backward do not look at the flag
         self.narrow_step_kernel = bool(narrow_step_kernel)
+        # OPT-IN: the differentiable ending's backward asks for the one-state-tile fused KKT kernels (LQRStep(narrow_kkt_kernel=True):
+        # _native.KKT_PREFER_NARROW -- 13 to 16 states, float32, C symmetric; every other backward is routed as without it).  With a
+        # slew_rate_penalty (12/4 differentiates at 16/4) the ending then also makes the symmetry promise the plain ending makes --
+        # `_c_symmetric`, which the slew loop established on the AUGMENTED C, and `_slew_compose` adds symmetric blocks only -- so
+        # that its backward is the fused one at all; flag off it makes none and takes the three-call route, as ever.  Where the
+        # loop's first step flagged a C that is not symmetric no promise is made and the gradients are the flag-off solve's.
+        # Off by default: the padded kernel is what existing tests pin, the narrow one's time is docs/history/r19.md's measurement
+        self.narrow_kkt_kernel = bool(narrow_kkt_kernel)
         # OPT-IN: a QuadCost / LinDx given in batch-shared form (C [T,n,n] or [n,n], c [T,n] or [n], F [T-1,ns,n] or [ns,n], f
         # likewise) reaches the final no-op step UN-expanded, whose backward then sums the gradients over the batch inside the
         # kernels (lqr_step._LQRStepSharedFn, mpc_lqr_kkt_grads_shared) instead of writing one [n,n] block per problem for
@@ -703,7 +712,8 @@ class MPC(Module):
             linesearch_decay=self.linesearch_decay, max_linesearch_iter=self.max_linesearch_iter,
             delta_space=True, current_x=x, current_u=u, back_eps=self.back_eps,
             no_op_forward=no_op_forward, c_symmetric=no_op_forward and getattr(self, "_c_symmetric", False),
-            reference_du_norm=self.reference_du_norm and not no_op_forward, shared_grad_kernel=shared_grad_kernel)
+            reference_du_norm=self.reference_du_norm and not no_op_forward, shared_grad_kernel=shared_grad_kernel,
+            **(dict(narrow_kkt_kernel=True) if self.narrow_kkt_kernel else {}))
         empty = torch.empty(0, dtype=x_init.dtype, device=x_init.device)
         return step(x_init, C, c, F, f if f is not None else empty)
 
@@ -728,7 +738,10 @@ class MPC(Module):
             true_cost=a_cost, true_dynamics=a_dyn, delta_u=self.delta_u,
             linesearch_decay=self.linesearch_decay, max_linesearch_iter=self.max_linesearch_iter,
             delta_space=True, current_x=ax, current_u=u, back_eps=self.back_eps, no_op_forward=no_op_forward,
-            reference_du_norm=self.reference_du_norm and not no_op_forward)
+            reference_du_norm=self.reference_du_norm and not no_op_forward,
+            # (`narrow_kkt_kernel` only: the promise of the plain ending, see __init__)
+            **(dict(narrow_kkt_kernel=True, c_symmetric=no_op_forward and getattr(self, "_c_symmetric", False))
+               if self.narrow_kkt_kernel else {}))
         empty = torch.empty(0, **kw)
         out = step(ax_init, aC, ac, aF, af if af is not None else empty)
         return (out[0][:, :, nc:],) + tuple(out[1:])
