@@ -245,6 +245,13 @@ int mpc_lqr_step(const mpc_lqr_problem *p, const mpc_lqr_options *o, const mpc_l
 int mpc_lqr_step_route(const mpc_lqr_problem *p, const mpc_lqr_options *o, const mpc_lqr_outputs *out,
                        const void *workspace, int64_t workspace_bytes, int impl, int *ring);
 
+/* (ABI 9, additive; a diagnostic) How many launches of this process took the resident-F build of the 12/4 step kernel: mode 0 (no
+ * bounds, no mask, 2 <= T <= 64, not sweep-only) on the two-slot ring at a batch of at most one wavefront per SIMD keeps a share of F
+ * in LDS between sweep and rollout -- the same kernel with the same results bit for bit, which is why mpc_lqr_step_route does not
+ * tell it apart.  MPC_DPP16_RESIDENT=0|1 in the environment forces it off / on where it applies (read when the library loads; with
+ * MPC_DPP16_RING_DYNAMIC set, at every launch). */
+int64_t mpc_lqr_resident_launches(void);
+
 /* (ABI 8) Where mpc_lqr_step (this p, o, impl; out->K / out->k NULL; a workspace of mpc_lqr_workspace_bytes) leaves the
  * solutions k_t of its sweep's box QPs inside `workspace`: byte offset of k[0][0][0] and the ELEMENT strides of its T and B
  * axes -- the array a later call at the same nominal may pass as o->qp_start (workspace + offset; that later call may be

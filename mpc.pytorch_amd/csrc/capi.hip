@@ -1,6 +1,7 @@
 // capi.hip -- extern "C" entry points of libmpc_lqr_hip.so (declared in include/mpc_lqr.h).
 // Argument validation + dtype / kernel dispatch; no computation happens on the host.
 #include <algorithm>
+#include <atomic>
 #include <cmath>
 #include <cstdio>
 #include <cstdlib>
@@ -26,6 +27,7 @@ struct DeviceFacts {
     int simds;
     int ring40_force;    // 0 = pick by mode and batch, 2 / 3 = MPC_MFMA40_RING
     bool sticky;         // false with MPC_DPP16_RING_DYNAMIC set: the switch is re-read at every launch (the tests flip it)
+    int resident;        // MPC_DPP16_RESIDENT: 0 / 1, -1 = not set (the default, see dpp16_resident)
 };
 static const DeviceFacts &device_facts()
 {
@@ -43,6 +45,8 @@ static const DeviceFacts &device_facts()
         const char *force40 = getenv("MPC_MFMA40_RING");         // "2" / "3": the 32/8 kernel's sweep ring, read at load
         if (force40 && (force40[0] == '2' || force40[0] == '3')) d.ring40_force = force40[0] - '0';
         d.sticky = getenv("MPC_DPP16_RING_DYNAMIC") == nullptr;
+        const char *res = getenv("MPC_DPP16_RESIDENT");          // "0" / "1": A/B switch of the resident-F build, read like MPC_DPP16_RING
+        d.resident = (res && (res[0] == '0' || res[0] == '1')) ? res[0] - '0' : -1;
         return d;
     }();
     return f;
@@ -54,6 +58,29 @@ static int dpp16_ring_force()
     // MPC_DPP16_RING_DYNAMIC=1 (the test suite): the switch follows the environment from launch to launch
     const char *force = getenv("MPC_DPP16_RING");
     return (force && (force[0] == '2' || force[0] == '4')) ? force[0] - '0' : 0;
+}
+
+// The mode-0 12/4 step on the two-slot ring with a share of F kept in LDS between sweep and rollout (lqr_dpp16_res.o): 39 KiB a wave,
+// so only while one wavefront per SIMD holds the batch -- beyond, 40 KiB would halve the occupancy the short ring is there for.
+#ifndef MPC_DPP16_RESIDENT_DEFAULT
+#define MPC_DPP16_RESIDENT_DEFAULT 1
+#endif
+static std::atomic<int64_t> g_resident_launches{0};          // mpc_lqr_resident_launches
+static bool dpp16_resident(const StepParams<float> &q)
+{
+    const DeviceFacts &f = device_facts();
+    int on = f.resident;
+    if (!f.sticky) {                       // MPC_DPP16_RING_DYNAMIC=1 (the test suite): the switch follows the environment
+        const char *e = getenv("MPC_DPP16_RESIDENT");
+        on = (e && (e[0] == '0' || e[0] == '1')) ? e[0] - '0' : -1;
+    }
+    // Unforced, only where the launch is bound by its traffic: the kept blocks cost the wavefront's own chain ~3.5 us (the copy, the choice
+    // of base and of DMA source at every timestep), which shows wherever the chain is the launch -- paired, MI355X: B = 2048 +3.6 us,
+    // 3072 +3.5, 3584 +1.2, 3840 -0.5, 4096 -1.75 (docs/history/r20.md).  Beyond 15/16 of one wavefront per SIMD it pays.
+    const int waves = (q.B + 3) / 4;
+    if (on < 0) on = (MPC_DPP16_RESIDENT_DEFAULT && 16 * (long)waves > 15 * (long)f.simds) ? 1 : 0;
+    return on != 0 && q.bound_mode == MPC_BOUND_NONE && !q.zero_mask && q.T >= 2 && q.T <= 64 /* dpp16::RG_STEPS */ && !q.sweep_only &&
+           (q.B + 3) / 4 <= f.simds;
 }
 
 // The 32/8 kernel's sweep ring: three slots (the DMA two timesteps ahead: address-translation misses behind another kernel
@@ -457,7 +484,14 @@ static int launch_routed(const StepRoute &r, const StepParams<float> &q, hipStre
     switch (r.kernel) {
     case MPC_IMPL_GENERIC: return launch_step_generic<float>(q, r.phase, st);
     case MPC_IMPL_MFMA16: return launch_step_mfma16(q, st);
-    case MPC_IMPL_DPP16: return r.ring == 2 ? launch_step_dpp16_ring2(q, st) : launch_step_dpp16(q, st);
+    case MPC_IMPL_DPP16:
+        // (the route's answer stays "impl 3, ring 2": the resident-F build is the same kernel with the same results, bit for bit)
+        if (r.ring == 2 && dpp16_resident(q)) {
+            g_resident_launches.fetch_add(1, std::memory_order_relaxed);
+            return launch_step_dpp16_res(q, st);
+        }
+        if (r.ring == 2) return launch_step_dpp16_ring2(q, st);
+        return launch_step_dpp16(q, st);
     case MPC_IMPL_TINY: return launch_step_tiny<float>(q, st);
     case MPC_IMPL_MFMA40: return r.ring == 2 ? launch_step_mfma40_ring2(q, st) : launch_step_mfma40(q, st);
     case MPC_IMPL_WAVE1: return launch_step_wave1(q, st);
@@ -765,6 +799,8 @@ int mpc_lqr_step(const mpc_lqr_problem *p, const mpc_lqr_options *o, const mpc_l
     return p->dtype == MPC_F32 ? step_impl<float>(p, o, out, workspace, workspace_bytes, impl, 3, nullptr, st)
                                : step_impl<double>(p, o, out, workspace, workspace_bytes, impl, 3, nullptr, st);
 }
+
+int64_t mpc_lqr_resident_launches(void) { return g_resident_launches.load(std::memory_order_relaxed); }
 
 int mpc_lqr_step_route(const mpc_lqr_problem *p, const mpc_lqr_options *o, const mpc_lqr_outputs *out, const void *workspace,
                        int64_t workspace_bytes, int impl, int *ring)

@@ -349,6 +349,10 @@ MPC_DEV double row_sum_f64(double x)
 // like every padded sweep but gives its second pass the deep ring's 36 KiB)
 #ifdef MPC_KF_LDS_BYTES
 #define MPC_DPP16_LDS (MPC_KF_LDS_BYTES)
+#elif defined(MPC_DPP16_RESIDENT)
+// (the resident-F compilation, lqr_dpp16_res.o: seven 3072-byte blocks of F behind the ring -- lqr_dpp16_body.h, RES_STAGES)
+#define MPC_DPP16_LDS (MPC_DPP16_NSTAGE * 9216 + 7 * 3072)
+static_assert(MPC_DPP16_LDS <= 40960, "resident F: a wavefront's quarter of the CU's 160 KiB");
 #else
 #define MPC_DPP16_LDS (MPC_DPP16_NSTAGE * 9216)
 #endif
@@ -675,6 +679,11 @@ bool dpp16_pad_supported(const StepParams<float> &p)
 #define MPC_DPP16_TAKES(p) dpp16_pad_supported(p)
 #elif MPC_DPP16_NSTAGE == 4
 #define MPC_DPP16_LAUNCH launch_step_dpp16
+#elif defined(MPC_DPP16_RESIDENT)
+// ... and a fifth time with -DMPC_DPP16_RESIDENT (on the 2-slot ring) as launch_step_dpp16_res: mode 0 with a share of F kept in LDS
+// between sweep and rollout (lqr_dpp16_body.h, RESK), 39 KiB a wave -- for batches of at most one wavefront per SIMD (capi.hip)
+#define MPC_DPP16_LAUNCH launch_step_dpp16_res
+bool dpp16_supported(const StepParams<float> &p);
 #else
 #define MPC_DPP16_LAUNCH launch_step_dpp16_ring2
 bool dpp16_supported(const StepParams<float> &p);
@@ -687,12 +696,17 @@ int MPC_DPP16_LAUNCH(const StepParams<float> &p, hipStream_t st)
     if (!MPC_DPP16_TAKES(p)) { set_last_error(dpp16::PADK ? "dpp16 (padded): needs fp32, n_state <= 12, n_ctrl <= 4, max_linesearch_iter <= 16" : "dpp16: needs n_state = 12, n_ctrl = 4, fp32, 16-byte aligned blocks"); return MPC_E_DIMS; }
     if (!p.Kk || (uintptr_t)p.Kk % 16 != 0) { set_last_error("dpp16: gain workspace missing or misaligned"); return MPC_E_NULL; }
     if (!p.sweep_only && (!p.new_x || !p.new_u)) { set_last_error("dpp16: new_x / new_u is NULL"); return MPC_E_NULL; }
-    static_assert(MPC_DPP16_LDS == dpp16::LDS_TOTAL, "LDS layout out of sync");
+    static_assert(MPC_DPP16_LDS == dpp16::LDS_RES_TOTAL, "LDS layout out of sync");
     const dim3 grid((p.B + 3) / 4), block(64);
+#ifdef MPC_DPP16_RESIDENT
+    if (p.bound_mode != MPC_BOUND_NONE || p.zero_mask || p.T > dpp16::RG_STEPS) { set_last_error("dpp16 (resident F): mode 0 only"); return MPC_E_ARG; }
+    hipLaunchKernelGGL((lqr_step_dpp16_kernel<0>), grid, block, 0, st, p);          // (the one mode this compilation instantiates)
+#else
     if (p.bound_mode != MPC_BOUND_NONE) hipLaunchKernelGGL((lqr_step_dpp16_kernel<2>), grid, block, 0, st, p);
     else if (p.zero_mask) hipLaunchKernelGGL((lqr_step_dpp16_kernel<1>), grid, block, 0, st, p);
     else if (p.T <= dpp16::RG_STEPS) hipLaunchKernelGGL((lqr_step_dpp16_kernel<0>), grid, block, 0, st, p);
     else hipLaunchKernelGGL((lqr_step_dpp16_kernel<3>), grid, block, 0, st, p);
+#endif
     hipError_t e = hipGetLastError();
     if (e != hipSuccess) {
         set_last_error((std::string("lqr_step_dpp16_kernel: ") + hipGetErrorString(e)).c_str());

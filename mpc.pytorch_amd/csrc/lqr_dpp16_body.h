@@ -352,6 +352,52 @@ enum {
     DMA_SWEEP = MPC_DPP16_PADK ? 32 : 8       // 4 C + 3 F + 1 record (padded instantiation, dwords: 16 + 12 + 4)
 #endif
 };
+// ---- Resident F (-DMPC_DPP16_RESIDENT, the compilation lqr_dpp16_res.o: mode 0 on the two-slot ring, one wavefront per SIMD) ----
+// The rollout's second read of F is the only traffic of the step the result does not need.  With one wavefront per SIMD a wave may
+// use 40 KiB of LDS; behind the 18 KiB ring sit RES_STAGES blocks of 3072 B: the four problems' F of RES_STAGES timesteps, copied
+// LDS -> LDS by the sweep (from its column-read layout into the rollout's row-read layout) and read there by every identity-priced
+// rollout pass, whose stage keeps its three F instructions -- the counted waits stand -- but points them at the record's own
+// lines (the alias idiom of dma_seek: no HBM traffic).  WHICH timesteps differs from wave to wave (res_slot): were they the same,
+// all waves would ask for nothing during those timesteps and for everything during the rest, bandwidth-bound there as before.
+#ifdef MPC_DPP16_RESIDENT
+#define MPC_DPP16_RESK 1
+#else
+#define MPC_DPP16_RESK 0
+#endif
+#ifndef MPC_DPP16_RES_T0
+#define MPC_DPP16_RES_T0 0            // >= 0: the first timestep kept; < 0: counted from the end of F's T-1 entries (-28 with stride 4: the late placement)
+#endif
+#ifndef MPC_DPP16_RES_STRIDE
+#define MPC_DPP16_RES_STRIDE 7          // (stride 7 from t = 0: even over a horizon of 50; measured 1.6-1.75 us against 0.9 us for the late placement)
+#endif
+constexpr bool RESK = MPC_DPP16_RESK != 0;
+enum { RES_STAGES = 7, RES_BLOCK = 3072, RES_T0 = MPC_DPP16_RES_T0, RES_STRIDE = MPC_DPP16_RES_STRIDE,
+       RES_BASE = LDS_TOTAL, LDS_RES_TOTAL = LDS_TOTAL + (RESK ? RES_STAGES * RES_BLOCK : 0) };
+static_assert(!RESK || (!PADK && LDS_RES_TOTAL <= 40960 && RES_STRIDE >= 1), "resident F: a quarter of a CU's LDS, exact 12/4 only");
+// The timesteps whose F wavefront `wave` keeps, as a bit mask (wave-uniform; T <= RG_STEPS = 64): entry t >= t0 with (t - t0) %
+// RES_STRIDE == wave % RES_STRIDE, the first RES_STAGES of them; a horizon of at most RES_STAGES entries is kept whole.  Worked out
+// once per launch: the loops shift and count bits.
+MPC_DEV unsigned long long res_mask(int wave, int T)
+{
+    const int nF = T - 1;
+    if (nF <= RES_STAGES) return nF > 0 ? (1ull << nF) - 1ull : 0ull;
+    const int t0 = RES_T0 >= 0 ? (int)RES_T0 : (nF + RES_T0 > 0 ? nF + RES_T0 : 0);
+    unsigned long long m = 0ull;
+#pragma unroll
+    for (int k = 0; k < RES_STAGES; ++k) {
+        const int t = t0 + wave % RES_STRIDE + k * RES_STRIDE;
+        if (t < nF) m |= 1ull << t;
+    }
+    return m;
+}
+// the resident block that holds F_t (the rank of t among the kept timesteps), or -1;  0 <= t < 64
+MPC_DEV int res_slot(unsigned long long mask, int t)
+{
+    return ((mask >> t) & 1ull) ? (int)__builtin_popcountll(mask & ((1ull << t) - 1ull)) : -1;
+}
+// a rollout stage whose F instructions fetch nothing: F_t is resident, or t = T-1, whose copy of F[T-2] nobody looks at;  0 <= t < T
+MPC_DEV bool res_alias(unsigned long long mask, int t, int T) { return t >= T - 1 || ((mask >> t) & 1ull) != 0ull; }
+
 // DMA instructions of one rollout stage: F, record, gains (+ C when priced directly, + (m, M) otherwise
 // when constraints are present)
 #if defined(MPC_PAD_PROBE_DUP) && MPC_DPP16_PADK
@@ -420,6 +466,29 @@ MPC_DEV int src_granule_C(int g, int problem_slot)
 #endif
     const int R = (g >> 2) ^ (problem_slot & 3);
     return 4 * R + ((g & 3) ^ quarter_swizzle(R));
+}
+// Resident F: the sweep's stage holds the wave's four F blocks by src_granule_cols, the rollout reads them by src_granule_rows.  Lane l
+// moves granules 64 k + l (k = 0..2) of the rollout's order: source granule s = src_granule_rows(gi) of problem slot `slot` sits at
+// position s ^ ((slot & 1) << 2) of the sweep's.  Offsets from the stage's base / the resident block's, computed once.
+struct ResLane { int src[3], dst; };
+MPC_DEV void res_lane_init(ResLane &R, int lane)
+{
+#pragma unroll
+    for (int k = 0; k < 3; ++k) {
+        const int G = 64 * k + lane, slot = G / 48, gi = G - 48 * slot;
+        R.src[k] = SF + 16 * (48 * slot + (src_granule_rows(gi) ^ ((slot & 1) << 2)));
+    }
+    R.dst = RES_BASE + 16 * lane;
+}
+// sweep ring slot `slot` (landed, read) -> resident block k.  DS instructions of a wave execute in order and the reads' data is back
+// before the writes issue: done long before the next timestep's DMA refills the slot.
+MPC_DEV void res_keep(const ResLane &R, int slot, int k)
+{
+    const unsigned sb = (unsigned)(slot * (int)STAGE_BYTES), db = (unsigned)(k * (int)RES_BLOCK + R.dst);
+    const f32x4 v0 = wv::lds_f32x4(sb + (unsigned)R.src[0]), v1 = wv::lds_f32x4(sb + (unsigned)R.src[1]), v2 = wv::lds_f32x4(sb + (unsigned)R.src[2]);
+    wv::lds_store_f32x4(db, v0);
+    wv::lds_store_f32x4(db + 1024, v1);
+    wv::lds_store_f32x4(db + 2048, v2);
 }
 
 struct Lane {
@@ -697,8 +766,10 @@ template <int MODE, bool ROLL, bool DIRECT, int K> MPC_DEV void pad_part(const D
 
 // DMA of the stage the pointers stand on into the ring slot anchored at `mid`: exactly DMA_SWEEP /
 // RollDma<MODE, DIRECT>::N instructions, all but the directly-priced rollout's gains on one M0.
+// alias_f (wave-uniform; resident F, identity-priced mode-0 rollouts only): the three F instructions re-fetch the lane's own record
+// granule -- the lines the record instruction behind them fetches anyway -- into the F block of the slot, which nobody reads then.
 template <int MODE, bool ROLL, bool DIRECT>
-MPC_DEV void stage_issue(const Dma &d, unsigned mid)
+MPC_DEV void stage_issue(const Dma &d, unsigned mid, bool alias_f = false)
 {
 #ifdef MPC_DPP16_PAD
     pad_part<MODE, ROLL, DIRECT, 0>(d, mid); pad_part<MODE, ROLL, DIRECT, 1>(d, mid);
@@ -716,9 +787,15 @@ MPC_DEV void stage_issue(const Dma &d, unsigned mid)
         wv::dma16_at<-2048, wv::DMA_C>(d.c_ptr[2], mid);
         wv::dma16_at<-1024, wv::DMA_C>(d.c_ptr[3], mid);
     }
-    wv::dma16_at<0, ROLL ? wv::DMA_LAST : wv::DMA_PLAIN>(d.f_ptr[0], mid);
-    wv::dma16_at<1024, ROLL ? wv::DMA_LAST : wv::DMA_PLAIN>(d.f_ptr[1], mid);
-    wv::dma16_at<2048, ROLL ? wv::DMA_LAST : wv::DMA_PLAIN>(d.f_ptr[2], mid);
+    if (RESK && ROLL && !DIRECT && MODE == 0 && alias_f) {
+        wv::dma16_at<0>(d.r_ptr + 3072, mid);
+        wv::dma16_at<1024>(d.r_ptr + 2048, mid);
+        wv::dma16_at<2048>(d.r_ptr + 1024, mid);
+    } else {
+        wv::dma16_at<0, ROLL ? wv::DMA_LAST : wv::DMA_PLAIN>(d.f_ptr[0], mid);
+        wv::dma16_at<1024, ROLL ? wv::DMA_LAST : wv::DMA_PLAIN>(d.f_ptr[1], mid);
+        wv::dma16_at<2048, ROLL ? wv::DMA_LAST : wv::DMA_PLAIN>(d.f_ptr[2], mid);
+    }
     wv::dma16_at<3072>(d.r_ptr, mid);
     if (ROLL && !rgm(MODE)) {
         if (DIRECT) {
@@ -783,6 +860,7 @@ template <int MODE, bool ROLL, bool DIRECT> struct Feed {
     unsigned mid;
     bool on;
     bool move_f;
+    bool alias_f;         // resident F: see stage_issue
     template <int K> MPC_DEVM void part()
     {
         if (!on) return;
@@ -804,11 +882,18 @@ template <int MODE, bool ROLL, bool DIRECT> struct Feed {
         enum { NC = (!ROLL || DIRECT) ? 4 : 0 };      // C instructions of a stage
         if (ROLL && !DIRECT) {
             // packed rollout stage: F0 F1 | F2 REC | G [G2] | moves
+            const bool alias = RESK && MODE == 0 && alias_f;
             if (K == 0) {
-                wv::dma16_at<0, wv::DMA_LAST>(d.f_ptr[0], mid);
-                wv::dma16_at<1024, wv::DMA_LAST>(d.f_ptr[1], mid);
+                if (alias) {
+                    wv::dma16_at<0>(d.r_ptr + 3072, mid);
+                    wv::dma16_at<1024>(d.r_ptr + 2048, mid);
+                } else {
+                    wv::dma16_at<0, wv::DMA_LAST>(d.f_ptr[0], mid);
+                    wv::dma16_at<1024, wv::DMA_LAST>(d.f_ptr[1], mid);
+                }
             } else if (K == 1) {
-                wv::dma16_at<2048, wv::DMA_LAST>(d.f_ptr[2], mid);
+                if (alias) wv::dma16_at<2048>(d.r_ptr + 1024, mid);
+                else wv::dma16_at<2048, wv::DMA_LAST>(d.f_ptr[2], mid);
                 wv::dma16_at<3072>(d.r_ptr, mid);
             } else if (K == 2) {
                 if (!rgm(MODE)) wv::dma16_at<-1024>(d.g_ptr, mid);
@@ -1286,9 +1371,11 @@ MPC_DEV void rg_price_terms(RoStage &s, const Lane &L)
 }
 
 template <int MODE, bool DIRECT>
-MPC_DEV void ro_read(RoStage &s, const P &p, const Lane &L, int t, int slot, unsigned zm)
+MPC_DEV void ro_read(RoStage &s, const P &p, const Lane &L, int t, int slot, unsigned zm, int res_k = -1)
 {
     const unsigned base = stage_mid<MODE, true, DIRECT>(slot) - SF;       // the lane offsets are SF-relative + SF
+    // (resident F: the rows of F_t from resident block res_k -- a wave-uniform choice of base -- where the wave kept them)
+    const unsigned fbase = (RESK && MODE == 0 && !DIRECT && res_k >= 0) ? (unsigned)((int)RES_BASE + res_k * (int)RES_BLOCK - (int)SF) : base;
     const unsigned mrec = base + RollRing<MODE, DIRECT>::MADJ;
     const unsigned gain = base + RollRing<MODE, DIRECT>::GADJ;
     s.cj = 0.f;
@@ -1316,7 +1403,7 @@ MPC_DEV void ro_read(RoStage &s, const P &p, const Lane &L, int t, int slot, uns
     // (t = T-1: a copy of F[T-2], unused)
 #pragma unroll
     for (int q = 0; q < 4; ++q) {
-        const f32x4 v = wv::lds_f32x4(base + L.aFq[q]);
+        const f32x4 v = wv::lds_f32x4(fbase + L.aFq[q]);
         s.Fr[4 * q] = v[0]; s.Fr[4 * q + 1] = v[1]; s.Fr[4 * q + 2] = v[2]; s.Fr[4 * q + 3] = v[3];
     }
     s.fj = p.f ? wv::lds_f32(base + L.aRecF) : 0.f;
@@ -1357,6 +1444,7 @@ struct RoState {
     float viol;       // > 0 once the nominal broke the dynamics somewhere
     float *out;       // this lane's element of new_x / new_u at the current timestep
     bool price_on;    // (wave-uniform) some row of this pass steps off the sweep's policy: the identity's terms are not all zero
+    unsigned long long resmask;   // (wave-uniform) resident F: the timesteps whose F this wave kept in LDS (res_mask)
     // the pair pass of the box-constrained line search: a second trial (alpha = decay) rolled out beside the first, its
     // trajectory parked in the workspace
     float xs1, cost1, du21;
@@ -1549,6 +1637,7 @@ MPC_DEV void rollout_pass(const P &p, const Lane &L, Dma &d, int wave, const Gai
     const bool use_zm = con(MODE) && p.zero_mask != nullptr;
     enum { NS = RollRing<MODE, DIRECT>::SLOTS, LA = NS - 1, ND = RollDma<MODE, DIRECT>::N };
     static_assert((LA - 1) * ND + 2 * LA < 64, "vmcnt is 6 bits");
+    constexpr bool RES = RESK && MODE == 0 && !DIRECT;          // resident F: the identity-priced passes of mode 0
     unsigned zq[NS];
 #pragma unroll
     for (int i = 0; i < NS; ++i) zq[i] = 0u;
@@ -1557,7 +1646,7 @@ MPC_DEV void rollout_pass(const P &p, const Lane &L, Dma &d, int wave, const Gai
 #pragma unroll
     for (int i = 0; i < LA; ++i) {
         if (i < T) {
-            stage_issue<MODE, true, DIRECT>(d, stage_mid<MODE, true, DIRECT>(i));
+            stage_issue<MODE, true, DIRECT>(d, stage_mid<MODE, true, DIRECT>(i), RES && res_alias(st.resmask, i, T));
             stage_move<MODE, true, DIRECT>(d, i + 1 <= T - 2);
             if (use_zm) zq[i] = zm_pick(L, zm_fetch(p, L, i));
         }
@@ -1573,7 +1662,7 @@ MPC_DEV void rollout_pass(const P &p, const Lane &L, Dma &d, int wave, const Gai
                 else tail_wait<(LA >= 2 ? LA - 2 : 0), ND>(T - 1 - t);
                 PROF_MARK(4);
                 RoStage s;
-                ro_read<MODE, DIRECT>(s, p, L, t, i, zq[i]);
+                ro_read<MODE, DIRECT>(s, p, L, t, i, zq[i], RES ? res_slot(st.resmask, t) : -1);
                 if (rgm(MODE)) {
                     s.rec = gain_get(G, t);
                     if (!DIRECT && st.price_on) rg_price_terms(s, L);
@@ -1582,7 +1671,7 @@ MPC_DEV void rollout_pass(const P &p, const Lane &L, Dma &d, int wave, const Gai
                 const int tn = t + LA;
                 ZmRaw zr = {{0u, 0u, 0u, 0u}};
                 if (use_zm && tn < T) zr = zm_fetch(p, L, tn);
-                Feed<MODE, true, DIRECT> feed = {d, stage_mid<MODE, true, DIRECT>((i + LA) % NS), tn < T, tn + 1 <= T - 2};
+                Feed<MODE, true, DIRECT> feed = {d, stage_mid<MODE, true, DIRECT>((i + LA) % NS), tn < T, tn + 1 <= T - 2, RES && tn < T && res_alias(st.resmask, tn, T)};
                 PROF_MARK(6);
                 if (MULTI) {
                     feed.template part<0>(); feed.template part<1>(); feed.template part<2>(); feed.template part<3>();
@@ -1842,6 +1931,9 @@ MPC_DEV void step_wave(const P &p)
     ss.rec2 = p.Kk + (long)T * p.B * 64 + ((long)(T - 1) * p.B + L.pb) * 4;
     {
         unsigned zq[NSTAGE] = {};
+        ResLane rl;
+        if (RESK && MODE == 0) res_lane_init(rl, lane);
+        const unsigned long long resmask = (RESK && MODE == 0) ? res_mask(wave, T) : 0ull;
         dma_seek<MODE, false, false>(d, p, L, wave);
         pad_clear(L.lane);
 #pragma unroll
@@ -1865,10 +1957,15 @@ MPC_DEV void step_wave(const P &p)
                     PROF_MARK(0);
                     SwStage s;
                     sw_read<MODE>(s, p, L, t, i, zq[i], ss.asym, ss.cmax);
+                    if (RESK && MODE == 0) {
+                        // resident F: the stage has landed and been read; keep its F blocks where the rollouts will look for them
+                        const int rk = res_slot(resmask, t);
+                        if (rk >= 0) res_keep(rl, i, rk);
+                    }
                     PROF_MARK(1);
                     ZmRaw zr = {{0u, 0u, 0u, 0u}};
                     if (MODE == 1 && t >= AHEAD) zr = zm_fetch(p, L, t - AHEAD);
-                    Feed<MODE, false, false> feed = {d, stage_mid<MODE, false, false>((i + AHEAD) % NSTAGE), t >= AHEAD, true};
+                    Feed<MODE, false, false> feed = {d, stage_mid<MODE, false, false>((i + AHEAD) % NSTAGE), t >= AHEAD, true, false};
                     PROF_MARK(2);
                     sweep_step<MODE>(p, L, s, ss, t, feed, G PROF_PASS);
                     if (MODE == 1) zq[(i + AHEAD) % NSTAGE] = zm_pick(L, zr);
@@ -1897,6 +1994,7 @@ MPC_DEV void step_wave(const P &p)
     // ---- line-searched rollout (mpc/lqr_step.py:164-261) --------------------------------------
     RoState rs;
     rs.viol = 0.f;
+    rs.resmask = (RESK && MODE == 0) ? res_mask(wave, T) : 0ull;
     float full2 = 0.f;
     if (p.on_dynamics) {
         // the caller vouches for the nominal (MPC_OPT_NOMINAL_ON_DYNAMICS): no verification in the loop
@@ -2365,7 +2463,7 @@ MPC_DEV void kkt_fused_wave(const P &p, const KktFusedArgs &k)
                         }
                     }
                 }
-                Feed<0, false, false> feed = {d, stage_mid<0, false, false>((i + AHEAD) % NSTAGE), t >= AHEAD, true};
+                Feed<0, false, false> feed = {d, stage_mid<0, false, false>((i + AHEAD) % NSTAGE), t >= AHEAD, true, false};
                 feed.template part<0>();
 
                 // lambda_t = C_x tau* + c_x + F_x' lambda_{t+1}   (:355-369; rows 0..11 of C, F_x = first 12 columns)

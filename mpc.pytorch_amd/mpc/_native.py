@@ -216,7 +216,7 @@ class Outputs(ctypes.Structure):
 
 
 EXPORTS = ("mpc_lqr_abi_version", "mpc_lqr_build_info", "mpc_lqr_last_error", "mpc_lqr_workspace_bytes",
-           "mpc_lqr_step", "mpc_lqr_step_route", "mpc_lqr_impl_supported", "mpc_lqr_qp_record", "mpc_lqr_sweep", "mpc_lqr_rollout", "mpc_lqr_kkt_grads", "mpc_lqr_kkt_prepare",
+           "mpc_lqr_step", "mpc_lqr_step_route", "mpc_lqr_resident_launches", "mpc_lqr_impl_supported", "mpc_lqr_qp_record", "mpc_lqr_sweep", "mpc_lqr_rollout", "mpc_lqr_kkt_grads", "mpc_lqr_kkt_prepare",
            "mpc_pnqp", "mpc_pnqp_lu", "mpc_traj_cost", "mpc_env_traj_cost", "mpc_env_linearize", "mpc_select_best",
            "mpc_env_param_grad_workspace_bytes", "mpc_env_param_grad",
            "mpc_mlp_workspace_bytes", "mpc_mlp_rollout", "mpc_mlp_linearize", "mpc_mlp_linearize_carry",
@@ -258,6 +258,8 @@ def load():
     PP, OP, UP = ctypes.POINTER(Problem), ctypes.POINTER(Options), ctypes.POINTER(Outputs)
     L.mpc_lqr_step.argtypes = [PP, OP, UP, _vp, _i64, ctypes.c_int, _vp]
     L.mpc_lqr_step_route.argtypes = [PP, OP, UP, _vp, _i64, ctypes.c_int, ctypes.POINTER(ctypes.c_int)]
+    L.mpc_lqr_resident_launches.restype = _i64
+    L.mpc_lqr_resident_launches.argtypes = []
     L.mpc_lqr_impl_supported.argtypes = [PP, OP, ctypes.c_int]
     L.mpc_lqr_qp_record.argtypes = [PP, OP, ctypes.c_int] + [ctypes.POINTER(_i64)] * 3
     L.mpc_lqr_sweep.argtypes = [PP, OP, UP, _vp]
