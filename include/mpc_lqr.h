@@ -99,7 +99,8 @@ enum {
                                     stays inside the simulator -- and the Jacobian [ns+1][ns+2] has the carry row (0 .. 0 1), a zero
                                     column for the previous control and the simulator's own block inside.
                                     Honoured by mpc_env_traj_cost and by mpc_lqr_step on the lane-per-problem kernel (impl 4; impl 0
-                                    routes every such call there, at every batch size), with or without `linearize`.  REFUSED
+                                    routes every such call there, at every batch size) and by impl 10, forced only (the row-per-problem
+                                    kernel's carry instantiation, float32), with or without `linearize`.  REFUSED
                                     (MPC_E_UNSUPPORTED, mpc_lqr_impl_supported answers 0) by the row-per-problem kernel (impl 6), the
                                     generic kernels (impl 1, mpc_lqr_sweep, mpc_lqr_rollout), mpc_env_linearize and
                                     mpc_env_param_grad: the differentiable ending linearises the simulator itself. */
@@ -228,14 +229,18 @@ int64_t mpc_lqr_workspace_bytes(const mpc_lqr_problem *p);
  *     tau is padded to [x(16); u(8)], a fifth of 7's matrix instructions per timestep of the sweep and a third of its staging; every
  *     mode and refusal of 7, the same workspace, the same mpc_lqr_qp_record; FORCED ONLY -- auto never picks it --, 8 = the kernel of 3 for
  *     ANY n_state <= 12, n_ctrl <= 4 (f32; round 6): tau is padded to [x(12); u(4)] by dword gathers of the staging DMA, every mode
- *     of 3, no alignment asked of any block (so also 12/4 itself where 3 refuses); float64 of these shapes stays on 2.
+ *     of 3, no alignment asked of any block (so also 12/4 itself where 3 refuses); float64 of these shapes stays on 2, 10
+ *     (MPC_IMPL_WAVE1_CARRY; additive, ABI 9 still) = the kernel of 6 for a simulator behind MPC_ENV_CTRL_CARRY, and for nothing else:
+ *     f32, n_ctrl = 1, n_state = 4 (pendulum + 1) or 6 (cart-pole + 1), with or without `linearize`, max_linesearch_iter <= 16, four
+ *     problems in 150 KiB of LDS, a whole step (no MPC_OPT_SWEEP_ONLY); FORCED ONLY -- auto keeps routing every carry call to 4, and 6
+ *     keeps refusing the flag; mpc_lqr_row_carry_pays says where its sixteen lanes a problem are worth it.
  *     Auto picks 5, 6 / 4, 3, 8, 2 (float64), 7, else 1 (float64 beyond 12/4, n_state > 32 or n_ctrl > 8, max_linesearch_iter > 16, a simulator
  *     beyond n_ctrl = 1).  The fused kernels need
  *     `workspace` (mpc_lqr_workspace_bytes, 16-byte aligned); out->K / out->k are optional there. */
 int mpc_lqr_step(const mpc_lqr_problem *p, const mpc_lqr_options *o, const mpc_lqr_outputs *out,
                  void *workspace, int64_t workspace_bytes, int impl, void *stream);
 
-/* (ABI 9, additive) Which kernel mpc_lqr_step would launch for exactly these arguments: the `impl` code 1..9 of the list above (9 only where 9 was forced), and in
+/* (ABI 9, additive) Which kernel mpc_lqr_step would launch for exactly these arguments: the `impl` code 1..10 of the list above (9 / 10 only where 9 / 10 was forced), and in
  * *ring (may be NULL) the depth of the sweep ring where the kernel has two (3: 2 or 4, 5: 2 or 3; 0 otherwise).  The same argument
  * checks and the same decision as mpc_lqr_step, nothing launched: where that call would be refused, its negative code, with the same
  * text in mpc_lqr_last_error().  0: B = 0 (mpc_lqr_step succeeds and launches nothing).  Every pointer -- the tensors of p, o and out,
@@ -259,8 +264,16 @@ int64_t mpc_lqr_resident_launches(void);
  * ignores the hint: with out->k given, that is the array). */
 int mpc_lqr_qp_record(const mpc_lqr_problem *p, const mpc_lqr_options *o, int impl, int64_t *offset_bytes, int64_t *st, int64_t *sb);
 
-/* Does kernel `impl` (1 generic, 2 fused MFMA, 3 DPP, 4 lane-per-problem, 5 MFMA sweep, 6 wavefront-per-problem, 7 padded 32/8, 8 padded 12/4, 9 narrow 16/8) accept this problem/options pair?  1 yes, 0 no. */
+/* Does kernel `impl` (1 generic, 2 fused MFMA, 3 DPP, 4 lane-per-problem, 5 MFMA sweep, 6 wavefront-per-problem, 7 padded 32/8, 8 padded 12/4, 9 narrow 16/8, 10 row-per-problem carry) accept this problem/options pair?  1 yes, 0 no. */
 int mpc_lqr_impl_supported(const mpc_lqr_problem *p, const mpc_lqr_options *o, int impl);
+
+/* (ABI 9, additive) Is the row-per-problem carry kernel (impl 10) worth forcing for this call?  The rule by which auto prefers impl 6 to
+ * impl 4 for the plain simulators, applied to the carry kernel's own LDS size: all wavefronts of the batch (four problems each) resident
+ * at once, at most two to a SIMD, as many to a CU as 160 KiB of LDS hold.  1 yes, 0 no -- 0 wherever impl 10 would refuse the call
+ * (float64, no simulator or one without MPC_ENV_CTRL_CARRY, max_linesearch_iter > 16, MPC_OPT_SWEEP_ONLY, B = 0 ...).  Silent:
+ * mpc_lqr_last_error() is left as it was.  Sizes, dtype and options only, no pointer is dereferenced; without a device the chip
+ * counts as 1024 SIMDs. */
+int mpc_lqr_row_carry_pays(const mpc_lqr_problem *p, const mpc_lqr_options *o);
 
 /* (2) The sweep alone: c_back + lqr_backward (mpc/lqr_step.py:284-296, 52-160).
  *     Writes out->K, out->k (required), out->old_costs, out->qp_iters, out->status. */

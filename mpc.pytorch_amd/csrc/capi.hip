@@ -187,6 +187,7 @@ static bool kernel_takes(int kernel, const StepParams<real> &sp, bool query = fa
         case MPC_IMPL_MFMA40_PAD: return mfma40_pad_supported(sp);
         case MPC_IMPL_MFMA40_NARROW: return mfma40_narrow_supported(sp);
         case MPC_IMPL_WAVE1: return tiny_supported(sp.ns, sp.nc) && wave1_supported(sp);
+        case MPC_IMPL_WAVE1_CARRY: return tiny_supported(sp.ns, sp.nc) && wave1_carry_supported(sp);
         }
     }
     return false;
@@ -213,6 +214,7 @@ static WsLayout ws_layout(int kernel, int T, int B, int ns, int nc)
     switch (kernel) {
     case MPC_IMPL_TINY:
     case MPC_IMPL_WAVE1:
+    case MPC_IMPL_WAVE1_CARRY:
         // one lane per problem; gains parked as [T][ns+1][B], behind them one trajectory column [T][ns+1] per line-search trial
         // lane (<= 8 per problem): 9 (ns + 1) reals per problem-step <= 504 bytes
         w.Kk = 0; w.bytes = (needK + needk) * 9;
@@ -269,13 +271,21 @@ static int64_t status_scratch_offset(const mpc_lqr_problem *p)
 // Worth its sixteen lanes while all its wavefronts are resident together, at most two to a SIMD (measured,
 // profiles/r03_experiments.md section 6: pendulum up to B = 8192, cart-pole -- 39.6 KB of LDS per wavefront --
 // up to 4096; twice that and the lane-per-problem kernel is level or ahead).
+static bool row_kernel_pays(long lds_bytes, int B)          // lds_bytes: of one wavefront (four problems)
+{
+    const long per_cu = (160L * 1024) / lds_bytes;
+    return (B + 3) / 4 <= (device_facts().simds / 4) * (per_cu < 8 ? per_cu : 8);
+}
 static bool wave1_pays(const StepParams<float> &sp)
 {
-    if (!wave1_supported(sp)) return false;
-    const long per_cu = (160L * 1024) / wave1_lds_bytes(sp);
-    return (sp.B + 3) / 4 <= (device_facts().simds / 4) * (per_cu < 8 ? per_cu : 8);
+    return wave1_supported(sp) && row_kernel_pays(wave1_lds_bytes(sp), sp.B);
 }
 static bool wave1_pays(const StepParams<double> &) { return false; }
+// ... the same rule for the carry instantiation (impl 10, forced only: mpc_lqr_row_carry_pays tells a caller where to force it)
+static bool wave1_carry_pays(const StepParams<float> &sp)
+{
+    return wave1_carry_supported(sp) && row_kernel_pays(wave1_carry_lds_bytes(sp), sp.B);
+}
 
 // ring depth of the 12/4 kernel (lqr_dpp16.hip): the unconstrained step always on the short ring; the constrained one there
 // only when the batch has more waves (4 problems each) than the chip has SIMDs (256 CUs x 4)
@@ -306,15 +316,15 @@ StepRoute step_route(const StepParams<real> &sp, const mpc_lqr_problem *p, int i
     // out->k given, no or a small workspace -- keeps the generic kernel under impl 0)
     const auto takes_now = [&](int kernel) {
         if (!kernel_takes<real>(kernel, sp)) return false;
-        if (kernel == MPC_IMPL_GENERIC || kernel == MPC_IMPL_TINY || kernel == MPC_IMPL_WAVE1) return true;
+        if (kernel == MPC_IMPL_GENERIC || kernel == MPC_IMPL_TINY || kernel == MPC_IMPL_WAVE1 || kernel == MPC_IMPL_WAVE1_CARRY) return true;
         if (sp.env.kind) return false;
         if (kernel == MPC_IMPL_MFMA40_PAD || kernel == MPC_IMPL_MFMA40_NARROW || (!f32 && kernel == MPC_IMPL_MFMA16))
             return room(layout(kernel).bytes) && aligned;
         return true;
     };
-    signed char asked[MPC_IMPL_MFMA40_NARROW + 1] = {-1, -1, -1, -1, -1, -1, -1, -1, -1, -1};      // each kernel is asked once per call
+    signed char asked[MPC_IMPL_WAVE1_CARRY + 1] = {-1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1};      // each kernel is asked once per call
     const auto takes = [&](int kernel) {
-        if (kernel < MPC_IMPL_GENERIC || kernel > MPC_IMPL_MFMA40_NARROW) return false;
+        if (kernel < MPC_IMPL_GENERIC || kernel > MPC_IMPL_WAVE1_CARRY) return false;
         if (asked[kernel] < 0) asked[kernel] = takes_now(kernel);
         return asked[kernel] != 0;
     };
@@ -360,12 +370,22 @@ StepRoute step_route(const StepParams<real> &sp, const mpc_lqr_problem *p, int i
             return r;
         }
     }
-    // MPC_ENV_CTRL_CARRY: the lane-per-problem kernel carries the control (lqr_tiny_body.h); the row-per-problem and the generic
-    // kernels call the simulator as it is and REFUSE the flag -- never a silent un-augmented answer
-    if (sp.env.carry && (!step || (impl != 0 && impl != 4)))
+    // MPC_ENV_CTRL_CARRY: the lane-per-problem kernel carries the control (lqr_tiny_body.h), and so does the row-per-problem kernel's
+    // carry instantiation (impl 10, forced only); the row-per-problem and the generic kernels call the simulator as it is and REFUSE the
+    // flag -- never a silent un-augmented answer
+    if (sp.env.carry && (!step || (impl != 0 && impl != 4 && impl != 10)))
         return refuse(MPC_E_UNSUPPORTED, "MPC_ENV_CTRL_CARRY: only mpc_lqr_step on the lane-per-problem kernel (impl 0 or 4) carries the control");
-    if (sp.env.kind && sp.env.linearize && !(step && tiny && (impl == 0 || impl == 4 || impl == 6)))
+    if (sp.env.kind && sp.env.linearize && !(step && tiny && (impl == 0 || impl == 4 || impl == 6 || impl == 10)))
         return refuse(MPC_E_ARG, "in-kernel linearisation needs the lane-per-problem kernel (n_ctrl = 1, n_state <= 6)");
+    // (impl 10 takes a simulator behind the flag and nothing else: a plain simulator or a linear model has impl 6)
+    if (impl == MPC_IMPL_WAVE1_CARRY) {
+        if (!f32) return refuse(MPC_E_DTYPE, "the row-per-problem carry kernel is fp32 only");
+        if (!step || !tiny) return refuse(MPC_E_DIMS, "the row-per-problem carry kernel needs a whole step with n_ctrl = 1, n_state = 4 or 6");
+        if (!sp.env.kind || !sp.env.carry)
+            return refuse(MPC_E_ARG, "the row-per-problem carry kernel needs a simulator behind MPC_ENV_CTRL_CARRY as true_dynamics");
+        if (!takes(impl))
+            return refuse(MPC_E_DIMS, "the row-per-problem carry kernel is float32, max_linesearch_iter <= 16, four problems in 150 KiB of LDS");
+    }
     if (sp.env.kind && (impl == 2 || impl == 3 || impl == 8))
         return refuse(MPC_E_ARG, "a simulator as true_dynamics runs on the generic kernels only");
     if (impl == MPC_IMPL_MFMA40_NARROW && !f32) return refuse(MPC_E_DTYPE, "the narrow MFMA kernel is fp32 only");
@@ -373,7 +393,7 @@ StepRoute step_route(const StepParams<real> &sp, const mpc_lqr_problem *p, int i
         return refuse(MPC_E_DIMS, "lane-per-problem / wavefront-per-problem kernel needs n_ctrl = 1, n_state <= 6");
     if (impl == 6 && !takes(MPC_IMPL_WAVE1))
         return refuse(MPC_E_DIMS, "the row-per-problem kernel is float32, max_linesearch_iter <= 16, four problems in 150 KiB of LDS");
-    if (step && (kernel == MPC_IMPL_TINY || kernel == MPC_IMPL_WAVE1)) {
+    if (step && (kernel == MPC_IMPL_TINY || kernel == MPC_IMPL_WAVE1 || kernel == MPC_IMPL_WAVE1_CARRY)) {
         // (these kernels keep Q and V as general matrices, like the reference: nothing to test, nothing to re-solve)
         const WsLayout w = layout(kernel);
         if (!room(w.bytes)) return refuse(MPC_E_ARG, "workspace too small (see mpc_lqr_workspace_bytes)");
@@ -495,6 +515,7 @@ static int launch_routed(const StepRoute &r, const StepParams<float> &q, hipStre
     case MPC_IMPL_TINY: return launch_step_tiny<float>(q, st);
     case MPC_IMPL_MFMA40: return r.ring == 2 ? launch_step_mfma40_ring2(q, st) : launch_step_mfma40(q, st);
     case MPC_IMPL_WAVE1: return launch_step_wave1(q, st);
+    case MPC_IMPL_WAVE1_CARRY: return launch_step_wave1_carry(q, st);
     case MPC_IMPL_MFMA40_PAD: return r.pad16 ? launch_step_mfma40_pad16(q, st) : launch_step_mfma40_pad4(q, st);
     case MPC_IMPL_DPP16_PAD: return launch_step_dpp16_pad(q, st);
     case MPC_IMPL_MFMA40_NARROW: return r.pad16 ? launch_step_mfma40_narrow16(q, st) : launch_step_mfma40_narrow4(q, st);
@@ -777,7 +798,7 @@ int mpc_lqr_abi_version(void) { return MPC_LQR_ABI_VERSION; }
 const char *mpc_lqr_build_info(void)
 {
     return "libmpc_lqr_hip gfx950 (CDNA4) | kernels: lqr_step_generic<f32,f64>, lqr_step_mfma16<f32,f64>, lqr_step_dpp16<f32>, lqr_step_dpp16_padded<f32>, "
-           "lqr_step_tiny<f32,f64>, lqr_step_wave1<f32>, lqr_step_mfma40<f32>, lqr_step_mfma40_padded<f32>, lqr_step_mfma40_narrow<f32>, nn_rollout<f32>, nn_linearize<f32>, nn_param_grad<f32>, env_linearize, env_param_grad<f32,f64>, kkt_grads, kkt_grads_shared<f32>, kkt_fused<f32>, kkt_fused_padded<f32>, kkt_fused_narrow<f32>, pnqp, traj_cost, select_best, slew_augment<f32,f64> | built " __DATE__ " " __TIME__;
+           "lqr_step_tiny<f32,f64>, lqr_step_wave1<f32>, lqr_step_wave1_carry<f32>, lqr_step_mfma40<f32>, lqr_step_mfma40_padded<f32>, lqr_step_mfma40_narrow<f32>, nn_rollout<f32>, nn_linearize<f32>, nn_param_grad<f32>, env_linearize, env_param_grad<f32,f64>, kkt_grads, kkt_grads_shared<f32>, kkt_fused<f32>, kkt_fused_padded<f32>, kkt_fused_narrow<f32>, pnqp, traj_cost, select_best, slew_augment<f32,f64> | built " __DATE__ " " __TIME__;
 }
 
 const char *mpc_lqr_last_error(void) { return g_last_error.c_str(); }
@@ -816,12 +837,24 @@ int mpc_lqr_step_route(const mpc_lqr_problem *p, const mpc_lqr_options *o, const
 int mpc_lqr_impl_supported(const mpc_lqr_problem *p, const mpc_lqr_options *o, int impl)
 {
     if (!p || check_problem(p, false, false) != MPC_OK || check_options(p, o) != MPC_OK) return 0;
-    if (impl < MPC_IMPL_GENERIC || impl > MPC_IMPL_MFMA40_NARROW) return 0;
-    // (MPC_ENV_CTRL_CARRY: the lane-per-problem kernel alone, see step_route)
-    if (o && o->true_dynamics && (o->true_dynamics->kind & MPC_ENV_CTRL_CARRY) && impl != MPC_IMPL_TINY) return 0;
+    if (impl < MPC_IMPL_GENERIC || impl > MPC_IMPL_WAVE1_CARRY) return 0;
+    // (MPC_ENV_CTRL_CARRY: the lane-per-problem kernel and the row-per-problem kernel's carry instantiation, see step_route)
+    if (o && o->true_dynamics && (o->true_dynamics->kind & MPC_ENV_CTRL_CARRY) && impl != MPC_IMPL_TINY && impl != MPC_IMPL_WAVE1_CARRY) return 0;
+    if (impl == MPC_IMPL_WAVE1_CARRY && o && (o->flags & MPC_OPT_SWEEP_ONLY)) return 0;      // (a whole step only)
     // sizes, dtype and options only: the alignment of the actual tensors is checked at launch
     return p->dtype == MPC_F32 ? kernel_takes<float>(impl, make_params<float>(p, o, nullptr), true)
                                : kernel_takes<double>(impl, make_params<double>(p, o, nullptr), true);
+}
+
+int mpc_lqr_row_carry_pays(const mpc_lqr_problem *p, const mpc_lqr_options *o)
+{
+    // (silent: what the argument checks say about a call impl 10 would refuse is not left behind)
+    const std::string keep = g_last_error;
+    // (sizes, dtype and options, as mpc_lqr_impl_supported -- but F may be NULL at any T: a linearising simulator has none)
+    const bool pays = p && o && check_problem(p, false, false, false) == MPC_OK && check_options(p, o) == MPC_OK && p->B > 0 &&
+                      p->dtype == MPC_F32 && !(o->flags & MPC_OPT_SWEEP_ONLY) && wave1_carry_pays(make_params<float>(p, o, nullptr));
+    g_last_error = keep;
+    return pays ? 1 : 0;
 }
 
 int mpc_lqr_qp_record(const mpc_lqr_problem *p, const mpc_lqr_options *o, int impl, int64_t *offset_bytes, int64_t *st, int64_t *sb)

@@ -18,13 +18,14 @@ void set_last_error(const char *msg);
 // the kernels behind mpc_lqr_step: the values of its `impl` argument (include/mpc_lqr.h)
 enum { MPC_IMPL_AUTO = 0, MPC_IMPL_GENERIC = 1, MPC_IMPL_MFMA16 = 2, MPC_IMPL_DPP16 = 3, MPC_IMPL_TINY = 4, MPC_IMPL_MFMA40 = 5,
        MPC_IMPL_WAVE1 = 6, MPC_IMPL_MFMA40_PAD = 7, MPC_IMPL_DPP16_PAD = 8,
-       MPC_IMPL_MFMA40_NARROW = 9 };       // (9: forced only -- impl 0 never chooses it; the narrow instantiation of 7 for n_state <= 16)
+       MPC_IMPL_MFMA40_NARROW = 9,         // (9: forced only -- impl 0 never chooses it; the narrow instantiation of 7 for n_state <= 16)
+       MPC_IMPL_WAVE1_CARRY = 10 };        // (10: forced only; the instantiation of 6 for a simulator behind MPC_ENV_CTRL_CARRY, n_state = 4 / 6)
 
 // Which kernel takes one step call and where its pieces live in the workspace (capi.hip: step_route decides, step_impl executes,
 // the queries mpc_lqr_step_route / mpc_lqr_qp_record read it off).  Host only.
 struct StepRoute {
     int code; const char *msg;     // code != 0: refused, with mpc_lqr_step's code and text (a string literal)
-    int kernel;                    // MPC_IMPL_* 1..9: the kernel that takes the call
+    int kernel;                    // MPC_IMPL_* 1..10: the kernel that takes the call
     int phase;                     // the generic kernels: 3 = sweep + rollout, 1 = sweep, 2 = rollout
     int ring;                      // 0, or the sweep ring of the 12/4 / 32/8 kernel (2 / 4, 2 / 3)
     bool pad16;                    // padded 32/8 and its narrow instantiation: 16-byte gathers
@@ -117,6 +118,10 @@ template <typename real> int launch_step_tiny(const StepParams<real> &p, hipStre
 bool wave1_supported(const StepParams<float> &p);
 long wave1_lds_bytes(const StepParams<float> &p);        // per wavefront (four problems)
 int launch_step_wave1(const StepParams<float> &p, hipStream_t st);
+// ... and its CARRY instantiation: a simulator behind MPC_ENV_CTRL_CARRY, n_state = 4 / 6, and nothing else (lqr_wave1_carry.hip)
+bool wave1_carry_supported(const StepParams<float> &p);
+long wave1_carry_lds_bytes(const StepParams<float> &p);  // per wavefront (four problems)
+int launch_step_wave1_carry(const StepParams<float> &p, hipStream_t st);
 
 // wave-per-problem trajectory kernel for 16 < n <= 64, f32 (kkt_wave.hip)
 bool traj_wave_supported(const StepParams<float> &p);

@@ -17,6 +17,9 @@
 //   P4  lane = (trial, slice of the horizon): the trials' costs (:230-232) from the LDS copies of C, c.
 //   P5  the first trial not worse than the nominal wins (else the last), its trajectory leaves LDS.
 // Written against the `wv::` lane interface: lqr_wave1.hip implements it for gfx950, tests/emu/ with lockstep fibers.
+// -DMPC_WAVE1_CARRY (lqr_wave1_carry.hip, impl 10): the same step for a shipped simulator behind MPC_ENV_CTRL_CARRY -- the slew-rate
+// augmentation z = (u_prev, x), n_state = 4 (pendulum) or 6 (cart-pole) -- with env_step_carry where P1 and P3 call env_step, as
+// lqr_tiny_body.h does; without the macro this header is the one it was.
 #pragma once
 #include <type_traits>
 #include "lqr_tiny_body.h"
@@ -67,7 +70,11 @@ MPC_HD Layout layout(const StepParams<float> &p)
 MPC_HD bool shape_supported(const StepParams<float> &p)
 {
     if (!(p.nc == 1 && p.ns >= 1 && p.ns <= 6 && p.T >= 1 && p.max_ls >= 1 && p.max_ls <= 16)) return false;
+#ifdef MPC_WAVE1_CARRY                      // the CARRY instantiation (lqr_wave1_carry.hip): a simulator behind MPC_ENV_CTRL_CARRY, nothing else
+    if (!(p.env.kind && p.env.carry && (p.ns == 4 || p.ns == 6) && p.ns == env_ns(p.env.kind) + 1)) return false;
+#else
     if (p.env.carry) return false;          // MPC_ENV_CTRL_CARRY: the lane-per-problem kernel only (this one calls env_step as it is)
+#endif
     if ((long)p.T * 49 * 16 > 160 * 1024) return false;                   // (before the sum below could overflow)
     return (long)layout(p).total * 16 <= 150 * 1024;                      // four problems per wavefront
 }
@@ -136,6 +143,12 @@ template <int NS> MPC_DEV void step_wave(const StepParams<float> &p)
         L.C += rb, L.c += rb, L.cb += rb, L.F += rb, L.f += rb, L.tau += rb, L.K += rb, L.lo += rb, L.hi += rb, L.mask += rb, L.X += rb;
     }
     const bool bounded = p.bound_mode != MPC_BOUND_NONE;
+#ifdef MPC_WAVE1_CARRY
+    // NS names the simulator (shape_supported holds n_state to env_ns(kind) + 1), so the other one's transition is not compiled in:
+    // with both, the two transitions' last stores into xn are merged into one store at a run-time index, and xn lives in scratch memory
+    EnvDesc<float> env = p.env;
+    env.kind = NS == 6 ? MPC_ENV_CARTPOLE : (p.env.kind == MPC_ENV_PENDULUM ? MPC_ENV_PENDULUM : MPC_ENV_PENDULUM_FULL);
+#endif
 
     // ------------------------------------------------------------------ P1: everything that is independent over t
     double oc = 0;
@@ -162,8 +175,13 @@ template <int NS> MPC_DEV void step_wave(const StepParams<float> &p)
         }
         if (t < T - 1) {
             if (p.env.kind && p.env.linearize) {       // F_t = d simulator / d [x;u] at the nominal
+#ifdef MPC_WAVE1_CARRY                                 // z = (u_prev, x): the carry row and the zero column around the simulator's block
+                float nxt[6], J[42];                   // (sized for either simulator, as lqr_tiny_body.h)
+                env_step_carry<float, NS - 1>(env, tau, tau[NS], nxt, J);
+#else
                 float nxt[NS > 5 ? NS : 5], J[NS * N > 30 ? NS * N : 30];
                 env_step<float>(p.env, tau, tau[NS], nxt, J);
+#endif
                 for (int m = 0; m < NS * N; ++m) wv::sm(L.F + t * NS * N + m) = J[m];
             } else {
                 const float *Ft = p.F + (long)t * p.F_st + (long)b * p.F_sb;
@@ -335,9 +353,17 @@ template <int NS> MPC_DEV void step_wave(const StepParams<float> &p)
             for (int i = 0; i < NS; ++i) wv::sm(xo + t * N + i) = x[i];
             wv::sm(xo + t * N + NS) = un;
             if (t < T - 1) {
+#ifdef MPC_WAVE1_CARRY
+                float xn[6];
+#else
                 float xn[NS > 5 ? NS : 5];
+#endif
                 if (p.env.kind) {                                           // :223-225
+#ifdef MPC_WAVE1_CARRY
+                    env_step_carry<float, NS - 1>(env, x, un, xn, nullptr);      // the control carried RAW into z+[0]
+#else
                     env_step<float>(p.env, x, un, xn, nullptr);
+#endif
                 } else {                                                    // :216-222
                     for (int i = 0; i < NS; ++i) {
                         float s = 0;

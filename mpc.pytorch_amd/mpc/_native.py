@@ -19,6 +19,7 @@ BOUND_NONE, BOUND_SCALAR, BOUND_TENSOR = 0, 1, 2
 ST_PNQP_UNCONVERGED, ST_NONFINITE, ST_NOMINAL_OFF_DYNAMICS, ST_C_ASYMMETRIC, ST_QUU_SINGULAR, ST_C_TESTED = 1, 2, 4, 8, 16, 32
 IMPL_AUTO, IMPL_GENERIC, IMPL_MFMA16, IMPL_DPP16, IMPL_TINY, IMPL_MFMA40, IMPL_WAVE1, IMPL_MFMA40_PAD, IMPL_DPP16_PAD = 0, 1, 2, 3, 4, 5, 6, 7, 8
 IMPL_MFMA40_NARROW = 9      # the padded 32/8 kernel on one 16-row state tile (n_state <= 16); forced only, IMPL_AUTO never picks it
+IMPL_WAVE1_CARRY = 10       # the row-per-problem kernel for a simulator behind ENV_CTRL_CARRY (n_state 4 / 6, float32); forced only
 
 KKT_NONE, KKT_DPP16, KKT_DPP16_PAD, KKT_MFMA40, KKT_MFMA40_PAD16, KKT_MFMA40_PAD4 = 0, 1, 2, 3, 4, 5      # mpc_lqr_kkt_fused_route (MPC_KKT_*)
 KKT_MFMA40_NARROW16, KKT_MFMA40_NARROW4 = 6, 7     # forced only: the padded 32/8 backward on one state tile (mpc_lqr_kkt_fused_kernel)
@@ -216,7 +217,7 @@ class Outputs(ctypes.Structure):
 
 
 EXPORTS = ("mpc_lqr_abi_version", "mpc_lqr_build_info", "mpc_lqr_last_error", "mpc_lqr_workspace_bytes",
-           "mpc_lqr_step", "mpc_lqr_step_route", "mpc_lqr_resident_launches", "mpc_lqr_impl_supported", "mpc_lqr_qp_record", "mpc_lqr_sweep", "mpc_lqr_rollout", "mpc_lqr_kkt_grads", "mpc_lqr_kkt_prepare",
+           "mpc_lqr_step", "mpc_lqr_step_route", "mpc_lqr_resident_launches", "mpc_lqr_impl_supported", "mpc_lqr_row_carry_pays", "mpc_lqr_qp_record", "mpc_lqr_sweep", "mpc_lqr_rollout", "mpc_lqr_kkt_grads", "mpc_lqr_kkt_prepare",
            "mpc_pnqp", "mpc_pnqp_lu", "mpc_traj_cost", "mpc_env_traj_cost", "mpc_env_linearize", "mpc_select_best",
            "mpc_env_param_grad_workspace_bytes", "mpc_env_param_grad",
            "mpc_mlp_workspace_bytes", "mpc_mlp_rollout", "mpc_mlp_linearize", "mpc_mlp_linearize_carry",
@@ -261,6 +262,7 @@ def load():
     L.mpc_lqr_resident_launches.restype = _i64
     L.mpc_lqr_resident_launches.argtypes = []
     L.mpc_lqr_impl_supported.argtypes = [PP, OP, ctypes.c_int]
+    L.mpc_lqr_row_carry_pays.argtypes = [PP, OP]
     L.mpc_lqr_qp_record.argtypes = [PP, OP, ctypes.c_int] + [ctypes.POINTER(_i64)] * 3
     L.mpc_lqr_sweep.argtypes = [PP, OP, UP, _vp]
     L.mpc_lqr_rollout.argtypes = [PP, OP, UP, _vp, _vp]
@@ -491,6 +493,18 @@ class HipBackend:
         if opts is not None:
             o, _keep = opts.to_struct(1, 1, nc, torch.empty(0, dtype=dtype))
         return bool(load().mpc_lqr_impl_supported(ctypes.byref(p), None if o is None else ctypes.byref(o), int(impl)))
+
+    def row_carry_pays(self, ns, nc, dtype, T, B, opts, like=None):
+        """mpc_lqr_row_carry_pays: is IMPL_WAVE1_CARRY worth forcing for a step of these sizes and options -- a simulator behind
+        ENV_CTRL_CARRY whose batch the row-per-problem kernel holds resident at once (auto's rule for IMPL_WAVE1, on the carry
+        kernel's LDS size)?  False wherever that kernel refuses the call.  A host call: sizes, dtype and options only (`like`: a tensor
+        of the problem's, so that tensor-valued options are bound where they live instead of being copied to the host)."""
+        p = Problem()
+        p.B, p.T, p.ns, p.nc = int(B), int(T), int(ns), int(nc)
+        p.dtype = MPC_F32 if dtype == torch.float32 else MPC_F64
+        p.x_init = 16        # (never dereferenced)
+        o, _keep = opts.to_struct(int(T), int(B), int(nc), torch.empty(0, dtype=dtype) if like is None else like)
+        return bool(load().mpc_lqr_row_carry_pays(ctypes.byref(p), ctypes.byref(o)))
 
     # -- (1) LQRStepFn.forward ------------------------------------------------------------------
     def lqr_step(self, x_init, C, c, F, f, cur_x, cur_u, opts, want_gains=False, impl=IMPL_AUTO,

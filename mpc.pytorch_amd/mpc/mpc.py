@@ -175,8 +175,8 @@ class MPC(Module):
                  back_eps=1e-7, n_batch=None, linesearch_decay=0.2, max_linesearch_iter=10,
                  exit_unconverged=True, detach_unconverged=True, backprop=True, slew_rate_penalty=None,
                  prev_ctrl=None, not_improved_lim=5, best_cost_eps=1e-4, reference_du_norm=False,
-                 narrow_step_kernel=False, narrow_kkt_kernel=False, shared_grad_kernel=False, weight_grad_kernel=False,
-                 planned_network_slew=False):
+                 narrow_step_kernel=False, narrow_kkt_kernel=False, row_carry_kernel=False, shared_grad_kernel=False,
+                 weight_grad_kernel=False, planned_network_slew=False):
         super().__init__()
         assert (u_lower is None) == (u_upper is None)
         assert max_linesearch_iter > 0
@@ -237,6 +237,15 @@ class MPC(Module):
         # loop's first step flagged a C that is not symmetric no promise is made and the gradients are the flag-off solve's.
         # Off by default: the padded kernel is what existing tests pin, the narrow one's time is docs/history/r19.md's measurement
         self.narrow_kkt_kernel = bool(narrow_kkt_kernel)
+        # OPT-IN: a slew-rate solve around a shipped simulator (`_iterate_slew` -> `_iterate_planned` with the simulator behind
+        # ENV_CTRL_CARRY) binds its step plans with _native.IMPL_WAVE1_CARRY -- a 16-lane row per problem instead of a lane per
+        # problem -- where the backend's `impl_supported` takes the step for impl 10 AND its `row_carry_pays` says the batch is small
+        # enough for the row kernel to hold it resident at once, at the sizes the loop runs at (`_row_carry_impl_kw`).  Everywhere
+        # else -- float64, a LinDx slew solve, a larger batch, a backend without the query -- IMPL_AUTO, as ever: bitwise the
+        # flag-off solve.  Off by default: auto routes every carry call to the lane-per-problem kernel and existing tests pin that;
+        # the row kernel's time against it is a measurement of docs/history/r21.md, not a promise.  The differentiable ending does
+        # not look at the flag
+        self.row_carry_kernel = bool(row_carry_kernel)
         # OPT-IN: a QuadCost / LinDx given in batch-shared form (C [T,n,n] or [n,n], c [T,n] or [n], F [T-1,ns,n] or [ns,n], f
         # likewise) reaches the final no-op step UN-expanded, whose backward then sums the gradients over the batch inside the
         # kernels (lqr_step._LQRStepSharedFn, mpc_lqr_kkt_grads_shared) instead of writing one [n,n] block per problem for
@@ -407,6 +416,11 @@ class MPC(Module):
         xb, ub = torch.empty_like(xa), torch.empty_like(ua)
         # (`narrow_step_kernel`: the forced kernel rides in the plan; its variants below keep it)
         kwi = self._narrow_impl_kw(be, xi.shape[1], ua.shape[2], xi.dtype, opts)
+        # (`row_carry_kernel`: likewise, for a simulator behind the carry.  That kernel keeps Q and V general like the lane-per-problem
+        # one and sets no MPC_ST_C_ASYMMETRIC, so there is nothing to start over from: no `on_asymmetric`)
+        kwr = self._row_carry_impl_kw(be, xi, ua, sim, opts) if not kwi else {}
+        restart = bool(kwi)
+        kwi = kwi or kwr
         variant = getattr(be, "plan_variant", None)      # (the test backends build every plan from scratch)
         # the raw stream handle, looked up once (torch.cuda.current_stream costs 4 us a call, two calls an iteration)
         stream = torch.cuda.current_stream(xa.device).cuda_stream if xa.is_cuda and variant is not None else None
@@ -451,7 +465,7 @@ class MPC(Module):
         # the narrow kernel whose first step reports the bit starts over on IMPL_AUTO plans: the nominal of iteration 0 is still
         # in (xa, ua) -- `_drive` holds iteration 1 back until the flags are in -- and the solve is the flag-off solve from there on
         return self._drive(be, launch, outputs, r, xa, ua, n_batch, stream, on_symmetric,
-                           on_asymmetric=(lambda: bind({})) if kwi else None)
+                           on_asymmetric=(lambda: bind({})) if restart else None)
 
     def _narrow_impl_kw(self, be, ns, nc, dtype, opts):
         """`narrow_step_kernel`: dict(impl=IMPL_MFMA40_NARROW) where the backend's narrow kernel takes a step of these sizes and
@@ -462,6 +476,19 @@ class MPC(Module):
                 # auto gives to the padded 32/8 kernel)
                 and not be.impl_supported(int(ns), int(nc), dtype, _native.IMPL_DPP16_PAD, opts)):
             return dict(impl=_native.IMPL_MFMA40_NARROW)
+        return {}
+
+    def _row_carry_impl_kw(self, be, xi, ua, sim, opts):
+        """`row_carry_kernel`: dict(impl=IMPL_WAVE1_CARRY) for a simulator behind ENV_CTRL_CARRY where the backend's row-per-problem
+        carry kernel takes the step (`impl_supported`) and pays at this horizon and batch (`row_carry_pays`), else {} -- the plan is
+        bound as ever, with IMPL_AUTO.  Flag off, neither predicate is asked."""
+        if not (self.row_carry_kernel and sim is not None and getattr(sim, "carry", False) and xi.dtype == torch.float32
+                and hasattr(be, "impl_supported") and hasattr(be, "row_carry_pays")):
+            return {}
+        ns, nc, T, B = int(xi.shape[1]), int(ua.shape[2]), int(ua.shape[0]), int(ua.shape[1])
+        if (be.impl_supported(ns, nc, xi.dtype, _native.IMPL_WAVE1_CARRY, opts)
+                and be.row_carry_pays(ns, nc, xi.dtype, T, B, opts, like=xi)):
+            return dict(impl=_native.IMPL_WAVE1_CARRY)
         return {}
 
     def _slew_plan(self, cost, dx, be, x_init):
