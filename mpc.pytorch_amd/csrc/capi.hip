@@ -20,45 +20,54 @@ static int fail(int code, const char *msg)
     return code;
 }
 
-// Read once per process (the first launch): the A/B switch of the 12/4 kernel's staging ring and the number of SIMDs of
-// the device the library runs on (MI355X: 256 CUs x 4), which is where the constrained step changes rings.
+// f(real()) with the `real` of a dtype the caller has checked: the float / double pair of an entry point written once
+template <typename F>
+static int by_dtype(int dtype, F &&f)
+{
+    return dtype == MPC_F32 ? f(float()) : f(double());
+}
+
+// A two-valued switch of the environment ("2" / "4", "0" / "1": its first character decides), `unset` where it is absent or says
+// anything else.
+struct EnvSwitch { const char *name; char a, b; int unset; };
+static const EnvSwitch SW_DPP16_RING = {"MPC_DPP16_RING", '2', '4', 0};              // A/B switch of the 12/4 kernel's staging ring
+static const EnvSwitch SW_MFMA40_RING = {"MPC_MFMA40_RING", '2', '3', 0};            // the 32/8 kernel's sweep ring
+static const EnvSwitch SW_DPP16_RESIDENT = {"MPC_DPP16_RESIDENT", '0', '1', -1};     // A/B switch of the resident-F build (see dpp16_resident)
+static int read_switch(const EnvSwitch &s)
+{
+    const char *e = getenv(s.name);
+    return (e && (e[0] == s.a || e[0] == s.b)) ? e[0] - '0' : s.unset;
+}
+
+// Read once per process (the first launch): the three switches and the number of SIMDs of the device the library runs on (MI355X:
+// 256 CUs x 4), which is where the constrained step changes rings.
 struct DeviceFacts {
     int ring_force;      // 0 = pick by mode and batch, 2 / 4 = MPC_DPP16_RING
     int simds;
     int ring40_force;    // 0 = pick by mode and batch, 2 / 3 = MPC_MFMA40_RING
-    bool sticky;         // false with MPC_DPP16_RING_DYNAMIC set: the switch is re-read at every launch (the tests flip it)
+    bool sticky;         // false with MPC_DPP16_RING_DYNAMIC set: the switches are re-read at every launch (the tests flip them)
     int resident;        // MPC_DPP16_RESIDENT: 0 / 1, -1 = not set (the default, see dpp16_resident)
 };
 static const DeviceFacts &device_facts()
 {
     static DeviceFacts f = [] {
         DeviceFacts d;
-        d.ring_force = 0;
-        d.ring40_force = 0;
         d.simds = 1024;
         hipDeviceProp_t prop;
         int dev = 0;
         if (hipGetDevice(&dev) == hipSuccess && hipGetDeviceProperties(&prop, dev) == hipSuccess && prop.multiProcessorCount > 0)
             d.simds = prop.multiProcessorCount * 4;
-        const char *force = getenv("MPC_DPP16_RING");            // "2" / "4": A/B switch, read at load
-        if (force && (force[0] == '2' || force[0] == '4')) d.ring_force = force[0] - '0';
-        const char *force40 = getenv("MPC_MFMA40_RING");         // "2" / "3": the 32/8 kernel's sweep ring, read at load
-        if (force40 && (force40[0] == '2' || force40[0] == '3')) d.ring40_force = force40[0] - '0';
+        d.ring_force = read_switch(SW_DPP16_RING);
+        d.ring40_force = read_switch(SW_MFMA40_RING);
         d.sticky = getenv("MPC_DPP16_RING_DYNAMIC") == nullptr;
-        const char *res = getenv("MPC_DPP16_RESIDENT");          // "0" / "1": A/B switch of the resident-F build, read like MPC_DPP16_RING
-        d.resident = (res && (res[0] == '0' || res[0] == '1')) ? res[0] - '0' : -1;
+        d.resident = read_switch(SW_DPP16_RESIDENT);
         return d;
     }();
     return f;
 }
-static int dpp16_ring_force()
-{
-    const DeviceFacts &f = device_facts();
-    if (f.sticky) return f.ring_force;
-    // MPC_DPP16_RING_DYNAMIC=1 (the test suite): the switch follows the environment from launch to launch
-    const char *force = getenv("MPC_DPP16_RING");
-    return (force && (force[0] == '2' || force[0] == '4')) ? force[0] - '0' : 0;
-}
+// a switch as a launch sees it: what the process read at load, or -- MPC_DPP16_RING_DYNAMIC=1, the test suite -- the environment of
+// this very launch
+static int env_switch(const EnvSwitch &s, int at_load) { return device_facts().sticky ? at_load : read_switch(s); }
 
 // The mode-0 12/4 step on the two-slot ring with a share of F kept in LDS between sweep and rollout (lqr_dpp16_res.o): 39 KiB a wave,
 // so only while one wavefront per SIMD holds the batch -- beyond, 40 KiB would halve the occupancy the short ring is there for.
@@ -69,11 +78,7 @@ static std::atomic<int64_t> g_resident_launches{0};          // mpc_lqr_resident
 static bool dpp16_resident(const StepParams<float> &q)
 {
     const DeviceFacts &f = device_facts();
-    int on = f.resident;
-    if (!f.sticky) {                       // MPC_DPP16_RING_DYNAMIC=1 (the test suite): the switch follows the environment
-        const char *e = getenv("MPC_DPP16_RESIDENT");
-        on = (e && (e[0] == '0' || e[0] == '1')) ? e[0] - '0' : -1;
-    }
+    int on = env_switch(SW_DPP16_RESIDENT, f.resident);
     // Unforced, only where the launch is bound by its traffic: the kept blocks cost the wavefront's own chain ~3.5 us (the copy, the choice
     // of base and of DMA source at every timestep), which shows wherever the chain is the launch -- paired, MI355X: B = 2048 +3.6 us,
     // 3072 +3.5, 3584 +1.2, 3840 -0.5, 4096 -1.75 (docs/history/r20.md).  Beyond 15/16 of one wavefront per SIMD it pays.
@@ -90,11 +95,7 @@ static bool dpp16_resident(const StepParams<float> &q)
 static int mfma40_ring(const StepParams<float> &sp)
 {
     const DeviceFacts &f = device_facts();
-    int force = f.ring40_force;
-    if (!f.sticky) {                       // MPC_DPP16_RING_DYNAMIC=1 (the test suite): the switch follows the environment
-        const char *e = getenv("MPC_MFMA40_RING");
-        force = (e && (e[0] == '2' || e[0] == '3')) ? e[0] - '0' : 0;
-    }
+    const int force = env_switch(SW_MFMA40_RING, f.ring40_force);
     if (force) return force;
     // Box-constrained: the three-slot ring while one wave per SIMD holds the batch, six waves per CU on the two-slot ring beyond.
     // Unconstrained / masked (round 4, final kernels, config 5 by HIP events): the two-slot ring keeps 1,536 waves resident, so a
@@ -129,6 +130,18 @@ static int check_env(const mpc_env_dynamics *e, int ns, int nc)
     if (nc != 1 || ns != env_ns(kind) + carry) return fail(MPC_E_DIMS, "n_state / n_ctrl do not match the simulator");
     if (!(e->dt > 0) || !(e->u_max >= 0)) return fail(MPC_E_ARG, "simulator dt / u_max");
     return MPC_OK;
+}
+
+// the argument checks mpc_env_linearize and mpc_env_param_grad share: the simulator itself at N points
+static int check_env_points(const mpc_env_dynamics *env, int dtype, int64_t N)
+{
+    if (!env) return fail(MPC_E_NULL, "simulator is NULL");
+    if (dtype != MPC_F32 && dtype != MPC_F64) return fail(MPC_E_DTYPE, "bad dtype");
+    if (env->kind & MPC_ENV_CTRL_CARRY) return fail(MPC_E_UNSUPPORTED, "MPC_ENV_CTRL_CARRY: linearise the simulator itself (the carry block is constant)");
+    if (env->kind < MPC_ENV_PENDULUM || env->kind > MPC_ENV_CARTPOLE) return fail(MPC_E_ARG, "unknown simulator kind");
+    const int rc = check_env(env, env_ns(env->kind), 1);
+    if (rc) return rc;
+    return N < 0 ? fail(MPC_E_DIMS, "N < 0") : MPC_OK;
 }
 
 static int check_options(const mpc_lqr_problem *p, const mpc_lqr_options *o)
@@ -170,99 +183,33 @@ static StepParams<real> sizes_only(const StepParams<real> &sp)
     return s;
 }
 
-// Does `kernel` take this call, by its own rule (lqr_*.hip)?  query: the form mpc_lqr_impl_supported asks -- sizes, dtype and options;
-// the alignment of the actual tensors is checked at launch.  The two exact kernels (12/4, 32/8), whose rule looks at the tensors,
-// answer a query from the sizes alone, as their queries always have; the others never look at a problem tensor.
-template <typename real>
-static bool kernel_takes(int kernel, const StepParams<real> &sp, bool query = false)
-{
-    if (kernel == MPC_IMPL_GENERIC) return generic_lds_bytes(sp.ns, sp.nc, sizeof(real)) <= 160 * 1024;
-    if (kernel == MPC_IMPL_TINY) return tiny_supported(sp.ns, sp.nc);
-    if (kernel == MPC_IMPL_MFMA16) return mfma16_supported(sp);
-    if constexpr (sizeof(real) == 4) {
-        switch (kernel) {
-        case MPC_IMPL_DPP16: return dpp16_supported(query ? sizes_only(sp) : sp);
-        case MPC_IMPL_DPP16_PAD: return dpp16_pad_supported(sp);
-        case MPC_IMPL_MFMA40: return mfma40_supported(query ? sizes_only(sp) : sp);
-        case MPC_IMPL_MFMA40_PAD: return mfma40_pad_supported(sp);
-        case MPC_IMPL_MFMA40_NARROW: return mfma40_narrow_supported(sp);
-        case MPC_IMPL_WAVE1: return tiny_supported(sp.ns, sp.nc) && wave1_supported(sp);
-        case MPC_IMPL_WAVE1_CARRY: return tiny_supported(sp.ns, sp.nc) && wave1_carry_supported(sp);
-        }
-    }
-    return false;
-}
-
-// the kernels that can stop after their sweep (MPC_OPT_SWEEP_ONLY): the 12/4 and 32/8 fused ones, exact and padded; a call heading
-// for any other kernel takes the generic sweep
-static bool stops_after_sweep(int kernel)
-{
-    return kernel == MPC_IMPL_DPP16 || kernel == MPC_IMPL_DPP16_PAD || kernel == MPC_IMPL_MFMA40 || kernel == MPC_IMPL_MFMA40_PAD ||
-           kernel == MPC_IMPL_MFMA40_NARROW;
-}
-
 // What a kernel keeps in the workspace, in bytes from its start (-1: not there): the gains K | k where the caller passes none, its own
 // record Kk, all it asks for (`bytes`), and the k_t of its box QPs a later step may start from (qp: byte offset, element strides).
-struct WsLayout {
-    int64_t K, k, Kk, bytes, qp, qp_st, qp_sb;
-};
-template <typename real>
-static WsLayout ws_layout(int kernel, int T, int B, int ns, int nc)
+// One function per layout; e = sizeof(real), TB = T B.
+struct WsLayout { int64_t K, k, Kk, bytes, qp, qp_st, qp_sb; };
+// the generic kernels: K [T,B,nc,ns] | k [T,B,nc]
+static WsLayout layout_generic(int64_t TB, int B, int ns, int nc, int64_t e) { return {0, TB * nc * ns * e, -1, TB * nc * (ns + 1) * e, -1, 0, 0}; }
+// one lane per problem; gains parked as [T][ns+1][B], behind them one trajectory column [T][ns+1] per line-search trial lane (<= 8 per
+// problem): 9 (ns + 1) reals per problem-step <= 504 bytes
+static WsLayout layout_row(int64_t TB, int B, int ns, int nc, int64_t e) { return {0, TB * nc * ns * e, 0, TB * nc * (ns + 1) * e * 9, -1, 0, 0}; }
+// the fused kernels park their gains [T,B,64] in the workspace; float32: gain record + (m, M) record + the second line-search trial's
+// trajectory (box-constrained 12/4 kernel); the 12/4 kernel's gain record Kk[t][b][lane 0..15][4]: lane 12 holds k
+static WsLayout layout_fused12(int64_t TB, int B, int ns, int nc, int64_t e) { return {0, TB * nc * ns * e, 0, e == 4 ? TB * (128 + 16) * 4 : TB * 64 * 8, -1, 0, 0}; }
+static WsLayout layout_dpp16(int64_t TB, int B, int ns, int nc, int64_t e) { return {0, TB * nc * ns * e, 0, layout_fused12(TB, B, ns, nc, e).bytes, 48 * 4, (int64_t)B * 64, 64}; }
+// the constrained modes park (M, Quu, m) [T,B,328] + the second trial's trajectory [T,B,40] behind the gains, for the rollout that
+// prices without C
+static WsLayout layout_mfma40(int64_t TB, int B, int ns, int nc, int64_t e)
 {
-    const int64_t TB = (int64_t)T * B, e = sizeof(real), needK = TB * nc * ns * e, needk = TB * nc * e;
-    WsLayout w = {0, needK, -1, needK + needk, -1, 0, 0};            // the generic kernels: K [T,B,nc,ns] | k [T,B,nc]
-    switch (kernel) {
-    case MPC_IMPL_TINY:
-    case MPC_IMPL_WAVE1:
-    case MPC_IMPL_WAVE1_CARRY:
-        // one lane per problem; gains parked as [T][ns+1][B], behind them one trajectory column [T][ns+1] per line-search trial
-        // lane (<= 8 per problem): 9 (ns + 1) reals per problem-step <= 504 bytes
-        w.Kk = 0; w.bytes = (needK + needk) * 9;
-        break;
-    case MPC_IMPL_MFMA16:
-    case MPC_IMPL_DPP16:
-    case MPC_IMPL_DPP16_PAD:
-        // the fused kernels park their gains [T,B,64] in the workspace; float32: gain record + (m, M) record + the second line-search
-        // trial's trajectory (box-constrained 12/4 kernel)
-        w.Kk = 0; w.bytes = e == 4 ? TB * (128 + 16) * 4 : TB * 64 * 8;
-        // the 12/4 kernel's gain record Kk[t][b][lane 0..15][4]: lane 12 holds k
-        if (kernel == MPC_IMPL_DPP16) { w.qp = 48 * 4; w.qp_st = (int64_t)B * 64; w.qp_sb = 64; }
-        break;
-    case MPC_IMPL_MFMA40:
-        // the constrained modes park (M, Quu, m) [T,B,328] + the second trial's trajectory [T,B,40] behind the gains, for the rollout
-        // that prices without C
-        w.Kk = needK + needk; w.bytes = w.Kk + TB * (328 + 40) * 4;
-        w.qp = w.k; w.qp_st = (int64_t)B * nc; w.qp_sb = nc;
-        break;
-    case MPC_IMPL_MFMA40_NARROW:
-        // (the narrow instantiation lives inside the padded kernel's layout: its gains K [T,B,8,16] in the front half of the K region, k
-        // where the padded kernel keeps it -- the record a later step starts from is the same --, (M, Quu, m) [T,B,200] | [T,B,24] in Kk)
-    case MPC_IMPL_MFMA40_PAD:
-        // the kernel's own padded gains K [T,B,8,32] | k [T,B,8] (entries >= n_ctrl zero) | (M, Quu, m) [T,B,328] | second trial [T,B,40]
-        w.K = 0; w.k = TB * 256 * 4; w.Kk = w.k + TB * 8 * 4; w.bytes = w.Kk + TB * (328 + 40) * 4;
-        w.qp = w.k; w.qp_st = (int64_t)B * 8; w.qp_sb = 8;
-        break;
-    }
-    return w;
+    const WsLayout w = layout_generic(TB, B, ns, nc, e);
+    return {w.K, w.k, w.bytes, w.bytes + TB * (328 + 40) * 4, w.k, (int64_t)B * nc, nc};
 }
-
-// where a caller's missing status array lives inside the workspace: behind the largest layout among the kernels the shape can reach
-// -- and never in front of the float32 12/4-class record, whatever the shape and dtype (the size callers have always been handed)
-template <typename real>
-static int64_t largest_layout(const mpc_lqr_problem *p)
+// the kernel's own padded gains K [T,B,8,32] | k [T,B,8] (entries >= n_ctrl zero) | (M, Quu, m) [T,B,328] | second trial [T,B,40]
+// (the narrow instantiation lives inside this layout: its gains K [T,B,8,16] in the front half of the K region, k where the padded kernel
+// keeps it -- the record a later step starts from is the same --, (M, Quu, m) [T,B,200] | [T,B,24] in Kk)
+static WsLayout layout_pad40(int64_t TB, int B, int ns, int nc, int64_t e)
 {
-    const mpc_lqr_problem q = sizes_only(p->B, p->T, p->ns, p->nc, p->dtype);
-    const StepParams<real> s = make_params<real>(&q, nullptr, nullptr);
-    int64_t m = ws_layout<float>(MPC_IMPL_DPP16, p->T, p->B, p->ns, p->nc).bytes;
-    for (int kernel = MPC_IMPL_GENERIC; kernel <= MPC_IMPL_DPP16_PAD; ++kernel) {
-        const int64_t b = ws_layout<real>(kernel, p->T, p->B, p->ns, p->nc).bytes;
-        if ((kernel == MPC_IMPL_GENERIC || kernel_takes<real>(kernel, s, true)) && b > m) m = b;
-    }
-    return m;
-}
-static int64_t status_scratch_offset(const mpc_lqr_problem *p)
-{
-    return ((p->dtype == MPC_F64 ? largest_layout<double>(p) : largest_layout<float>(p)) + 15) & ~(int64_t)15;
+    const int64_t k = TB * 256 * 4, Kk = k + TB * 8 * 4;
+    return {0, k, Kk, Kk + TB * (328 + 40) * 4, k, (int64_t)B * 8, 8};
 }
 
 // A lane per problem leaves the chip empty at the batch sizes iLQR is run at (B = 1024: 16 .. 128 wavefronts
@@ -276,82 +223,229 @@ static bool row_kernel_pays(long lds_bytes, int B)          // lds_bytes: of one
     const long per_cu = (160L * 1024) / lds_bytes;
     return (B + 3) / 4 <= (device_facts().simds / 4) * (per_cu < 8 ? per_cu : 8);
 }
-static bool wave1_pays(const StepParams<float> &sp)
-{
-    return wave1_supported(sp) && row_kernel_pays(wave1_lds_bytes(sp), sp.B);
-}
+static bool wave1_pays(const StepParams<float> &sp) { return wave1_supported(sp) && row_kernel_pays(wave1_lds_bytes(sp), sp.B); }
 static bool wave1_pays(const StepParams<double> &) { return false; }
 // ... the same rule for the carry instantiation (impl 10, forced only: mpc_lqr_row_carry_pays tells a caller where to force it)
-static bool wave1_carry_pays(const StepParams<float> &sp)
-{
-    return wave1_carry_supported(sp) && row_kernel_pays(wave1_carry_lds_bytes(sp), sp.B);
-}
+static bool wave1_carry_pays(const StepParams<float> &sp) { return wave1_carry_supported(sp) && row_kernel_pays(wave1_carry_lds_bytes(sp), sp.B); }
 
 // ring depth of the 12/4 kernel (lqr_dpp16.hip): the unconstrained step always on the short ring; the constrained one there
 // only when the batch has more waves (4 problems each) than the chip has SIMDs (256 CUs x 4)
 static int dpp16_ring(const StepParams<float> &sp)
 {
     const bool constrained = sp.bound_mode != MPC_BOUND_NONE || sp.zero_mask != nullptr;
-    const int force = dpp16_ring_force();
+    const int force = env_switch(SW_DPP16_RING, device_facts().ring_force);
     return (force ? force == 2 : (!constrained || (sp.B + 3) / 4 > device_facts().simds)) ? 2 : 4;
+}
+static int launch_dpp16(const StepRoute &r, const StepParams<float> &q, hipStream_t st)
+{
+    // (the route's answer stays "impl 3, ring 2": the resident-F build is the same kernel with the same results, bit for bit)
+    if (r.ring == 2 && dpp16_resident(q)) {
+        g_resident_launches.fetch_add(1, std::memory_order_relaxed);
+        return launch_step_dpp16_res(q, st);
+    }
+    return r.ring == 2 ? launch_step_dpp16_ring2(q, st) : launch_step_dpp16(q, st);
+}
+
+// One row per kernel, step_kernels[MPC_IMPL_*]: all the router knows about it.  The families are the placement blocks of step_route.
+enum StepFamily { FAM_NONE, FAM_GENERIC, FAM_ROW /* a lane or a row per problem */, FAM_FUSED12 /* 12/4-class fused, gains optional */,
+                  FAM_MFMA40 /* 32/8 exact */, FAM_PAD40 /* 32/8 padded, narrow */ };
+enum {
+    K_SIMULATOR = 1,        // takes a simulator as true_dynamics
+    K_CARRIES = 2,          // ... and one behind MPC_ENV_CTRL_CARRY
+    K_CARRY_ONLY = 4,       // ... and nothing else (so: a whole step only)
+    K_SWEEP_STOP = 8,       // can stop after its sweep (MPC_OPT_SWEEP_ONLY); a call heading for any other kernel takes the generic sweep
+    K_PARKS_STATUS = 16,    // its layout counts where a caller's missing status words are parked (status_scratch_offset)
+    K_SIZES_QUERY = 32,     // its rule looks at the tensors: a query (mpc_lqr_impl_supported) is answered from the sizes alone, as ever
+    K_SIZES_RECORD = 64,    // ... and so is mpc_lqr_qp_record for a call that forces it
+};
+struct StepRefusal { int code; const char *text; };
+template <typename real>
+struct StepKernelIn {                                                 // a kernel in one dtype
+    bool (*rule)(const StepParams<real> &);                           // its own rule (lqr_*.hip); NULL: it does not exist in this dtype
+    int (*launch)(const StepRoute &, const StepParams<real> &, hipStream_t);      // picks the build variant from (route, params)
+    bool needs_workspace;                                             // takes the call only with room in an aligned workspace
+    int (*ring)(const StepParams<real> &);                            // its sweep ring, where it has more than one
+    StepRefusal refused;                                              // what a forced call it does not take is told (NULL: the call goes on)
+};
+struct StepKernel {
+    int code; const char *name; StepFamily family;
+    int auto_rank;                               // its place in the order impl 0 proposes kernels in; 0: never proposed by that order
+    unsigned flags;                              // K_*
+    WsLayout (*layout)(int64_t TB, int B, int ns, int nc, int64_t e);
+    StepKernelIn<float> f32;
+    StepKernelIn<double> f64;
+    // what a forced call is told at once: in a dtype the kernel does not exist in (NULL: see `refused`), off its shapes, and with (or,
+    // K_CARRY_ONLY, without) a simulator
+    const char *no_dtype, *no_shape, *no_simulator;
+};
+typedef StepParams<float> P32;
+// launchers and rules that need a word more than the kernel's own: a kernel with one build, the generic kernels, the one-control shapes
+template <typename real, int (*launch)(const StepParams<real> &, hipStream_t)>
+static int one_build(const StepRoute &, const StepParams<real> &q, hipStream_t st) { return launch(q, st); }
+template <typename real>
+static int launch_generic(const StepRoute &r, const StepParams<real> &q, hipStream_t st) { return launch_step_generic<real>(q, r.phase, st); }
+template <typename real>
+static bool generic_fits(const StepParams<real> &s) { return generic_lds_bytes(s.ns, s.nc, sizeof(real)) <= 160 * 1024; }
+template <typename real>
+static bool is_tiny(const StepParams<real> &s) { return tiny_supported(s.ns, s.nc); }
+static const char ws_small[] = "workspace too small (see mpc_lqr_workspace_bytes)";
+static const char ws_small_or_off[] = "workspace too small or not 16-byte aligned (see mpc_lqr_workspace_bytes)";
+static const char both_gains[] = "pass both K and k, or neither";
+static const char generic_only[] = "a simulator as true_dynamics runs on the generic kernels only";
+static const char lane_shapes[] = "lane-per-problem / wavefront-per-problem kernel needs n_ctrl = 1, n_state <= 6";
+static const char wave4_fp32[] = "the 4-problems-per-wave kernel is fp32 only";
+static const char row_rule[] = "the row-per-problem kernel is float32, max_linesearch_iter <= 16, four problems in 150 KiB of LDS";
+static constexpr StepKernel step_kernels[] = {
+    {MPC_IMPL_AUTO, "auto", FAM_NONE, 0, 0, layout_generic},         // (nobody: also an unknown code)
+    {MPC_IMPL_GENERIC, "generic", FAM_GENERIC, 0, K_SIMULATOR | K_PARKS_STATUS, layout_generic,
+     {generic_fits<float>, launch_generic<float>}, {generic_fits<double>, launch_generic<double>}},
+    // float64 (round 5, v_mfma_f64_16x16x4_f64) only with its workspace: a caller written against ABI 7 -- out->K / out->k given, no or
+    // a small workspace -- keeps the generic kernel under impl 0
+    {MPC_IMPL_MFMA16, "mfma16", FAM_FUSED12, 3, K_PARKS_STATUS, layout_fused12,
+     {mfma16_supported, one_build<float, launch_step_mfma16>, false, nullptr,
+      {MPC_E_DIMS, "fused MFMA kernel needs fp32, n_state <= 12, n_ctrl <= 4, max_linesearch_iter <= 16"}},
+     {mfma16_supported, one_build<double, launch_step_mfma16>, true, nullptr,
+      {MPC_E_DIMS, "fused MFMA kernel needs n_state <= 12, n_ctrl <= 4, max_linesearch_iter <= 16"}},
+     nullptr, nullptr, generic_only},
+    {MPC_IMPL_DPP16, "dpp16", FAM_FUSED12, 1, K_SWEEP_STOP | K_PARKS_STATUS | K_SIZES_QUERY, layout_dpp16,
+     {dpp16_supported, launch_dpp16, false, dpp16_ring, {MPC_E_DIMS, "DPP kernel needs fp32, n_state = 12, n_ctrl = 4 and 16-byte aligned blocks"}},
+     {nullptr, nullptr, false, nullptr, {MPC_E_DTYPE, wave4_fp32}}, nullptr, nullptr, generic_only},
+    {MPC_IMPL_TINY, "tiny", FAM_ROW, 0, K_SIMULATOR | K_CARRIES | K_PARKS_STATUS, layout_row,
+     {is_tiny<float>, one_build<float, launch_step_tiny<float>>}, {is_tiny<double>, one_build<double, launch_step_tiny<double>>},
+     nullptr, lane_shapes},
+    // n_state = 32, n_ctrl = 8: register-resident MFMA sweep and rollout (lqr_mfma40_body.h)
+    {MPC_IMPL_MFMA40, "mfma40", FAM_MFMA40, 4, K_SWEEP_STOP | K_PARKS_STATUS | K_SIZES_QUERY | K_SIZES_RECORD, layout_mfma40,
+     {mfma40_supported, [](const StepRoute &r, const P32 &q, hipStream_t st) { return r.ring == 2 ? launch_step_mfma40_ring2(q, st) : launch_step_mfma40(q, st); },
+      false, mfma40_ring, {MPC_E_DIMS, "MFMA kernel needs fp32, n_state = 32, n_ctrl = 8, 16-byte aligned blocks, no simulator"}},
+     {nullptr, nullptr, false, nullptr, {MPC_E_DTYPE, "the MFMA sweep is fp32 only"}}},
+    {MPC_IMPL_WAVE1, "wave1", FAM_ROW, 0, K_SIMULATOR | K_PARKS_STATUS, layout_row,
+     {[](const P32 &s) { return is_tiny(s) && wave1_supported(s); }, one_build<float, launch_step_wave1>, false, nullptr, {MPC_E_DIMS, row_rule}},
+     {nullptr, nullptr, false, nullptr, {MPC_E_DIMS, row_rule}}, nullptr, lane_shapes},
+    // with the workspace only: its padded gains and the constrained modes' records, 16-byte aligned
+    {MPC_IMPL_MFMA40_PAD, "mfma40_pad", FAM_PAD40, 5, K_SWEEP_STOP | K_PARKS_STATUS, layout_pad40,
+     {mfma40_pad_supported, [](const StepRoute &r, const P32 &q, hipStream_t st) { return r.pad16 ? launch_step_mfma40_pad16(q, st) : launch_step_mfma40_pad4(q, st); },
+      true, nullptr, {MPC_E_DIMS, "padded MFMA kernel needs fp32, n_state <= 32, n_ctrl <= 8, max_linesearch_iter <= 16, no simulator, and the "
+                                  "workspace of mpc_lqr_workspace_bytes (16-byte aligned)"}}},
+    {MPC_IMPL_DPP16_PAD, "dpp16_pad", FAM_FUSED12, 2, K_SWEEP_STOP | K_PARKS_STATUS, layout_fused12,
+     {dpp16_pad_supported, one_build<float, launch_step_dpp16_pad>, false, nullptr,
+      {MPC_E_DIMS, "padded DPP kernel needs fp32, n_state <= 12, n_ctrl <= 4, max_linesearch_iter <= 16"}},
+     {nullptr, nullptr, false, nullptr, {MPC_E_DTYPE, wave4_fp32}}, nullptr, nullptr, generic_only},
+    // (impl 9, the padded kernel's narrow instantiation, and impl 10, the row kernel's for a simulator behind the flag -- a plain
+    // simulator or a linear model has impl 6: forced only, and outside the parked-status offset callers have always been handed)
+    {MPC_IMPL_MFMA40_NARROW, "mfma40_narrow", FAM_PAD40, 0, K_SWEEP_STOP, layout_pad40,
+     {mfma40_narrow_supported, [](const StepRoute &r, const P32 &q, hipStream_t st) { return r.pad16 ? launch_step_mfma40_narrow16(q, st) : launch_step_mfma40_narrow4(q, st); },
+      true, nullptr, {MPC_E_DIMS, "narrow MFMA kernel needs fp32, n_state <= 16, n_ctrl <= 8, max_linesearch_iter <= 16, no simulator, and the "
+                                  "workspace of mpc_lqr_workspace_bytes (16-byte aligned)"}},
+     {}, "the narrow MFMA kernel is fp32 only"},
+    {MPC_IMPL_WAVE1_CARRY, "wave1_carry", FAM_ROW, 0, K_SIMULATOR | K_CARRIES | K_CARRY_ONLY, layout_row,
+     {[](const P32 &s) { return is_tiny(s) && wave1_carry_supported(s); }, one_build<float, launch_step_wave1_carry>, false, nullptr,
+      {MPC_E_DIMS, "the row-per-problem carry kernel is float32, max_linesearch_iter <= 16, four problems in 150 KiB of LDS"}},
+     {}, "the row-per-problem carry kernel is fp32 only", "the row-per-problem carry kernel needs a whole step with n_ctrl = 1, n_state = 4 or 6",
+     "the row-per-problem carry kernel needs a simulator behind MPC_ENV_CTRL_CARRY as true_dynamics"},
+};
+constexpr int N_STEP_KERNELS = sizeof(step_kernels) / sizeof(step_kernels[0]);
+constexpr bool step_kernels_in_place(int i = 0) { return i == N_STEP_KERNELS || (step_kernels[i].code == i && step_kernels_in_place(i + 1)); }
+static_assert(N_STEP_KERNELS == MPC_IMPL_WAVE1_CARRY + 1 && step_kernels_in_place(), "step_kernels[code] is the row of `code`");
+
+// The order impl 0 proposes kernels in, off the ranks: 12/4 on its own kernel; every other float32 shape up to 12/4, and 12/4 itself where
+// a block is not 16-byte aligned, on that kernel's PADDED instantiation (round 6; ahead of the one-problem-per-wavefront kernel that
+// served them in rounds 1-5 and still serves float64: what every test and gradient check of the reference runs in, tests/test_mpc.py
+// .double()); 32/8 on its own kernel; every float32 shape up to 32/8 that has no kernel of its own (13/4, 20/5, 24/8, 32/4, 8/6 ...) on
+// the 32/8 kernel's PADDED instantiation (lqr_mfma40_body.h, PADK) -- the reference's sweep is shape-agnostic (mpc/lqr_step.py:61-158),
+// and between the hand-tuned shapes the generic kernel ran at 4 % of the roofline (missing 1).
+struct StepOrder { int n, code[N_STEP_KERNELS]; };
+constexpr StepOrder step_order_of_ranks()
+{
+    StepOrder o = {};
+    for (int rank = 1; rank < N_STEP_KERNELS; ++rank)
+        for (const StepKernel &k : step_kernels)
+            if (k.auto_rank == rank) o.code[o.n++] = k.code;
+    return o;
+}
+static constexpr StepOrder step_auto_order = step_order_of_ranks();
+
+static bool known_kernel(int kernel) { return kernel > MPC_IMPL_AUTO && kernel < N_STEP_KERNELS; }
+template <typename real>
+static const StepKernelIn<real> &in_dtype(const StepKernel &k) { if constexpr (sizeof(real) == 4) return k.f32; else return k.f64; }
+// Does the kernel take this call, by its own rule?  query: sizes, dtype and options -- the alignment of the tensors is checked at launch.
+template <typename real>
+static bool kernel_takes(const StepKernel &k, const StepParams<real> &sp, bool query = false)
+{
+    const StepKernelIn<real> &d = in_dtype<real>(k);
+    return d.rule && d.rule(query && (k.flags & K_SIZES_QUERY) ? sizes_only(sp) : sp);
+}
+template <typename real>
+static WsLayout ws_layout(int kernel, int T, int B, int ns, int nc) { return step_kernels[kernel].layout((int64_t)T * B, B, ns, nc, sizeof(real)); }
+
+// where a caller's missing status array lives inside the workspace: behind the largest layout among the kernels the shape can reach
+// -- and never in front of the float32 12/4-class record, whatever the shape and dtype (the size callers have always been handed)
+template <typename real>
+static int64_t largest_layout(const mpc_lqr_problem *p)
+{
+    const mpc_lqr_problem q = sizes_only(p->B, p->T, p->ns, p->nc, p->dtype);
+    const StepParams<real> s = make_params<real>(&q, nullptr, nullptr);
+    int64_t m = ws_layout<float>(MPC_IMPL_DPP16, p->T, p->B, p->ns, p->nc).bytes;
+    for (const StepKernel &k : step_kernels) {
+        if (!(k.flags & K_PARKS_STATUS)) continue;
+        const int64_t b = ws_layout<real>(k.code, p->T, p->B, p->ns, p->nc).bytes;
+        if ((k.family == FAM_GENERIC || kernel_takes<real>(k, s, true)) && b > m) m = b;
+    }
+    return m;
+}
+static int64_t status_scratch_offset(const mpc_lqr_problem *p)
+{
+    return ((p->dtype == MPC_F64 ? largest_layout<double>(p) : largest_layout<float>(p)) + 15) & ~(int64_t)15;
 }
 
 // Which kernel takes this call, and where its pieces live in the workspace.  Launches nothing, sets no error state, allocates
-// nothing; never cached (the answer depends on the pointers and, with MPC_DPP16_RING_DYNAMIC, on the environment).
+// nothing; never cached (the answer depends on the pointers and, with MPC_DPP16_RING_DYNAMIC, on the environment).  The checks of the
+// call, then one block per family: what a call that forces a kernel of the family is refused with, and where a call heading for one
+// (forced or under impl 0) finds its pieces.  The order in which refusals fire is part of the interface.
 template <typename real>
 StepRoute step_route(const StepParams<real> &sp, const mpc_lqr_problem *p, int impl, int phase_mask, const void *workspace,
                      int64_t workspace_bytes)
 {
     constexpr bool f32 = sizeof(real) == 4;
-    StepRoute r;
-    r.code = 0; r.msg = nullptr; r.kernel = 0; r.phase = phase_mask; r.ring = 0; r.pad16 = false; r.needs_resolve = false;
-    r.K_off = r.k_off = r.Kk_off = r.status_off = r.qp_off = -1; r.qp_st = r.qp_sb = 0;
+    StepRoute r = {0, nullptr, 0, phase_mask, 0, false, false, -1, -1, -1, -1, -1, 0, 0};
     const auto refuse = [&r](int code, const char *msg) { r.code = code; r.msg = msg; return r; };
-    const bool step = phase_mask == 3, aligned = (uintptr_t)workspace % 16 == 0, tiny = tiny_supported(sp.ns, sp.nc);
+    const bool step = phase_mask == 3, aligned = (uintptr_t)workspace % 16 == 0, tiny = tiny_supported(sp.ns, sp.nc), forcing = impl != MPC_IMPL_AUTO;
     const auto room = [&](int64_t bytes) { return workspace && workspace_bytes >= bytes; };
     const auto layout = [&](int kernel) { return ws_layout<real>(kernel, sp.T, sp.B, sp.ns, sp.nc); };
-    // a kernel takes the call: by its own rule; with a simulator only the lane- / row-per-problem and the generic kernels; and with the
-    // workspace where the call falls through to the next kernel without it -- the padded 32/8 instantiation (its padded gains and the
-    // constrained modes' records, 16-byte aligned) and the float64 MFMA kernel (a caller written against ABI 7 -- out->K /
-    // out->k given, no or a small workspace -- keeps the generic kernel under impl 0)
-    const auto takes_now = [&](int kernel) {
-        if (!kernel_takes<real>(kernel, sp)) return false;
-        if (kernel == MPC_IMPL_GENERIC || kernel == MPC_IMPL_TINY || kernel == MPC_IMPL_WAVE1 || kernel == MPC_IMPL_WAVE1_CARRY) return true;
-        if (sp.env.kind) return false;
-        if (kernel == MPC_IMPL_MFMA40_PAD || kernel == MPC_IMPL_MFMA40_NARROW || (!f32 && kernel == MPC_IMPL_MFMA16))
-            return room(layout(kernel).bytes) && aligned;
-        return true;
+    // a kernel takes the call: by its own rule; with a simulator only where it runs one; and with the workspace where the call falls
+    // through to the next kernel without it
+    const auto takes_now = [&](const StepKernel &k) {
+        if (!kernel_takes<real>(k, sp)) return false;
+        if (sp.env.kind && !(k.flags & K_SIMULATOR)) return false;
+        return !in_dtype<real>(k).needs_workspace || (room(layout(k.code).bytes) && aligned);
     };
-    signed char asked[MPC_IMPL_WAVE1_CARRY + 1] = {-1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1};      // each kernel is asked once per call
+    signed char asked[N_STEP_KERNELS];           // each kernel is asked once per call
+    memset(asked, -1, sizeof(asked));
     const auto takes = [&](int kernel) {
-        if (kernel < MPC_IMPL_GENERIC || kernel > MPC_IMPL_WAVE1_CARRY) return false;
-        if (asked[kernel] < 0) asked[kernel] = takes_now(kernel);
+        if (!known_kernel(kernel)) return false;
+        if (asked[kernel] < 0) asked[kernel] = takes_now(step_kernels[kernel]);
         return asked[kernel] != 0;
     };
-    // a fused kernel took the call: under impl 0 the problems it flags MPC_ST_C_ASYMMETRIC are solved again (resolve_asymmetric)
-    const auto fused = [&](int kernel, const WsLayout &w) {
-        r.kernel = kernel;
-        r.Kk_off = w.Kk;
-        r.needs_resolve = impl == 0 && !sp.c_symmetric;
-        return r;
+    const auto family_takes = [&](StepFamily family) {
+        for (const StepKernel &k : step_kernels)
+            if (k.family == family && takes(k.code)) return true;
+        return false;
     };
+    // a fused kernel took the call: under impl 0 the problems it flags MPC_ST_C_ASYMMETRIC are solved again (resolve_asymmetric)
+    const auto fused = [&](int kernel, const WsLayout &w) { r.kernel = kernel; r.Kk_off = w.Kk; r.needs_resolve = !forcing && !sp.c_symmetric; return r; };
+    const auto record = [&r](const WsLayout &w) { r.qp_off = w.qp; r.qp_st = w.qp_st; r.qp_sb = w.qp_sb; };
 
-    // The kernel the call is heading for: the forced one, or under impl 0 the first of this order that takes it -- the one-control
-    // shapes up to six states on the lane- / row-per-problem kernels; 12/4 on its own kernel; every other float32 shape up to 12/4,
-    // and 12/4 itself where a block is not 16-byte aligned, on that kernel's PADDED instantiation (round 6; ahead of the
-    // one-problem-per-wavefront kernel that served them in rounds 1-5 and still serves float64: round 5, v_mfma_f64_16x16x4_f64, what
-    // every test and gradient check of the reference runs in, tests/test_mpc.py .double()); 32/8 on its own kernel; every float32
-    // shape up to 32/8 that has no kernel of its own (13/4, 20/5, 24/8, 32/4, 8/6 ...) on the 32/8 kernel's PADDED instantiation
-    // (lqr_mfma40_body.h, PADK) -- the reference's sweep is shape-agnostic (mpc/lqr_step.py:61-158), and between the hand-tuned
-    // shapes the generic kernel ran at 4 % of the roofline (missing 1); everything else on the generic kernels.
+    // The kernel the call is heading for: the forced one, or under impl 0 the one-control shapes up to six states on the lane- /
+    // row-per-problem kernels, whichever pays; the first of step_auto_order that takes any other; everything else on the generic kernels.
     int kernel = impl;
-    if (impl == 0) {
+    if (!forcing) {
         kernel = MPC_IMPL_GENERIC;
         if (step && tiny) kernel = wave1_pays(sp) ? MPC_IMPL_WAVE1 : MPC_IMPL_TINY;
         else if (step)
-            for (int next : {MPC_IMPL_DPP16, MPC_IMPL_DPP16_PAD, MPC_IMPL_MFMA16, MPC_IMPL_MFMA40, MPC_IMPL_MFMA40_PAD})
-                if (takes(next)) { kernel = next; break; }
+            for (int i = 0; i < step_auto_order.n; ++i)
+                if (takes(step_auto_order.code[i])) { kernel = step_auto_order.code[i]; break; }
     }
+    const StepKernel &heading = step_kernels[known_kernel(kernel) ? kernel : MPC_IMPL_AUTO];
+    const StepKernelIn<real> &mine = in_dtype<real>(heading);
 
     // the symmetry verdict travels in the status words: a caller that passes none gets them parked behind the workspace
     if (!sp.status && step && workspace) {
@@ -363,113 +457,88 @@ StepRoute step_route(const StepParams<real> &sp, const mpc_lqr_problem *p, int i
         if (!step) return refuse(MPC_E_ARG, "MPC_OPT_SWEEP_ONLY is an option of mpc_lqr_step");
         if (!sp.K || !sp.k) return refuse(MPC_E_NULL, "MPC_OPT_SWEEP_ONLY needs out->K and out->k");
         if (sp.env.kind) return refuse(MPC_E_ARG, "MPC_OPT_SWEEP_ONLY with a simulator as true_dynamics");
-        if (!(stops_after_sweep(kernel) && takes(kernel))) {
-            if (impl != 0 && impl != 1) return refuse(MPC_E_ARG, "MPC_OPT_SWEEP_ONLY: this kernel cannot stop after its sweep");
-            r.kernel = MPC_IMPL_GENERIC;
-            r.phase = 1;
+        if (!((heading.flags & K_SWEEP_STOP) && takes(kernel))) {
+            if (forcing && heading.family != FAM_GENERIC) return refuse(MPC_E_ARG, "MPC_OPT_SWEEP_ONLY: this kernel cannot stop after its sweep");
+            r.kernel = MPC_IMPL_GENERIC; r.phase = 1;
             return r;
         }
     }
     // MPC_ENV_CTRL_CARRY: the lane-per-problem kernel carries the control (lqr_tiny_body.h), and so does the row-per-problem kernel's
-    // carry instantiation (impl 10, forced only); the row-per-problem and the generic kernels call the simulator as it is and REFUSE the
+    // carry instantiation (forced only); the row-per-problem and the generic kernels call the simulator as it is and REFUSE the
     // flag -- never a silent un-augmented answer
-    if (sp.env.carry && (!step || (impl != 0 && impl != 4 && impl != 10)))
+    if (sp.env.carry && (!step || (forcing && !(heading.flags & K_CARRIES))))
         return refuse(MPC_E_UNSUPPORTED, "MPC_ENV_CTRL_CARRY: only mpc_lqr_step on the lane-per-problem kernel (impl 0 or 4) carries the control");
-    if (sp.env.kind && sp.env.linearize && !(step && tiny && (impl == 0 || impl == 4 || impl == 6 || impl == 10)))
+    if (sp.env.kind && sp.env.linearize && !(step && tiny && (!forcing || heading.family == FAM_ROW)))
         return refuse(MPC_E_ARG, "in-kernel linearisation needs the lane-per-problem kernel (n_ctrl = 1, n_state <= 6)");
-    // (impl 10 takes a simulator behind the flag and nothing else: a plain simulator or a linear model has impl 6)
-    if (impl == MPC_IMPL_WAVE1_CARRY) {
-        if (!f32) return refuse(MPC_E_DTYPE, "the row-per-problem carry kernel is fp32 only");
-        if (!step || !tiny) return refuse(MPC_E_DIMS, "the row-per-problem carry kernel needs a whole step with n_ctrl = 1, n_state = 4 or 6");
-        if (!sp.env.kind || !sp.env.carry)
-            return refuse(MPC_E_ARG, "the row-per-problem carry kernel needs a simulator behind MPC_ENV_CTRL_CARRY as true_dynamics");
-        if (!takes(impl))
-            return refuse(MPC_E_DIMS, "the row-per-problem carry kernel is float32, max_linesearch_iter <= 16, four problems in 150 KiB of LDS");
-    }
-    if (sp.env.kind && (impl == 2 || impl == 3 || impl == 8))
-        return refuse(MPC_E_ARG, "a simulator as true_dynamics runs on the generic kernels only");
-    if (impl == MPC_IMPL_MFMA40_NARROW && !f32) return refuse(MPC_E_DTYPE, "the narrow MFMA kernel is fp32 only");
-    if ((impl == 4 || impl == 6) && (!step || !tiny))
-        return refuse(MPC_E_DIMS, "lane-per-problem / wavefront-per-problem kernel needs n_ctrl = 1, n_state <= 6");
-    if (impl == 6 && !takes(MPC_IMPL_WAVE1))
-        return refuse(MPC_E_DIMS, "the row-per-problem kernel is float32, max_linesearch_iter <= 16, four problems in 150 KiB of LDS");
-    if (step && (kernel == MPC_IMPL_TINY || kernel == MPC_IMPL_WAVE1 || kernel == MPC_IMPL_WAVE1_CARRY)) {
-        // (these kernels keep Q and V as general matrices, like the reference: nothing to test, nothing to re-solve)
+    if (forcing && !mine.rule && heading.no_dtype) return refuse(MPC_E_DTYPE, heading.no_dtype);
+
+    // A lane or a row per problem.  (These kernels keep Q and V as general matrices, like the reference: nothing to test or re-solve.)
+    if (heading.family == FAM_ROW) {
+        if (forcing) {
+            if (!step || !tiny) return refuse(MPC_E_DIMS, heading.no_shape);
+            if ((heading.flags & K_CARRY_ONLY) && !(sp.env.kind && sp.env.carry)) return refuse(MPC_E_ARG, heading.no_simulator);
+            if (mine.refused.text && !takes(kernel)) return refuse(mine.refused.code, mine.refused.text);
+        }
         const WsLayout w = layout(kernel);
-        if (!room(w.bytes)) return refuse(MPC_E_ARG, "workspace too small (see mpc_lqr_workspace_bytes)");
-        r.kernel = kernel;
-        r.Kk_off = w.Kk;
+        if (!room(w.bytes)) return refuse(MPC_E_ARG, ws_small);
+        r.kernel = kernel; r.Kk_off = w.Kk;
         return r;
     }
-    if (step && impl != 1 && !sp.env.kind) {
-        const bool half_gains = (sp.K == nullptr) != (sp.k == nullptr);
-        const WsLayout w = layout(MPC_IMPL_MFMA16);                   // out->K / out->k are optional on these three kernels
+
+    // The 12/4 class: out->K / out->k are optional on its three kernels, which share the size of their workspace.  Whoever the call is
+    // heading for -- the forced generic kernel and a simulator apart --, float32 insists on the pair of gains and, where one of the three
+    // takes the call, on their workspace; float64 hands the call to the fused kernel wherever that takes it (a forced 5 or 7 as well).
+    if (heading.family == FAM_FUSED12 && sp.env.kind) return refuse(MPC_E_ARG, heading.no_simulator);
+    if (step && !(forcing && heading.family == FAM_GENERIC) && !sp.env.kind) {
+        const bool half_gains = (sp.K == nullptr) != (sp.k == nullptr), heading12 = heading.family == FAM_FUSED12, forced12 = forcing && heading12;
         if constexpr (f32) {
-            if (half_gains) return refuse(MPC_E_NULL, "pass both K and k, or neither");
-            const bool dpp = takes(MPC_IMPL_DPP16), mfma = takes(MPC_IMPL_MFMA16), dpad = takes(MPC_IMPL_DPP16_PAD);
-            if (impl == 3 && !dpp)
-                return refuse(MPC_E_DIMS, "DPP kernel needs fp32, n_state = 12, n_ctrl = 4 and 16-byte aligned blocks");
-            if (impl == 8 && !dpad)
-                return refuse(MPC_E_DIMS, "padded DPP kernel needs fp32, n_state <= 12, n_ctrl <= 4, max_linesearch_iter <= 16");
-            if (impl == 2 && !mfma)
-                return refuse(MPC_E_DIMS, "fused MFMA kernel needs fp32, n_state <= 12, n_ctrl <= 4, max_linesearch_iter <= 16");
-            if ((impl == 3 || impl == 2 || impl == 8 || dpp || mfma || dpad) && !(room(w.bytes) && aligned))
-                return refuse(MPC_E_ARG, "workspace too small or not 16-byte aligned (see mpc_lqr_workspace_bytes)");
-            if (kernel == MPC_IMPL_DPP16 || kernel == MPC_IMPL_DPP16_PAD || kernel == MPC_IMPL_MFMA16) {
-                const WsLayout wk = layout(kernel);
-                if (kernel == MPC_IMPL_DPP16) r.ring = dpp16_ring(sp);
-                r.qp_off = wk.qp; r.qp_st = wk.qp_st; r.qp_sb = wk.qp_sb;
-                return fused(kernel, wk);
+            if (half_gains) return refuse(MPC_E_NULL, both_gains);
+            if (forced12 && !takes(kernel)) return refuse(mine.refused.code, mine.refused.text);
+            if (heading12 || family_takes(FAM_FUSED12)) {
+                const WsLayout w = layout(heading12 ? kernel : MPC_IMPL_MFMA16);      // (`bytes` is the same for the three)
+                if (!(room(w.bytes) && aligned)) return refuse(MPC_E_ARG, ws_small_or_off);
+                if (heading12) {
+                    if (mine.ring) r.ring = mine.ring(sp);
+                    record(w);
+                    return fused(kernel, w);
+                }
             }
         } else {
-            if (impl == 3 || impl == 8) return refuse(MPC_E_DTYPE, "the 4-problems-per-wave kernel is fp32 only");
-            if (impl == 2 && !mfma16_supported(sp))
-                return refuse(MPC_E_DIMS, "fused MFMA kernel needs n_state <= 12, n_ctrl <= 4, max_linesearch_iter <= 16");
-            // (only a FORCED impl 2 insists on the fused kernel's workspace)
-            if (impl == 2 && !takes(impl))
-                return refuse(MPC_E_ARG, "workspace too small or not 16-byte aligned (see mpc_lqr_workspace_bytes)");
-            if (takes(MPC_IMPL_MFMA16)) {                             // (whatever impl asked for, as ever: a forced 5 or 7 lands here too)
-                if (half_gains) return refuse(MPC_E_NULL, "pass both K and k, or neither");
-                return fused(MPC_IMPL_MFMA16, w);
+            if (forced12 && !kernel_takes<real>(heading, sp)) return refuse(mine.refused.code, mine.refused.text);
+            if (forced12 && !takes(kernel)) return refuse(MPC_E_ARG, ws_small_or_off);     // (only a FORCED fused kernel insists on its workspace)
+            if (takes(MPC_IMPL_MFMA16)) {
+                if (half_gains) return refuse(MPC_E_NULL, both_gains);
+                return fused(MPC_IMPL_MFMA16, layout(MPC_IMPL_MFMA16));
             }
         }
     }
+
+    // The 32/8 kernel's padded and narrow instantiations, on their own padded gains (float64 has neither: a forced 7 goes on).
     if constexpr (f32) {
-        if (impl == 7 && !(step && takes(impl)))
-            return refuse(MPC_E_DIMS, "padded MFMA kernel needs fp32, n_state <= 32, n_ctrl <= 8, max_linesearch_iter <= 16, no simulator, and the "
-                                      "workspace of mpc_lqr_workspace_bytes (16-byte aligned)");
-        // (impl 9, the padded kernel's narrow instantiation: forced only -- the loop above never proposes it)
-        if (impl == MPC_IMPL_MFMA40_NARROW && !(step && takes(impl)))
-            return refuse(MPC_E_DIMS, "narrow MFMA kernel needs fp32, n_state <= 16, n_ctrl <= 8, max_linesearch_iter <= 16, no simulator, and the "
-                                      "workspace of mpc_lqr_workspace_bytes (16-byte aligned)");
-        if (step && (kernel == MPC_IMPL_MFMA40_PAD || kernel == MPC_IMPL_MFMA40_NARROW)) {
+        if (heading.family == FAM_PAD40) {
+            if (forcing && !(step && takes(kernel))) return refuse(mine.refused.code, mine.refused.text);
             const WsLayout w = layout(kernel);
-            r.K_off = w.K; r.k_off = w.k;
-            r.pad16 = mfma40_pad16_supported(sp);
-            r.qp_off = w.qp; r.qp_st = w.qp_st; r.qp_sb = w.qp_sb;
+            r.K_off = w.K; r.k_off = w.k; r.pad16 = mfma40_pad16_supported(sp);
+            record(w);
             return fused(kernel, w);
         }
     }
+
+    // Everybody else works on the gains K | k of the generic layout: the caller's, or parked in the workspace.
     if (!sp.K || !sp.k) {
         const WsLayout w = layout(MPC_IMPL_GENERIC);
         if (!step) return refuse(MPC_E_NULL, "K / k is NULL");
-        if (!room(w.bytes)) return refuse(MPC_E_ARG, "workspace too small (see mpc_lqr_workspace_bytes)");
+        if (!room(w.bytes)) return refuse(MPC_E_ARG, ws_small);
         r.K_off = w.K; r.k_off = w.k;
     }
-    if constexpr (f32) {
-        // n_state = 32, n_ctrl = 8: register-resident MFMA sweep and rollout (lqr_mfma40_body.h)
-        if (impl == 5 && !(step && takes(impl)))
-            return refuse(MPC_E_DIMS, "MFMA kernel needs fp32, n_state = 32, n_ctrl = 8, 16-byte aligned blocks, no simulator");
-        if (step && kernel == MPC_IMPL_MFMA40) {
-            WsLayout w = layout(kernel);
-            // (M, Quu, m) record of the constrained modes: behind K | k where the workspace has the room (rollout_priced)
-            if (!((sp.bound_mode != MPC_BOUND_NONE || sp.zero_mask) && room(w.bytes) && aligned)) w.Kk = -1;
-            r.ring = mfma40_ring(sp);
-            if (r.K_off >= 0) { r.qp_off = w.qp; r.qp_st = w.qp_st; r.qp_sb = w.qp_sb; }
-            return fused(kernel, w);
-        }
-    } else if (impl == 5) {
-        return refuse(MPC_E_DTYPE, "the MFMA sweep is fp32 only");
+    if (heading.family == FAM_MFMA40) {
+        if (forcing && !(step && takes(kernel))) return refuse(mine.refused.code, mine.refused.text);
+        WsLayout w = layout(kernel);
+        // (M, Quu, m) record of the constrained modes: behind K | k where the workspace has the room (rollout_priced)
+        if (!((sp.bound_mode != MPC_BOUND_NONE || sp.zero_mask) && room(w.bytes) && aligned)) w.Kk = -1;
+        r.ring = mine.ring(sp);
+        if (r.K_off >= 0) record(w);
+        return fused(kernel, w);
     }
     r.kernel = MPC_IMPL_GENERIC;
     return r;
@@ -499,37 +568,11 @@ static int resolve_asymmetric(StepParams<real> sp, void *workspace, hipStream_t 
 }
 
 // one launch per kernel
-static int launch_routed(const StepRoute &r, const StepParams<float> &q, hipStream_t st)
+template <typename real>
+static int launch_routed(const StepRoute &r, const StepParams<real> &q, hipStream_t st)
 {
-    switch (r.kernel) {
-    case MPC_IMPL_GENERIC: return launch_step_generic<float>(q, r.phase, st);
-    case MPC_IMPL_MFMA16: return launch_step_mfma16(q, st);
-    case MPC_IMPL_DPP16:
-        // (the route's answer stays "impl 3, ring 2": the resident-F build is the same kernel with the same results, bit for bit)
-        if (r.ring == 2 && dpp16_resident(q)) {
-            g_resident_launches.fetch_add(1, std::memory_order_relaxed);
-            return launch_step_dpp16_res(q, st);
-        }
-        if (r.ring == 2) return launch_step_dpp16_ring2(q, st);
-        return launch_step_dpp16(q, st);
-    case MPC_IMPL_TINY: return launch_step_tiny<float>(q, st);
-    case MPC_IMPL_MFMA40: return r.ring == 2 ? launch_step_mfma40_ring2(q, st) : launch_step_mfma40(q, st);
-    case MPC_IMPL_WAVE1: return launch_step_wave1(q, st);
-    case MPC_IMPL_WAVE1_CARRY: return launch_step_wave1_carry(q, st);
-    case MPC_IMPL_MFMA40_PAD: return r.pad16 ? launch_step_mfma40_pad16(q, st) : launch_step_mfma40_pad4(q, st);
-    case MPC_IMPL_DPP16_PAD: return launch_step_dpp16_pad(q, st);
-    case MPC_IMPL_MFMA40_NARROW: return r.pad16 ? launch_step_mfma40_narrow16(q, st) : launch_step_mfma40_narrow4(q, st);
-    }
-    return MPC_E_ARG;
-}
-static int launch_routed(const StepRoute &r, const StepParams<double> &q, hipStream_t st)
-{
-    switch (r.kernel) {
-    case MPC_IMPL_GENERIC: return launch_step_generic<double>(q, r.phase, st);
-    case MPC_IMPL_MFMA16: return launch_step_mfma16(q, st);
-    case MPC_IMPL_TINY: return launch_step_tiny<double>(q, st);
-    }
-    return MPC_E_ARG;
+    const auto launch = known_kernel(r.kernel) ? in_dtype<real>(step_kernels[r.kernel]).launch : nullptr;
+    return launch ? launch(r, q, st) : MPC_E_ARG;
 }
 
 // mpc_lqr_options.qp_start is a hint: an array the staging DMAs cannot fetch (16-byte granules) is ignored, not an error
@@ -556,7 +599,7 @@ static int step_impl(const mpc_lqr_problem *p, const mpc_lqr_options *o, const m
     real *const K_caller = sp.K, *const k_caller = sp.k;
     sp.Kk = (real *)at(r.Kk_off);
     if (r.K_off >= 0) {                          // gains where the route put them
-        if (r.kernel == MPC_IMPL_MFMA40_PAD || r.kernel == MPC_IMPL_MFMA40_NARROW) { sp.K_user = sp.K; sp.k_user = sp.k; }
+        if (step_kernels[r.kernel].family == FAM_PAD40) { sp.K_user = sp.K; sp.k_user = sp.k; }
         sp.K = (real *)at(r.K_off);
         sp.k = (real *)at(r.k_off);
     }
@@ -567,14 +610,27 @@ static int step_impl(const mpc_lqr_problem *p, const mpc_lqr_options *o, const m
 }
 
 // the argument checks of mpc_lqr_step, and of mpc_lqr_step_route, which answers for the same arguments
-static int check_step(const mpc_lqr_problem *p, const mpc_lqr_options *o, const mpc_lqr_outputs *out)
+// (whole_step false: of mpc_lqr_sweep and mpc_lqr_rollout, which have no in-kernel linearisation and so always need F)
+static int check_step(const mpc_lqr_problem *p, const mpc_lqr_options *o, const mpc_lqr_outputs *out, bool whole_step = true)
 {
-    const bool inline_lin = o && o->true_dynamics && o->true_dynamics->linearize;
+    const bool inline_lin = whole_step && o && o->true_dynamics && o->true_dynamics->linearize;
     int rc = check_problem(p, true, true, !inline_lin);
     if (rc) return rc;
     if ((rc = check_options(p, o))) return rc;
     if (!out) return fail(MPC_E_NULL, "outputs is NULL");
     return MPC_OK;
+}
+
+// mpc_lqr_sweep (phase 1) and mpc_lqr_rollout (phase 2): the generic kernels, the gains the caller's
+static int sweep_or_rollout(const mpc_lqr_problem *p, const mpc_lqr_options *o, const mpc_lqr_outputs *out, int phase, const void *old_costs_in,
+                            void *stream)
+{
+    const int rc = check_step(p, o, out, false);
+    if (rc) return rc;
+    if (p->B == 0) return MPC_OK;
+    hipStream_t st = (hipStream_t)stream;
+    return p->dtype == MPC_F32 ? step_impl<float>(p, o, out, nullptr, 0, MPC_IMPL_GENERIC, phase, old_costs_in, st)
+                               : step_impl<double>(p, o, out, nullptr, 0, MPC_IMPL_GENERIC, phase, old_costs_in, st);
 }
 
 template <typename real>
@@ -837,13 +893,14 @@ int mpc_lqr_step_route(const mpc_lqr_problem *p, const mpc_lqr_options *o, const
 int mpc_lqr_impl_supported(const mpc_lqr_problem *p, const mpc_lqr_options *o, int impl)
 {
     if (!p || check_problem(p, false, false) != MPC_OK || check_options(p, o) != MPC_OK) return 0;
-    if (impl < MPC_IMPL_GENERIC || impl > MPC_IMPL_WAVE1_CARRY) return 0;
-    // (MPC_ENV_CTRL_CARRY: the lane-per-problem kernel and the row-per-problem kernel's carry instantiation, see step_route)
-    if (o && o->true_dynamics && (o->true_dynamics->kind & MPC_ENV_CTRL_CARRY) && impl != MPC_IMPL_TINY && impl != MPC_IMPL_WAVE1_CARRY) return 0;
-    if (impl == MPC_IMPL_WAVE1_CARRY && o && (o->flags & MPC_OPT_SWEEP_ONLY)) return 0;      // (a whole step only)
+    if (!known_kernel(impl)) return 0;
+    const StepKernel &k = step_kernels[impl];
+    // (MPC_ENV_CTRL_CARRY: the kernels that carry the control, see step_route)
+    if (o && o->true_dynamics && (o->true_dynamics->kind & MPC_ENV_CTRL_CARRY) && !(k.flags & K_CARRIES)) return 0;
+    if ((k.flags & K_CARRY_ONLY) && o && (o->flags & MPC_OPT_SWEEP_ONLY)) return 0;          // (a whole step only)
     // sizes, dtype and options only: the alignment of the actual tensors is checked at launch
-    return p->dtype == MPC_F32 ? kernel_takes<float>(impl, make_params<float>(p, o, nullptr), true)
-                               : kernel_takes<double>(impl, make_params<double>(p, o, nullptr), true);
+    return p->dtype == MPC_F32 ? kernel_takes<float>(k, make_params<float>(p, o, nullptr), true)
+                               : kernel_takes<double>(k, make_params<double>(p, o, nullptr), true);
 }
 
 int mpc_lqr_row_carry_pays(const mpc_lqr_problem *p, const mpc_lqr_options *o)
@@ -867,7 +924,8 @@ int mpc_lqr_qp_record(const mpc_lqr_problem *p, const mpc_lqr_options *o, int im
     memset(&out, 0, sizeof(out));
     out.new_x = out.new_u = (void *)16;          // (a step has them; the route looks at pointers for NULL and alignment only)
     // (a forced impl 5 has always been answered from the sizes alone: off the 16-byte grid the step itself is refused at launch)
-    const mpc_lqr_problem q = impl == MPC_IMPL_MFMA40 ? sizes_only(p->B, p->T, p->ns, p->nc, p->dtype) : *p;
+    const bool by_sizes = known_kernel(impl) && (step_kernels[impl].flags & K_SIZES_RECORD);
+    const mpc_lqr_problem q = by_sizes ? sizes_only(p->B, p->T, p->ns, p->nc, p->dtype) : *p;
     const StepParams<float> sp = make_params<float>(&q, o, &out);
     const StepRoute r = step_route(sp, p, impl, 3, (const void *)16, mpc_lqr_workspace_bytes(p));
     if (r.code || r.qp_off < 0) return 0;        // 0 = not filled (only where the kernel that keeps the record really takes the call)
@@ -877,27 +935,13 @@ int mpc_lqr_qp_record(const mpc_lqr_problem *p, const mpc_lqr_options *o, int im
 
 int mpc_lqr_sweep(const mpc_lqr_problem *p, const mpc_lqr_options *o, const mpc_lqr_outputs *out, void *stream)
 {
-    int rc = check_problem(p, true, true);
-    if (rc) return rc;
-    if ((rc = check_options(p, o))) return rc;
-    if (!out) return fail(MPC_E_NULL, "outputs is NULL");
-    if (p->B == 0) return MPC_OK;
-    hipStream_t st = (hipStream_t)stream;
-    return p->dtype == MPC_F32 ? step_impl<float>(p, o, out, nullptr, 0, 1, 1, nullptr, st)
-                               : step_impl<double>(p, o, out, nullptr, 0, 1, 1, nullptr, st);
+    return sweep_or_rollout(p, o, out, 1, nullptr, stream);
 }
 
 int mpc_lqr_rollout(const mpc_lqr_problem *p, const mpc_lqr_options *o, const mpc_lqr_outputs *out,
                     const void *old_costs_in, void *stream)
 {
-    int rc = check_problem(p, true, true);
-    if (rc) return rc;
-    if ((rc = check_options(p, o))) return rc;
-    if (!out) return fail(MPC_E_NULL, "outputs is NULL");
-    if (p->B == 0) return MPC_OK;
-    hipStream_t st = (hipStream_t)stream;
-    return p->dtype == MPC_F32 ? step_impl<float>(p, o, out, nullptr, 0, 1, 2, old_costs_in, st)
-                               : step_impl<double>(p, o, out, nullptr, 0, 1, 2, old_costs_in, st);
+    return sweep_or_rollout(p, o, out, 2, old_costs_in, stream);
 }
 
 int mpc_lqr_kkt_grads(const mpc_lqr_problem *p, const void *dx_, const void *du_, const void *dl_dx_,
@@ -1001,35 +1045,21 @@ int mpc_lqr_kkt_fused(const mpc_lqr_problem *p, const mpc_lqr_options *o, const 
                       void *dC, void *dc, void *dF, void *df, void *dx_init, void *dx_out, void *du_out, int32_t *status,
                       void *workspace, int64_t workspace_bytes, void *stream)
 {
-    const int rc = check_kkt_fused(p, o);
-    if (rc) return rc;
-    const StepParams<float> sp = kkt_fused_params(p, o, status);
-    const KktRoute r = kkt_fused_route(sp, p, KktPointers{dl_dx, dl_du, dC, dc, dF, df, dx_init, dx_out, du_out, workspace}, workspace_bytes);
-    if (r.code) return fail(r.code, r.msg);
-    if (!r.kernel) return MPC_OK;                // (an empty batch)
-    // the nested solve is a plain LQRStep(...) in the reference (:328-338): linesearch_decay 0.2, max_linesearch_iter 10
-    return kkt_order[r.kernel - 1].launch(sp, (const float *)dl_dx, (const float *)dl_du, (float *)dC, (float *)dc, (float *)dF, (float *)df,
-                                          (float *)dx_init, (float *)dx_out, (float *)du_out, (float *)workspace, 0.2f, 10, (hipStream_t)stream);
+    return mpc_lqr_kkt_fused_kernel(p, o, MPC_KKT_NONE, dl_dx, dl_du, dC, dc, dF, df, dx_init, dx_out, du_out, status, workspace, workspace_bytes, stream);
 }
 
 int mpc_lqr_kkt_fused_route(const mpc_lqr_problem *p, const mpc_lqr_options *o, const void *dl_dx, const void *dl_du,
                             const void *dC, const void *dc, const void *dF, const void *df, const void *dx_init, const void *dx_out,
                             const void *du_out, const int32_t *status, const void *workspace, int64_t workspace_bytes)
 {
-    const int rc = check_kkt_fused(p, o);
-    if (rc) return rc;
-    const KktRoute r = kkt_fused_route(kkt_fused_params(p, o, (int32_t *)status), p,
-                                       KktPointers{dl_dx, dl_du, dC, dc, dF, df, dx_init, dx_out, du_out, workspace}, workspace_bytes);
-    if (r.code && !r.no_kernel) return fail(r.code, r.msg);
-    return r.kernel;                             // (MPC_KKT_NONE: a legal call that no fused kernel takes, or an empty batch)
+    return mpc_lqr_kkt_fused_kernel_route(p, o, MPC_KKT_NONE, dl_dx, dl_du, dC, dc, dF, df, dx_init, dx_out, du_out, status, workspace, workspace_bytes);
 }
 
 int mpc_lqr_kkt_fused_kernel(const mpc_lqr_problem *p, const mpc_lqr_options *o, int kernel, const void *dl_dx, const void *dl_du,
                              void *dC, void *dc, void *dF, void *df, void *dx_init, void *dx_out, void *du_out, int32_t *status,
                              void *workspace, int64_t workspace_bytes, void *stream)
 {
-    if (kernel == MPC_KKT_NONE)
-        return mpc_lqr_kkt_fused(p, o, dl_dx, dl_du, dC, dc, dF, df, dx_init, dx_out, du_out, status, workspace, workspace_bytes, stream);
+    // (MPC_KKT_NONE: nobody asked -- kkt_fused_route_kernel is kkt_fused_route then, and this is mpc_lqr_kkt_fused)
     const int rc = check_kkt_fused(p, o);
     if (rc) return rc;
     const StepParams<float> sp = kkt_fused_params(p, o, status);
@@ -1037,6 +1067,7 @@ int mpc_lqr_kkt_fused_kernel(const mpc_lqr_problem *p, const mpc_lqr_options *o,
                                               workspace_bytes, kernel);
     if (r.code) return fail(r.code, r.msg);
     if (!r.kernel) return MPC_OK;                // (an empty batch)
+    // the nested solve is a plain LQRStep(...) in the reference (:328-338): linesearch_decay 0.2, max_linesearch_iter 10
     return kkt_order[r.kernel - 1].launch(sp, (const float *)dl_dx, (const float *)dl_du, (float *)dC, (float *)dc, (float *)dF, (float *)df,
                                           (float *)dx_init, (float *)dx_out, (float *)du_out, (float *)workspace, 0.2f, 10, (hipStream_t)stream);
 }
@@ -1045,8 +1076,6 @@ int mpc_lqr_kkt_fused_kernel_route(const mpc_lqr_problem *p, const mpc_lqr_optio
                                    const void *dC, const void *dc, const void *dF, const void *df, const void *dx_init, const void *dx_out,
                                    const void *du_out, const int32_t *status, const void *workspace, int64_t workspace_bytes)
 {
-    if (kernel == MPC_KKT_NONE)
-        return mpc_lqr_kkt_fused_route(p, o, dl_dx, dl_du, dC, dc, dF, df, dx_init, dx_out, du_out, status, workspace, workspace_bytes);
     const int rc = check_kkt_fused(p, o);
     if (rc) return rc;
     const KktRoute r = kkt_fused_route_kernel(kkt_fused_params(p, o, (int32_t *)status), p,
@@ -1065,15 +1094,12 @@ int mpc_env_traj_cost(const mpc_lqr_problem *p, const mpc_env_dynamics *env, voi
     if (p->B == 0) return MPC_OK;
     if (!p->x_init || !p->cur_u) return fail(MPC_E_NULL, "x_init / u is NULL");
     if (cost && (!p->C || !p->c)) return fail(MPC_E_NULL, "cost requested but C / c is NULL");
-    hipStream_t st = (hipStream_t)stream;
-    if (p->dtype == MPC_F32) {
-        StepParams<float> sp = make_params<float>(p, nullptr, nullptr);
+    return by_dtype(p->dtype, [&](auto t) {
+        typedef decltype(t) real;
+        StepParams<real> sp = make_params<real>(p, nullptr, nullptr);
         set_env(sp.env, env);
-        return launch_traj_cost<float>(sp, (float *)x, (float *)cost, st);
-    }
-    StepParams<double> sp = make_params<double>(p, nullptr, nullptr);
-    set_env(sp.env, env);
-    return launch_traj_cost<double>(sp, (double *)x, (double *)cost, st);
+        return launch_traj_cost<real>(sp, (real *)x, (real *)cost, (hipStream_t)stream);
+    });
 }
 
 int mpc_slew_augment(const mpc_lqr_problem *p, double gamma, void *aC, void *ac, void *aF, void *af, void *stream)
@@ -1096,24 +1122,15 @@ int mpc_slew_augment(const mpc_lqr_problem *p, double gamma, void *aC, void *ac,
 int mpc_env_linearize(const mpc_env_dynamics *env, int dtype, int64_t N, const void *x, const void *u, void *F,
                       void *f, void *stream)
 {
-    if (!env) return fail(MPC_E_NULL, "simulator is NULL");
-    if (dtype != MPC_F32 && dtype != MPC_F64) return fail(MPC_E_DTYPE, "bad dtype");
-    if (env->kind & MPC_ENV_CTRL_CARRY) return fail(MPC_E_UNSUPPORTED, "MPC_ENV_CTRL_CARRY: linearise the simulator itself (the carry block is constant)");
-    if (env->kind < MPC_ENV_PENDULUM || env->kind > MPC_ENV_CARTPOLE) return fail(MPC_E_ARG, "unknown simulator kind");
-    int rc = check_env(env, env_ns(env->kind), 1);
-    if (rc) return rc;
-    if (N < 0) return fail(MPC_E_DIMS, "N < 0");
-    if (N == 0) return MPC_OK;
+    const int rc = check_env_points(env, dtype, N);
+    if (rc || N == 0) return rc;
     if (!x || !u || !F || !f) return fail(MPC_E_NULL, "env_linearize: NULL argument");
-    hipStream_t st = (hipStream_t)stream;
-    if (dtype == MPC_F32) {
-        EnvDesc<float> e;
+    return by_dtype(dtype, [&](auto t) {
+        typedef decltype(t) real;
+        EnvDesc<real> e;
         set_env(e, env);
-        return launch_env_linearize<float>(e, (long)N, (const float *)x, (const float *)u, (float *)F, (float *)f, st);
-    }
-    EnvDesc<double> e;
-    set_env(e, env);
-    return launch_env_linearize<double>(e, (long)N, (const double *)x, (const double *)u, (double *)F, (double *)f, st);
+        return launch_env_linearize<real>(e, (long)N, (const real *)x, (const real *)u, (real *)F, (real *)f, (hipStream_t)stream);
+    });
 }
 
 int64_t mpc_env_param_grad_workspace_bytes(int64_t N) { return env_param_grad_workspace_bytes(N < 0 ? 0 : N); }
@@ -1121,29 +1138,19 @@ int64_t mpc_env_param_grad_workspace_bytes(int64_t N) { return env_param_grad_wo
 int mpc_env_param_grad(const mpc_env_dynamics *env, int dtype, int64_t N, const void *x, const void *u, const void *gF,
                        const void *gf, void *gparams, void *workspace, int64_t workspace_bytes, void *stream)
 {
-    if (!env) return fail(MPC_E_NULL, "simulator is NULL");
-    if (dtype != MPC_F32 && dtype != MPC_F64) return fail(MPC_E_DTYPE, "bad dtype");
-    if (env->kind & MPC_ENV_CTRL_CARRY) return fail(MPC_E_UNSUPPORTED, "MPC_ENV_CTRL_CARRY: linearise the simulator itself (the carry block is constant)");
-    if (env->kind < MPC_ENV_PENDULUM || env->kind > MPC_ENV_CARTPOLE) return fail(MPC_E_ARG, "unknown simulator kind");
-    int rc = check_env(env, env_ns(env->kind), 1);
-    if (rc) return rc;
-    if (N < 0) return fail(MPC_E_DIMS, "N < 0");
-    if (N == 0) return MPC_OK;
+    const int rc = check_env_points(env, dtype, N);
+    if (rc || N == 0) return rc;
     if (!x || !u || !gF || !gf || !gparams || !workspace) return fail(MPC_E_NULL, "env_param_grad: NULL argument");
     if (workspace_bytes < env_param_grad_workspace_bytes(N))
         return fail(MPC_E_DIMS, "workspace too small (see mpc_env_param_grad_workspace_bytes)");
     if ((uintptr_t)workspace % 8) return fail(MPC_E_ARG, "env_param_grad: the workspace must be 8-byte aligned");
-    hipStream_t st = (hipStream_t)stream;
-    if (dtype == MPC_F32) {
-        EnvDesc<float> e;
+    return by_dtype(dtype, [&](auto t) {
+        typedef decltype(t) real;
+        EnvDesc<real> e;
         set_env(e, env);
-        return launch_env_param_grad<float>(e, (long)N, (const float *)x, (const float *)u, (const float *)gF, (const float *)gf,
-                                            (float *)gparams, (double *)workspace, st);
-    }
-    EnvDesc<double> e;
-    set_env(e, env);
-    return launch_env_param_grad<double>(e, (long)N, (const double *)x, (const double *)u, (const double *)gF, (const double *)gf,
-                                         (double *)gparams, (double *)workspace, st);
+        return launch_env_param_grad<real>(e, (long)N, (const real *)x, (const real *)u, (const real *)gF, (const real *)gf, (real *)gparams,
+                                           (double *)workspace, (hipStream_t)stream);
+    });
 }
 
 int64_t mpc_mlp_workspace_bytes(const mpc_mlp_dynamics *net) { return nn_workspace_bytes(net); }
@@ -1161,7 +1168,7 @@ int mpc_mlp_rollout(const mpc_lqr_problem *p, const mpc_lqr_options *o, const mp
     if (!p->x_init || !p->cur_u) return fail(MPC_E_NULL, "x_init / current_u is NULL");
     if ((p->C == nullptr) != (p->c == nullptr)) return fail(MPC_E_NULL, "pass both C and c, or neither");
     if (!out->new_x) return fail(MPC_E_NULL, "new_x is NULL");
-    if ((K == nullptr) != (k == nullptr)) return fail(MPC_E_NULL, "pass both K and k, or neither");
+    if ((K == nullptr) != (k == nullptr)) return fail(MPC_E_NULL, both_gains);
     if (K) {
         if (!p->cur_x || !p->C || !old_costs || !out->new_u)
             return fail(MPC_E_NULL, "line search needs current_x, C, c, old_costs and new_u");
@@ -1223,16 +1230,12 @@ int mpc_lqr_kkt_prepare(int dtype, int B, int T, int ns, int nc, const void *dl_
     const int mode = o ? o->bound_mode : MPC_BOUND_NONE;
     if (mask && (mode == MPC_BOUND_NONE || !u_star)) return fail(MPC_E_ARG, "kkt_prepare: mask needs bounds and u*");
     if (mask && mode == MPC_BOUND_TENSOR && (!o->lo || !o->hi)) return fail(MPC_E_NULL, "tensor bounds are NULL");
-    hipStream_t st = (hipStream_t)stream;
-    if (dtype == MPC_F32)
-        return launch_kkt_prepare<float>(B, T, ns, nc, (const float *)dl_dx, (const float *)dl_du,
-                                         (const float *)u_star, mode, o ? (float)o->lo_s : 0.f,
-                                         o ? (float)o->hi_s : 0.f, o ? (const float *)o->lo : nullptr,
-                                         o ? (const float *)o->hi : nullptr, (float *)negr, mask, st);
-    return launch_kkt_prepare<double>(B, T, ns, nc, (const double *)dl_dx, (const double *)dl_du,
-                                      (const double *)u_star, mode, o ? o->lo_s : 0., o ? o->hi_s : 0.,
-                                      o ? (const double *)o->lo : nullptr, o ? (const double *)o->hi : nullptr,
-                                      (double *)negr, mask, st);
+    return by_dtype(dtype, [&](auto t) {
+        typedef decltype(t) real;
+        return launch_kkt_prepare<real>(B, T, ns, nc, (const real *)dl_dx, (const real *)dl_du, (const real *)u_star, mode, o ? (real)o->lo_s : 0,
+                                        o ? (real)o->hi_s : 0, o ? (const real *)o->lo : nullptr, o ? (const real *)o->hi : nullptr, (real *)negr,
+                                        mask, (hipStream_t)stream);
+    });
 }
 
 int mpc_pnqp_lu(int dtype, int B, int n, const void *H, const void *q, const void *lo, const void *hi,
@@ -1244,14 +1247,11 @@ int mpc_pnqp_lu(int dtype, int B, int n, const void *H, const void *q, const voi
     if (B == 0) return MPC_OK;
     if (!H || !q || !lo || !hi || !x) return fail(MPC_E_NULL, "pnqp: NULL argument");
     if (n_iter < 1) n_iter = 20;
-    hipStream_t st = (hipStream_t)stream;
-    if (dtype == MPC_F32)
-        return launch_pnqp<float>(B, n, (const float *)H, (const float *)q, (const float *)lo, (const float *)hi,
-                                  (const float *)x0, n_iter, (float *)x, If_out, iters, status, (float *)Hfree,
-                                  (float *)LU, pivots, st);
-    return launch_pnqp<double>(B, n, (const double *)H, (const double *)q, (const double *)lo, (const double *)hi,
-                               (const double *)x0, n_iter, (double *)x, If_out, iters, status, (double *)Hfree,
-                               (double *)LU, pivots, st);
+    return by_dtype(dtype, [&](auto t) {
+        typedef decltype(t) real;
+        return launch_pnqp<real>(B, n, (const real *)H, (const real *)q, (const real *)lo, (const real *)hi, (const real *)x0, n_iter, (real *)x,
+                                 If_out, iters, status, (real *)Hfree, (real *)LU, pivots, (hipStream_t)stream);
+    });
 }
 
 int mpc_pnqp(int dtype, int B, int n, const void *H, const void *q, const void *lo, const void *hi,
@@ -1289,16 +1289,12 @@ int mpc_select_best(int dtype, int B, int T, int ns, int nc, int first, double b
     if (!x || !u || !costs || !du_norm || !best_x || !best_u || !best_costs || !best_du_norm || !flags)
         return fail(MPC_E_NULL, "select_best: NULL argument");
     if ((uintptr_t)flags & 7 || (uintptr_t)host_flags & 7) return fail(MPC_E_ARG, "select_best: the flags blocks must be 8-byte aligned");
-    hipStream_t st = (hipStream_t)stream;
-    if (dtype == MPC_F32)
-        return launch_select_best<float>(B, T, ns, nc, first, (float)best_cost_eps, (const float *)x,
-                                         (const float *)u, (const float *)costs, (const float *)du_norm,
-                                         (float *)best_x, (float *)best_u, (float *)best_costs,
-                                         (float *)best_du_norm, flags, host_flags, host_tag, status, st);
-    return launch_select_best<double>(B, T, ns, nc, first, best_cost_eps, (const double *)x, (const double *)u,
-                                      (const double *)costs, (const double *)du_norm, (double *)best_x,
-                                      (double *)best_u, (double *)best_costs, (double *)best_du_norm,
-                                      flags, host_flags, host_tag, status, st);
+    return by_dtype(dtype, [&](auto t) {
+        typedef decltype(t) real;
+        return launch_select_best<real>(B, T, ns, nc, first, (real)best_cost_eps, (const real *)x, (const real *)u, (const real *)costs,
+                                        (const real *)du_norm, (real *)best_x, (real *)best_u, (real *)best_costs, (real *)best_du_norm, flags,
+                                        host_flags, host_tag, status, (hipStream_t)stream);
+    });
 }
 
 int mpc_du_norm_reference(int dtype, int T, int B, int nc, const void *u, const void *new_u, void *out, void *stream)

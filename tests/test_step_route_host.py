@@ -22,9 +22,17 @@ import pytest
 from conftest import GOLDEN
 from mpc import _native
 
-_spec = importlib.util.spec_from_file_location("make_golden_step_route", os.path.join(GOLDEN, "make_golden_step_route.py"))
-gen = importlib.util.module_from_spec(_spec)
-_spec.loader.exec_module(gen)
+
+
+def _generator(name):
+    spec = importlib.util.spec_from_file_location(name, os.path.join(GOLDEN, name + ".py"))
+    module = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(module)
+    return module
+
+
+gen = _generator("make_golden_step_route")
+full = _generator("make_golden_step_route_full")
 
 
 def expected_routes():
@@ -136,12 +144,7 @@ def test_an_empty_batch_launches_nothing(lib):
 def probe(tmp_path_factory):
     """tests/step_route_probe.cpp, built host-only against the library under test (the compiler of csrc/Makefile)."""
     import subprocess
-    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-    lib_dir = os.path.dirname(_native.lib_path())
-    exe = str(tmp_path_factory.mktemp("probe") / "step_route_probe")
-    subprocess.check_call([os.environ.get("HIPCC", "/opt/rocm/bin/hipcc"), "-std=c++17", "-O1", "-x", "hip", "--cuda-host-only",
-                           os.path.join(root, "tests", "step_route_probe.cpp"), "-o", exe, "-L" + lib_dir, "-lmpc_lqr_hip",
-                           "-Wl,-rpath," + lib_dir])
+    exe = full.build_probe(_native.lib_path(), str(tmp_path_factory.mktemp("probe") / "step_route_probe"))
 
     def run(*calls):
         env = dict(os.environ)
@@ -149,6 +152,7 @@ def probe(tmp_path_factory):
         env.pop("MPC_MFMA40_RING", None)
         out = subprocess.check_output([exe] + [str(v) for call in calls for v in call], env=env).decode()
         return [json.loads(line) for line in out.splitlines()]
+    run.exe = exe
     return run
 
 
@@ -159,7 +163,7 @@ def test_the_route_puts_every_piece_where_the_ladder_put_it(probe):
     padded gains; generic: K | k; the parked status words behind the largest of them, rounded to 16."""
     NONE, SCALAR = 0, 1
     FULL, NO_WS, GAINS_ONLY = 1, 0, 3
-    #        ns  nc f64 T  B  bounds  mask ls sweep gains ws     align impl status
+    #        ns  nc f64 T  B  bounds  mask ls sweep gains ws     align impl status  (+ no simulator, the whole step)
     calls = {
         "12/4 box": (12, 4, 0, 5, 3, SCALAR, 0, 10, 0, 0, FULL, 16, 0, 0),
         "12/4 box off the grid": (12, 4, 0, 5, 3, SCALAR, 0, 10, 0, 0, FULL, 4, 0, 1),
@@ -197,11 +201,37 @@ def test_the_route_puts_every_piece_where_the_ladder_put_it(probe):
         "5/3 float64": dict(kernel=2, Kk_off=0, status_off=TB * (128 + 16) * 4),
         "12/4 forced generic, gains given": dict(kernel=1, needs_resolve=0),
     }
-    got = probe(*calls.values())
+    got = probe(*(call + (0, 0, 0, 3) for call in calls.values()))
     assert len(got) == len(calls)
     for name, g in zip(calls, got):
+        assert g.pop("msg") is None and g.pop("entry") == [want[name]["kernel"], want[name].get("ring", 0), ""]
         assert g.pop("workspace_bytes") == _native.load().mpc_lqr_workspace_bytes(ctypes.byref(gen.problem(_native, *calls[name][:2], calls[name][2], 5, 3)))
         assert g == dict(base, **want[name]), (name, g)
+
+
+def test_the_whole_route_is_the_one_before_the_kernels_became_a_table(probe, tmp_path):
+    """tests/golden/step_route_full.json: one digest per (shape, dtype, impl) over the probe's lines of the grid of
+    make_golden_step_route_full.py -- simulators, gains, workspaces, bounds, masks, alignments, the batch rules, the two phases --,
+    recorded from a build of the commit before docs/history/r22.md.  A cell that differs is run again and shown; with
+    MPC_LQR_HIP_PARENT_LIB pointing at a build of that commit, next to that build's lines from the first call that differs."""
+    with open(os.path.join(GOLDEN, "step_route_full.json")) as fh:
+        want = json.load(fh)["cells"]
+    got = full.digests(probe.exe)
+    assert list(got) == list(want)
+    bad = [cell for cell in got if got[cell] != want[cell]]
+    if bad:
+        cs = full.calls(*(int(v) for v in bad[0].split("/")))
+        mine = full.lines(probe.exe, full.as_text(cs))
+        shown = ["%d cells differ: %s" % (len(bad), " ".join(bad)), "cell %s:" % bad[0]]
+        parent = os.environ.get("MPC_LQR_HIP_PARENT_LIB")
+        if parent:
+            theirs = full.lines(full.build_probe(parent, str(tmp_path / "parent_probe")), full.as_text(cs))
+            i = next((i for i in range(len(cs)) if mine[i] != theirs[i]), None)
+            shown += ["no line differs from that build's: the table was not recorded from it"] if i is None else \
+                     ["call %d %r" % (i, cs[i]), "  here:   " + mine[i].decode(), "  parent: " + theirs[i].decode()]
+        else:
+            shown += ["%r -> %s" % (c, line.decode()) for c, line in zip(cs, mine)]
+        pytest.fail("\n".join(shown))
 
 
 def test_the_record_query_answers_for_the_kernel_that_takes_the_call(lib):
