@@ -86,7 +86,8 @@ size_t generic_lds_bytes(int ns, int nc, size_t elem);
 // the slew-rate augmentation (aC, ac, aF, af) of p's (C, c, F, f) in one launch (slew_augment.hip)
 template <typename real> int launch_slew_augment(const mpc_lqr_problem *p, double gamma, real *aC, real *ac, real *aF, real *af, hipStream_t st);
 
-// 4-problems-per-wave DPP path for n_state = 12, n_ctrl = 4, f32 (lqr_dpp16.hip)
+// 4-problems-per-wave DPP path for n_state = 12, n_ctrl = 4, f32 (lqr_dpp16.hip: the launchers, one per compilation of that file --
+// Makefile; lqr_rules.hip: every *_supported and *_workspace_bytes of this family and of the 32/8 one below, compiled once)
 bool dpp16_supported(const StepParams<float> &p);
 int launch_step_dpp16(const StepParams<float> &p, hipStream_t st);
 int launch_step_dpp16_ring2(const StepParams<float> &p, hipStream_t st);    // the same kernels on a 2-slot sweep ring (two waves per SIMD)

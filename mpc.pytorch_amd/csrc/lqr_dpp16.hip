@@ -356,12 +356,10 @@ static_assert(MPC_DPP16_LDS <= 40960, "resident F: a wavefront's quarter of the 
 #else
 #define MPC_DPP16_LDS (MPC_DPP16_NSTAGE * 9216)
 #endif
-// the KKT kernel shares this file's staging array: it lives in the compilation whose array fits its ring
+// the KKT kernel shares this file's staging array: it lives in the compilation whose array fits its ring (-DMPC_DPP16_WITH_KKT; the
+// other builds' -DMPC_DPP16_NO_KKT says the same by its absence and is read by nothing)
 #ifndef MPC_KKT16_NSTAGE
 #define MPC_KKT16_NSTAGE 4
-#endif
-#if !defined(MPC_DPP16_WITH_KKT) && !defined(MPC_DPP16_NO_KKT) && MPC_DPP16_NSTAGE == 4
-#define MPC_DPP16_WITH_KKT 1
 #endif
 __shared__ __attribute__((aligned(16))) char g_stage16[MPC_DPP16_LDS];
 typedef __attribute__((address_space(3))) void lds_void_t;
@@ -512,6 +510,35 @@ MPC_DEV void fence_own_stores()
 
 #include "lqr_dpp16_body.h"
 
+// ---- Which build is this? -------------------------------------------------------------------------------------------------------------
+// The five flag sets of the Makefile (FLAGS_lqr_dpp16*) and the launchers each object exports; any other combination is an error.
+//   MPC_DPP16_LAUNCH   the step launcher: modes 0..3, or with -DMPC_DPP16_RESIDENT mode 0 alone
+//   MPC_KF_LAUNCH      the fused KKT backward's: its four kernels exist where the staging array has the deep ring's 36 KiB
+//   (launch_kkt_dpp16, the three-call backward's kernel, goes with -DMPC_DPP16_WITH_KKT: the build whose array fits ITS ring)
+// capi.hip picks among the step builds: the memory-bound unconstrained step is faster on the short ring at every batch (fewer bytes in
+// flight per CU: 83.3 against 86.0 us at B = 4096, 65 against 74 at 1024); the instruction-bound constrained step wants the deep ring
+// while there is one wave per SIMD (B <= 4096: 184.8 against 191.0 us) and a second wave per SIMD beyond it (B = 6144: 248 against
+// 347 us; 8192: 304 against 371) -- profiles/r02_experiments.md 15.  What else the step launcher has to know about its build is Build, next to it.
+#define MPC_DPP16_ON(ring, kkt16) (MPC_DPP16_NSTAGE == ring && MPC_KKT16_NSTAGE == kkt16)
+#if MPC_DPP16_ON(4, 4) && !defined(MPC_DPP16_WITH_KKT) && !defined(MPC_DPP16_PAD) && !defined(MPC_DPP16_PAD_KKT) && !defined(MPC_DPP16_RESIDENT)
+#define MPC_DPP16_LAUNCH launch_step_dpp16               // lqr_dpp16.o: the 4-slot sweep ring (36 KiB of LDS per wave, four waves per CU)
+#define MPC_KF_LAUNCH launch_kkt_fused_dpp16
+#elif MPC_DPP16_ON(2, 2) && defined(MPC_DPP16_WITH_KKT) && !defined(MPC_DPP16_PAD) && !defined(MPC_DPP16_PAD_KKT) && !defined(MPC_DPP16_RESIDENT)
+#define MPC_DPP16_LAUNCH launch_step_dpp16_ring2         // lqr_dpp16_ring2.o: two slots (18 KiB, eight waves per CU = two per SIMD)
+#elif MPC_DPP16_ON(2, 4) && !defined(MPC_DPP16_WITH_KKT) && defined(MPC_DPP16_PAD) && !defined(MPC_DPP16_PAD_KKT) && !defined(MPC_DPP16_RESIDENT)
+// lqr_dpp16_pad.o: the PADDED instantiation on two slots, any n_state <= 12, n_ctrl <= 4 (lqr_dpp16_body.h, PADK): dword gathers with
+// the zero padding done by the DMA, no alignment asked of anybody
+#define MPC_DPP16_LAUNCH launch_step_dpp16_pad
+#elif MPC_DPP16_ON(2, 4) && !defined(MPC_DPP16_WITH_KKT) && defined(MPC_DPP16_PAD) && defined(MPC_DPP16_PAD_KKT) && !defined(MPC_DPP16_RESIDENT)
+#define MPC_KF_LAUNCH launch_kkt_fused_dpp16_pad         // lqr_dpp16_padkkt.o: the padded fused backward alone (-DMPC_KF_LDS_BYTES: its 36 KiB)
+#elif MPC_DPP16_ON(2, 4) && !defined(MPC_DPP16_WITH_KKT) && !defined(MPC_DPP16_PAD) && !defined(MPC_DPP16_PAD_KKT) && defined(MPC_DPP16_RESIDENT)
+// lqr_dpp16_res.o: mode 0 on two slots with a share of F kept in LDS between sweep and rollout (lqr_dpp16_body.h, RESK), 39 KiB a wave --
+// for batches of at most one wavefront per SIMD (capi.hip)
+#define MPC_DPP16_LAUNCH launch_step_dpp16_res
+#else
+#error "lqr_dpp16.hip: a combination of MPC_DPP16_NSTAGE / _WITH_KKT / _PAD / _PAD_KKT / _RESIDENT that the Makefile does not build"
+#endif
+
 namespace mpclqr {
 namespace {
 
@@ -522,8 +549,10 @@ __global__ void __launch_bounds__(64, 1) lqr_step_dpp16_kernel(StepParams<float>
 {
     dpp16::step_wave<MODE>(p);
 }
+}  // namespace
 
-#if MPC_DPP16_NSTAGE == 4 || defined(MPC_DPP16_PAD_KKT)
+#ifdef MPC_KF_LAUNCH
+namespace {
 // the whole of LQRStepFn.backward in one launch (lqr_dpp16_body.h: kkt_fused_wave); MASKED = controls on a bound are pinned
 static_assert((int)dpp16::KfP2<false>::SLOTS * (int)dpp16::KfP2<false>::STAGE + (int)dpp16::KfP2<false>::GST <= MPC_DPP16_LDS &&
               (int)dpp16::KfP2<false>::SLOTS >= 5, "the fused KKT kernel's second ring does not fit");
@@ -541,80 +570,8 @@ __global__ void __launch_bounds__(64, 1) lqr_kkt_fused_long_dpp16_kernel(StepPar
 {
     dpp16::kkt_fused_wave<MASKED, true>(p, k);
 }
-
-#endif
-
-#ifdef MPC_DPP16_WITH_KKT
-static_assert(MPC_KKT16_NSTAGE * 8192 <= MPC_DPP16_LDS, "the KKT kernel's ring does not fit this compilation's staging array");
-__global__ void __launch_bounds__(64, 1) lqr_kkt_dpp16_kernel(StepParams<float> p, dpp16::KktArgs k)
-{
-    dpp16::kkt_wave(p, k);
-}
-
-#endif
 }  // namespace
 
-#ifdef MPC_DPP16_WITH_KKT
-bool kkt_dpp16_supported(const StepParams<float> &p, const float *dx, const float *du, const float *dl_dx,
-                         const float *dC, const float *dF)
-{
-    auto al = [](const void *q, long st, long sb) { return ((uintptr_t)q % 16 == 0) && (st % 4 == 0) && (sb % 4 == 0); };
-    if (!(p.ns == 12 && p.nc == 4 && p.T >= 1)) return false;
-    if (!al(p.C, p.C_st, p.C_sb) || !al(p.c, p.c_st, p.c_sb)) return false;
-    if (p.T > 1 && !al(p.F, p.F_st, p.F_sb)) return false;
-    return al(p.cur_x, 0, 0) && al(p.cur_u, 0, 0) && al(dx, 0, 0) && al(du, 0, 0) && al(dl_dx, 0, 0) && al(dC, 0, 0) &&
-           (p.T == 1 || al(dF, 0, 0));
-}
-
-int launch_kkt_dpp16(const StepParams<float> &p, const float *dx, const float *du, const float *dl_dx, float *dC,
-                     float *dc, float *dF, float *df, float *dx_init, hipStream_t st)
-{
-    dpp16::KktArgs k;
-    k.dx = dx; k.du = du; k.dl_dx = dl_dx; k.dC = dC; k.dc = dc; k.dF = dF; k.df = df; k.dx_init = dx_init;
-    hipLaunchKernelGGL(lqr_kkt_dpp16_kernel, dim3((p.B + 3) / 4), dim3(64), 0, st, p, k);
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) {
-        set_last_error((std::string("lqr_kkt_dpp16_kernel: ") + hipGetErrorString(e)).c_str());
-        return MPC_E_LAUNCH;
-    }
-    return MPC_OK;
-}
-
-#endif
-
-#ifdef MPC_DPP16_PAD_KKT
-// the PADDED instantiation of the fused KKT backward (round 6): any n_state <= 12, n_ctrl <= 4, no alignment asked of the caller's blocks
-// (dword gathers and dword stores); the workspace -- the library's own layout, padded to 12/4 -- on 16 bytes
-bool kkt_fused_dpp16_pad_supported(const StepParams<float> &p, const float *ws)
-{
-    return p.ns >= 1 && p.ns <= 12 && p.nc >= 1 && p.nc <= 4 && p.T >= 1 && (uintptr_t)ws % 16 == 0;
-}
-#define MPC_KF_LAUNCH launch_kkt_fused_dpp16_pad
-#elif MPC_DPP16_NSTAGE == 4
-#define MPC_KF_LAUNCH launch_kkt_fused_dpp16
-// (built in the compilation with the deep staging array: four sweep stages, six rollout stages, see kkt_fused_wave)
-bool kkt_fused_dpp16_supported(const StepParams<float> &p, const float *dl_dx, const float *dl_du, const float *dC,
-                               const float *dF, const float *ws)
-{
-    auto al = [](const void *q, long st, long sb) { return ((uintptr_t)q % 16 == 0) && (st % 4 == 0) && (sb % 4 == 0); };
-    if (!(p.ns == 12 && p.nc == 4 && p.T >= 1)) return false;          // (any horizon since round 4: T > 64 on the LONG instantiation)
-    if (!al(p.C, p.C_st, p.C_sb) || !al(p.c, p.c_st, p.c_sb)) return false;
-    if (p.T > 1 && !al(p.F, p.F_st, p.F_sb)) return false;
-    if (p.bound_mode == MPC_BOUND_TENSOR && (!al(p.lo, 0, 0) || !al(p.hi, 0, 0))) return false;
-    // (p.zero_mask / p.has_delta: the forward's u_zero_I and delta_u, which the backward does not use -- mpc/lqr_step.py:322-340;
-    // launch_kkt_fused_dpp16 clears them)
-    return al(p.cur_x, 0, 0) && al(p.cur_u, 0, 0) && al(dl_dx, 0, 0) && al(dl_du, 0, 0) && al(dC, 0, 0) && al(ws, 0, 0) &&
-           (p.T == 1 || al(dF, 0, 0));
-}
-
-// floats per problem-step: (V | v) 96, (lambda | g) 24, and beyond 64 timesteps the gain record 64
-int64_t kkt_fused_dpp16_workspace_bytes(int T, int B)
-{
-    return (int64_t)T * B * (dpp16::KF_VBLK + 24 + (T > dpp16::RG_STEPS ? 64 : 0)) * 4 + 64;
-}
-#endif
-
-#if MPC_DPP16_NSTAGE == 4 || defined(MPC_DPP16_PAD_KKT)
 int MPC_KF_LAUNCH(const StepParams<float> &p_in, const float *dl_dx, const float *dl_du, float *dC, float *dc, float *dF,
                   float *df, float *dx_init, float *dx_out, float *du_out, float *ws, float decay, int max_ls,
                   hipStream_t st)
@@ -639,61 +596,45 @@ int MPC_KF_LAUNCH(const StepParams<float> &p_in, const float *dl_dx, const float
     }
     return MPC_OK;
 }
-
 #endif
 
-#if MPC_DPP16_NSTAGE == 4
-bool dpp16_supported(const StepParams<float> &p)
+#ifdef MPC_DPP16_WITH_KKT
+namespace {
+static_assert(MPC_KKT16_NSTAGE * 8192 <= MPC_DPP16_LDS, "the KKT kernel's ring does not fit this compilation's staging array");
+__global__ void __launch_bounds__(64, 1) lqr_kkt_dpp16_kernel(StepParams<float> p, dpp16::KktArgs k)
 {
-    // 16-byte DMA granules: every block the kernel streams must start on a 16-byte boundary
-    auto al = [](const void *q, long st, long sb) { return ((uintptr_t)q % 16 == 0) && (st % 4 == 0) && (sb % 4 == 0); };
-    if (!(p.ns == 12 && p.nc == 4 && p.T >= 1 && p.max_ls >= 1 && p.max_ls <= 16)) return false;
-    if (!al(p.C, p.C_st, p.C_sb) || !al(p.c, p.c_st, p.c_sb)) return false;
-    if (p.T > 1 && !al(p.F, p.F_st, p.F_sb)) return false;
-    if (p.f && !al(p.f, p.f_st, p.f_sb)) return false;
-    if (!al(p.cur_x, 0, 0) || !al(p.cur_u, 0, 0)) return false;
-    if (p.bound_mode == MPC_BOUND_TENSOR && (!al(p.lo, 0, 0) || !al(p.hi, 0, 0))) return false;
-    if (p.zero_mask && (uintptr_t)p.zero_mask % 4 != 0) return false;
-    return true;
+    dpp16::kkt_wave(p, k);
 }
+}  // namespace
 
-#endif
-
-// This file is compiled twice (Makefile): with the 4-slot sweep ring (36 KiB of LDS per wave, four waves per CU) as
-// launch_step_dpp16, and with -DMPC_DPP16_NSTAGE=2 (18 KiB, eight waves per CU = two per SIMD) as launch_step_dpp16_ring2.
-// capi.hip picks: the memory-bound unconstrained step is faster on the short ring at every batch (fewer bytes in
-// flight per CU: 83.3 against 86.0 us at B = 4096, 65 against 74 at 1024); the instruction-bound constrained step wants the
-// deep ring while there is one wave per SIMD (B <= 4096: 184.8 against 191.0 us) and a second wave per SIMD beyond it
-// (B = 6144: 248 against 347 us; 8192: 304 against 371) -- profiles/r02_experiments.md 15.
-// ... and a third time with -DMPC_DPP16_PAD (on the 2-slot ring) as launch_step_dpp16_pad: the PADDED instantiation for any n_state <=
-// 12, n_ctrl <= 4 (lqr_dpp16_body.h, PADK): dword gathers with the zero padding done by the DMA, no alignment asked of anybody.
-#ifndef MPC_DPP16_PAD_KKT
-#ifdef MPC_DPP16_PAD
-#define MPC_DPP16_LAUNCH launch_step_dpp16_pad
-bool dpp16_pad_supported(const StepParams<float> &p)
+int launch_kkt_dpp16(const StepParams<float> &p, const float *dx, const float *du, const float *dl_dx, float *dC,
+                     float *dc, float *dF, float *df, float *dx_init, hipStream_t st)
 {
-    // (dword gathers: float arrays are 4-byte aligned by construction; u_zero_I is read byte-wise.  12/4 itself is welcome too: blocks or
-    // strides that are not 16-byte aligned, which the exact kernel refuses)
-    return p.ns >= 1 && p.ns <= 12 && p.nc >= 1 && p.nc <= 4 && p.T >= 1 && p.max_ls >= 1 && p.max_ls <= 16 && !p.env.kind;
+    dpp16::KktArgs k;
+    k.dx = dx; k.du = du; k.dl_dx = dl_dx; k.dC = dC; k.dc = dc; k.dF = dF; k.df = df; k.dx_init = dx_init;
+    hipLaunchKernelGGL(lqr_kkt_dpp16_kernel, dim3((p.B + 3) / 4), dim3(64), 0, st, p, k);
+    hipError_t e = hipGetLastError();
+    if (e != hipSuccess) {
+        set_last_error((std::string("lqr_kkt_dpp16_kernel: ") + hipGetErrorString(e)).c_str());
+        return MPC_E_LAUNCH;
+    }
+    return MPC_OK;
 }
-#define MPC_DPP16_TAKES(p) dpp16_pad_supported(p)
-#elif MPC_DPP16_NSTAGE == 4
-#define MPC_DPP16_LAUNCH launch_step_dpp16
-#elif defined(MPC_DPP16_RESIDENT)
-// ... and a fifth time with -DMPC_DPP16_RESIDENT (on the 2-slot ring) as launch_step_dpp16_res: mode 0 with a share of F kept in LDS
-// between sweep and rollout (lqr_dpp16_body.h, RESK), 39 KiB a wave -- for batches of at most one wavefront per SIMD (capi.hip)
-#define MPC_DPP16_LAUNCH launch_step_dpp16_res
-bool dpp16_supported(const StepParams<float> &p);
-#else
-#define MPC_DPP16_LAUNCH launch_step_dpp16_ring2
-bool dpp16_supported(const StepParams<float> &p);
 #endif
+
+#ifdef MPC_DPP16_LAUNCH
+namespace {
+struct Build {
+    // the step launcher's rule (lqr_rules.hip) and the text of its refusal
+    static bool takes(const StepParams<float> &p) { return dpp16::PADK ? dpp16_pad_supported(p) : dpp16_supported(p); }
+    static constexpr const char *REFUSED = dpp16::PADK ? "dpp16 (padded): needs fp32, n_state <= 12, n_ctrl <= 4, max_linesearch_iter <= 16"
+                                                       : "dpp16: needs n_state = 12, n_ctrl = 4, fp32, 16-byte aligned blocks";
+};
+}  // namespace
+
 int MPC_DPP16_LAUNCH(const StepParams<float> &p, hipStream_t st)
 {
-#ifndef MPC_DPP16_TAKES
-#define MPC_DPP16_TAKES(p) dpp16_supported(p)
-#endif
-    if (!MPC_DPP16_TAKES(p)) { set_last_error(dpp16::PADK ? "dpp16 (padded): needs fp32, n_state <= 12, n_ctrl <= 4, max_linesearch_iter <= 16" : "dpp16: needs n_state = 12, n_ctrl = 4, fp32, 16-byte aligned blocks"); return MPC_E_DIMS; }
+    if (!Build::takes(p)) { set_last_error(Build::REFUSED); return MPC_E_DIMS; }
     if (!p.Kk || (uintptr_t)p.Kk % 16 != 0) { set_last_error("dpp16: gain workspace missing or misaligned"); return MPC_E_NULL; }
     if (!p.sweep_only && (!p.new_x || !p.new_u)) { set_last_error("dpp16: new_x / new_u is NULL"); return MPC_E_NULL; }
     static_assert(MPC_DPP16_LDS == dpp16::LDS_RES_TOTAL, "LDS layout out of sync");

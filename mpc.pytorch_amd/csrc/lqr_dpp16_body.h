@@ -125,7 +125,7 @@ constexpr bool rgm(int MODE) { return MODE < 1; }                     // registe
 // 1..3 of Quu (Quu[0][0] in element 2 of lane 13).  Registers cannot be indexed by a runtime t, so put / get are
 // switches over t whose cases name their registers statically: a compare tree of ~12 scalar instructions around four
 // register moves (the array lives in the accumulation half of the 512-entry file).
-enum { RG_STEPS = 64 };
+enum { RG_STEPS = rules::DPP16_RG_STEPS };          // (64, lqr_params.h: the host's rules read it too)
 // (the storage itself is the wave interface's: wv::rg_put / wv::rg_get name accumulation registers a[4t .. 4t+3] in
 // inline assembly on the GPU -- as compiler-visible values the 256 registers were copied around at every loop
 // boundary, 112 us against 99 -- and a plain per-lane array in the host emulator)
@@ -2268,7 +2268,7 @@ struct KktFusedArgs {
 // timestep's stores right behind that read: vector stores sit in the same vmcnt queue as the stage DMAs, a counted wait
 // can only count the loads (reads and writes complete out of order with respect to each other), so a wait pays for
 // every store still in flight -- behind the read they have a timestep of arithmetic to land in.
-enum { KF_VBLK = 96 };
+enum { KF_VBLK = rules::DPP16_KF_VBLK };          // (96, lqr_params.h)
 // LONG (round 4): T > RG_STEPS -- the gains of the whole horizon do not fit the 256 accumulation registers; pass 1 stores the
 // record [T,B,64] behind (lambda | g) in the workspace like mode 3 of the step kernel, pass 2's stage carries it as a seventh
 // DMA instruction (+ 1 KiB: five slots in the same staging memory instead of six).  T <= 64 is the kernel of round 3, untouched.

@@ -233,8 +233,35 @@ MPC_DEV void absmax3(float &acc, float a, float b)
 // (the fused KKT builds, whose array may be set by pass 2's ring instead; the step builds assert equality further down)
 static_assert(mpclqr::mfma40::LDS_TOTAL <= MPC_MFMA40_LDS, "the staging array is smaller than the body's rings");
 
-#ifdef MPC_MFMA40_KKT
+// ---- Which build is this? -------------------------------------------------------------------------------------------------------------
+// The shapes and sweep rings the Makefile builds (FLAGS_lqr_mfma40*), each with the launchers of its two objects: without -DMPC_MFMA40_KKT
+// an object holds the step kernel's three modes and exports MPC_MFMA40_STEP_LAUNCH, with it the fused KKT backward's two kernels, no step
+// kernel, and MPC_MFMA40_KF_LAUNCH.  Any other combination of the flags is an error.  What else the step launcher has to know about its
+// build -- the shape, its rule (lqr_rules.hip), what it checks beyond the rule, its texts -- it reads off the body's constants: Build, next to it.
+#define MPC_MFMA40_ON(xt, ring) (MPC_MFMA40_XT == xt && MPC_MFMA40_SWEEP_NSTAGE == ring)
+#if !defined(MPC_MFMA40_PAD) && MPC_MFMA40_ON(2, 3)          // lqr_mfma40.o, lqr_mfma40_kkt.o: the exact shape on three sweep slots
+#define MPC_MFMA40_STEP_LAUNCH launch_step_mfma40
+#define MPC_MFMA40_KF_LAUNCH launch_kkt_fused_mfma40
+#elif !defined(MPC_MFMA40_PAD) && MPC_MFMA40_ON(2, 2) && !defined(MPC_MFMA40_KKT)          // lqr_mfma40_ring2.o: ... on two (the step alone)
+#define MPC_MFMA40_STEP_LAUNCH launch_step_mfma40_ring2
+#elif MPC_MFMA40_PAD == 4 && MPC_MFMA40_ON(2, 2)             // lqr_mfma40_pad4.o, _padkkt.o: padded, dword gathers, two slots
+#define MPC_MFMA40_STEP_LAUNCH launch_step_mfma40_pad4
+#define MPC_MFMA40_KF_LAUNCH launch_kkt_fused_mfma40_pad
+#elif MPC_MFMA40_PAD == 16 && MPC_MFMA40_ON(2, 2)            // lqr_mfma40_pad16.o, _pad16kkt.o: ... 16-byte gathers
+#define MPC_MFMA40_STEP_LAUNCH launch_step_mfma40_pad16
+#define MPC_MFMA40_KF_LAUNCH launch_kkt_fused_mfma40_pad16
+#elif MPC_MFMA40_PAD == 4 && MPC_MFMA40_ON(1, 3)             // lqr_mfma40_narrow4.o, _narrow4kkt.o: padded on ONE state tile, three slots
+#define MPC_MFMA40_STEP_LAUNCH launch_step_mfma40_narrow4
+#define MPC_MFMA40_KF_LAUNCH launch_kkt_fused_mfma40_narrow4
+#elif MPC_MFMA40_PAD == 16 && MPC_MFMA40_ON(1, 3)            // lqr_mfma40_narrow16.o, _narrow16kkt.o
+#define MPC_MFMA40_STEP_LAUNCH launch_step_mfma40_narrow16
+#define MPC_MFMA40_KF_LAUNCH launch_kkt_fused_mfma40_narrow16
+#else
+#error "lqr_mfma40.hip: a combination of MPC_MFMA40_PAD / _XT / _SWEEP_NSTAGE / _KKT that the Makefile does not build"
+#endif
+
 namespace mpclqr {
+#ifdef MPC_MFMA40_KKT
 namespace {
 static_assert(mfma40::KLDS_TOTAL <= MPC_MFMA40_LDS && mfma40::LDS_TOTAL <= MPC_MFMA40_LDS, "the fused KKT kernel's rings do not fit");
 // MODE 0: no bounds; 1: controls on a bound pinned in the nested solve
@@ -245,72 +272,21 @@ template <int MODE> __global__ void __launch_bounds__(64, 1) lqr_kkt_fused_mfma4
 }
 }  // namespace
 
-#if defined(MPC_MFMA40_PAD) && MPC_MFMA40_XT == 1
-// the NARROW instantiation of the padded fused backward (-DMPC_MFMA40_KKT -DMPC_MFMA40_PAD=4 | 16 -DMPC_MFMA40_XT=1 on three sweep slots,
-// lqr_mfma40_narrow4kkt.o / _narrow16kkt.o): n_state <= 16 on one state tile, in a workspace packed for it.  Forced only (capi.hip: kkt_order).
-#if MPC_MFMA40_PAD == 4
-bool kkt_fused_mfma40_narrow_supported(const StepParams<float> &p, const float *ws) { return kkt_fused_mfma40_pad_supported(p, ws) && p.ns <= 16; }
-bool kkt_fused_mfma40_narrow16_supported(const StepParams<float> &p, const float *ws) { return kkt_fused_mfma40_pad16_supported(p, ws) && p.ns <= 16; }
-// floats: K [T,B,8,16] | k [T,B,8] | V [T,B,256] | v,g [T,B,32] | (dx [T,B,16] | du [T,B,8] when the caller keeps none): 448 a problem-step
-int64_t kkt_fused_mfma40_narrow_workspace_bytes(int T, int B)
-{
-    return (int64_t)T * B * (8 * MPC_MFMA40_NS_ + 8 + 256 * MPC_MFMA40_XT * MPC_MFMA40_XT + 32 * MPC_MFMA40_XT + MPC_MFMA40_N_) * 4 + 64;
-}
-#define MPC_KF40_LAUNCH launch_kkt_fused_mfma40_narrow4
-#else
-#define MPC_KF40_LAUNCH launch_kkt_fused_mfma40_narrow16
-#endif
-#elif defined(MPC_MFMA40_PAD)
-// the PADDED instantiation (round 6; -DMPC_MFMA40_KKT -DMPC_MFMA40_PAD=4 on the two-slot sweep ring, lqr_mfma40_padkkt.o): any n_state <= 32,
-// n_ctrl <= 8, dword gathers -- nothing but 4-byte alignment asked of the caller's blocks; the workspace (the library's padded layout) on 16
-#if MPC_MFMA40_PAD == 4
-bool kkt_fused_mfma40_pad_supported(const StepParams<float> &p, const float *ws)
-{
-    return p.ns >= 1 && p.ns <= 32 && p.nc >= 1 && p.nc <= 8 && p.T >= 1 && !p.env.kind && ((uintptr_t)ws & 15) == 0 &&
-           (p.bound_mode != MPC_BOUND_TENSOR || ((((uintptr_t)p.lo | (uintptr_t)p.hi) & 3) == 0));
-}
-// ... with 16-byte gathers (lqr_mfma40_pad16kkt.o): rows of C and F and the x | u boundary on 16 bytes -- a quarter of the staging instructions
-bool kkt_fused_mfma40_pad16_supported(const StepParams<float> &p, const float *ws)
-{
-    auto al = [](const void *q) { return ((uintptr_t)q & 15) == 0; };
-    return kkt_fused_mfma40_pad_supported(p, ws) && p.ns % 4 == 0 && p.nc % 4 == 0 && al(p.C) && (p.T == 1 || al(p.F)) && p.C_st % 4 == 0 &&
-           p.C_sb % 4 == 0 && p.F_st % 4 == 0 && p.F_sb % 4 == 0;
-}
-#define MPC_KF40_LAUNCH launch_kkt_fused_mfma40_pad
-#else
-#define MPC_KF40_LAUNCH launch_kkt_fused_mfma40_pad16
-#endif
-#else
-#define MPC_KF40_LAUNCH launch_kkt_fused_mfma40
-// floats: K [T,B,8,32] | k [T,B,8] | V [T,B,1024] | v,g [T,B,64] | (dx [T,B,32] | du [T,B,8] when the caller keeps none)
-int64_t kkt_fused_mfma40_workspace_bytes(int T, int B) { return (int64_t)T * B * (256 + 8 + 1024 + 64 + 40) * 4 + 64; }
-
-bool kkt_fused_mfma40_supported(const StepParams<float> &p, const float *dl_dx, const float *dl_du, const float *dC,
-                                const float *dF, const float *ws)
-{
-    auto al = [](const void *q, long st, long sb) { return ((uintptr_t)q % 16 == 0) && (st % 4 == 0) && (sb % 4 == 0); };
-    if (!(p.ns == 32 && p.nc == 8 && p.T >= 1)) return false;
-    if (!al(p.C, p.C_st, p.C_sb) || !al(p.c, p.c_st, p.c_sb)) return false;
-    if (p.T > 1 && !al(p.F, p.F_st, p.F_sb)) return false;
-    if (p.bound_mode == MPC_BOUND_TENSOR && ((((uintptr_t)p.lo | (uintptr_t)p.hi) & 3) != 0)) return false;
-    if (p.env.kind) return false;           // (zero_mask / has_delta: the forward's, dropped by the launcher -- mpc/lqr_step.py:322-340)
-    if (p.c_st >= (1L << 30) || (long)p.B * 64 >= (1L << 30)) return false;       // (32-bit record steps, lqr_mfma40_body.h: Stream)
-    return al(p.cur_x, 0, 0) && al(p.cur_u, 0, 0) && al(dl_dx, 0, 0) && al(dl_du, 0, 0) && al(dC, 0, 0) && al(ws, 0, 0) &&
-           (p.T == 1 || al(dF, 0, 0));
-}
-
-#endif
-
 // the nested step with lambda and dlambda riding along (one launch), then the outer products (kkt_wave.hip)
-int MPC_KF40_LAUNCH(const StepParams<float> &p_in, const float *dl_dx, const float *dl_du, float *dC, float *dc, float *dF,
-                            float *df, float *dx_init, float *dx_out, float *du_out, float *ws, float decay, int max_ls,
-                            hipStream_t st)
+int MPC_MFMA40_KF_LAUNCH(const StepParams<float> &p_in, const float *dl_dx, const float *dl_du, float *dC, float *dc, float *dF,
+                         float *df, float *dx_init, float *dx_out, float *du_out, float *ws, float decay, int max_ls, hipStream_t st)
 {
+    using namespace rules;
     StepParams<float> p = p_in;
     const long TB = (long)p.T * p.B;
-    // (two state tiles: 256 | 8 | 1024 | 64 | 32 | 8 words a problem-step; one: 128 | 8 | 256 | 32 | 16 | 8)
-    float *K = ws, *k = K + TB * (8 * MPC_MFMA40_NS_), *V = k + TB * 8, *vg = V + TB * (256 * MPC_MFMA40_XT * MPC_MFMA40_XT),
-          *dx = vg + TB * (32 * MPC_MFMA40_XT), *du = dx + TB * MPC_MFMA40_NS_;
+    // the workspace as lqr_params.h describes it for this build's state tiles (and lqr_rules.hip sizes it)
+    constexpr int XT = mfma40::XT;
+    constexpr int at_K = kf40_off(XT, KF40_K), at_k = kf40_off(XT, KF40_k), at_V = kf40_off(XT, KF40_V), at_vg = kf40_off(XT, KF40_VG),
+                  at_dx = kf40_off(XT, KF40_DX), at_du = kf40_off(XT, KF40_DU);
+    float *K = ws + TB * at_K, *k = ws + TB * at_k, *V = ws + TB * at_V, *vg = ws + TB * at_vg, *dx = ws + TB * at_dx, *du = ws + TB * at_du;
+    static_assert(at_du + mfma40::NC == kf40_off(XT, KF40_END), "the carving ends where the workspace's size does");
+    static_assert(kf40_words(XT, KF40_K) == mfma40::NC * mfma40::NS && kf40_words(XT, KF40_k) == mfma40::NC &&
+                  kf40_words(XT, KF40_DX) == mfma40::NS, "the workspace's parts are the body's");
     if (dx_out && du_out) { dx = dx_out; du = du_out; }
     p.new_x = dx;
     p.new_u = du;
@@ -335,40 +311,50 @@ int MPC_KF40_LAUNCH(const StepParams<float> &p_in, const float *dl_dx, const flo
 #endif
     return launch_kkt_outer(p, dx, du, dC, dc, dF, st);
 }
-}  // namespace mpclqr
 #else
-namespace mpclqr {
 namespace {
+// the step launcher's texts, by shape
+struct StepTexts { const char *refused, *missing, *misaligned, *launch; };
+struct Build {
+    enum Shape { EXACT, PADDED, NARROW };
+    static constexpr Shape SHAPE = !mfma40::PADK ? EXACT : mfma40::XT == 2 ? PADDED : NARROW;
+    static constexpr bool GATHERS16 = mfma40::PADK && mfma40::PADG == 16;
+    static constexpr StepTexts TEXTS[3] = {
+        {"mfma40: needs fp32, n_state = 32, n_ctrl = 8, 16-byte aligned blocks", "mfma40: K / k / new_x / new_u missing",
+         "mfma40: outputs must be 16-byte aligned", "lqr_step_mfma40_kernel: "},
+        {"mfma40 (padded): needs fp32, n_state <= 32, n_ctrl <= 8, max_linesearch_iter <= 16, no simulator", "mfma40 (padded): K / k / new_x / new_u missing",
+         "mfma40 (padded): the gain workspace must be 16-byte aligned", "lqr_step_mfma40_kernel (padded): "},
+        {"mfma40 (narrow): needs fp32, n_state <= 16, n_ctrl <= 8, max_linesearch_iter <= 16, no simulator", "mfma40 (narrow): K / k / new_x / new_u missing",
+         "mfma40 (narrow): the gain workspace must be 16-byte aligned", "lqr_step_mfma40_kernel (narrow): "}};
+    static bool takes(const StepParams<float> &p)
+    {
+        return SHAPE == NARROW ? mfma40_narrow_supported(p) : SHAPE == PADDED ? mfma40_pad_supported(p) : mfma40_supported(p);
+    }
+    // what has to sit on 16 bytes beyond the rule: the exact kernel's outputs, or the padded kernels' own gains in the workspace (p.K / p.k:
+    // [T,B,8,32] or [T,B,8,16] / [T,B,8]; p.K_user / p.k_user are the caller's) -- and the narrow kernel's record
+    static bool misaligned(const StepParams<float> &p)
+    {
+        const uintptr_t more = SHAPE == EXACT ? (uintptr_t)p.new_x | (uintptr_t)p.new_u : SHAPE == NARROW ? (uintptr_t)p.Kk : 0;
+        return (((uintptr_t)p.K | (uintptr_t)p.k | more) & 15) != 0;
+    }
+};
 
+static_assert(mfma40::LDS_TOTAL == MPC_MFMA40_LDS, "the step kernels reserve their rings and nothing more");
 // MODE: 0 unconstrained, 1 unconstrained + u_zero_I, 2 box-constrained (pnqp8 in the sweep)
 template <int MODE> __global__ void __launch_bounds__(64, 1) lqr_step_mfma40_kernel(StepParams<float> p)
 {
     mfma40::step_wave<MODE>(p, p.K, p.k);
 }
-
 }  // namespace
 
-static_assert(mpclqr::mfma40::LDS_TOTAL == MPC_MFMA40_LDS, "the step kernels reserve their rings and nothing more");
-#if defined(MPC_MFMA40_PAD) && MPC_MFMA40_XT == 1
-// ---- the NARROW instantiation (two more compilations: -DMPC_MFMA40_PAD=4 / =16 -DMPC_MFMA40_XT=1): n_state <= 16 on ONE state tile ----
-// The padded kernel below with 24 x 24 | 16 x 24 stages and a fifth of the sweep's MFMAs.  Three sweep slots: a stage is 4352 B
-// and 17 (dword) or 7 (16-byte) staging instructions, so the ring that looks two timesteps ahead fits vmcnt's six bits and costs
-// 13.5 KiB of LDS a wave, where the 32/8 shape's dword gathers (47 a stage) had to stay on two slots.
-#if MPC_MFMA40_PAD == 4
-bool mfma40_narrow_supported(const StepParams<float> &p) { return mfma40_pad_supported(p) && p.ns <= 16; }
-#define MPC_MFMA40_LAUNCH launch_step_mfma40_narrow4
-#else
-#define MPC_MFMA40_LAUNCH launch_step_mfma40_narrow16
-#endif
-// p.K / p.k: the kernel's own gains [T,B,8,16] / [T,B,8] (16-byte aligned, workspace); p.K_user / p.k_user the caller's
-int MPC_MFMA40_LAUNCH(const StepParams<float> &p, hipStream_t st)
+int MPC_MFMA40_STEP_LAUNCH(const StepParams<float> &p, hipStream_t st)
 {
-    if (!mfma40_narrow_supported(p)) { set_last_error("mfma40 (narrow): needs fp32, n_state <= 16, n_ctrl <= 8, max_linesearch_iter <= 16, no simulator"); return MPC_E_DIMS; }
-#if MPC_MFMA40_PAD == 16
-    if (!mfma40_pad16_supported(p)) { set_last_error("mfma40 (narrow): 16-byte gathers need n_state, n_ctrl multiples of 4 and 16-byte aligned blocks"); return MPC_E_ARG; }
-#endif
-    if (!p.K || !p.k || (!p.sweep_only && (!p.new_x || !p.new_u))) { set_last_error("mfma40 (narrow): K / k / new_x / new_u missing"); return MPC_E_NULL; }
-    if (((uintptr_t)p.K & 15) || ((uintptr_t)p.k & 15) || ((uintptr_t)p.Kk & 15)) { set_last_error("mfma40 (narrow): the gain workspace must be 16-byte aligned"); return MPC_E_ARG; }
+    constexpr StepTexts tx = Build::TEXTS[Build::SHAPE];
+    if (!Build::takes(p)) { set_last_error(tx.refused); return MPC_E_DIMS; }
+    // (the padded kernel's 16-byte build is only ever handed calls that pass this, capi.hip: StepRoute::pad16; the narrow one asks)
+    if (Build::SHAPE == Build::NARROW && Build::GATHERS16 && !mfma40_pad16_supported(p)) { set_last_error("mfma40 (narrow): 16-byte gathers need n_state, n_ctrl multiples of 4 and 16-byte aligned blocks"); return MPC_E_ARG; }
+    if (!p.K || !p.k || (!p.sweep_only && (!p.new_x || !p.new_u))) { set_last_error(tx.missing); return MPC_E_NULL; }
+    if (Build::misaligned(p)) { set_last_error(tx.misaligned); return MPC_E_ARG; }
     if (p.bound_mode != MPC_BOUND_NONE)
         hipLaunchKernelGGL(lqr_step_mfma40_kernel<2>, dim3(p.B), dim3(64), 0, st, p);
     else if (p.zero_mask)
@@ -377,99 +363,11 @@ int MPC_MFMA40_LAUNCH(const StepParams<float> &p, hipStream_t st)
         hipLaunchKernelGGL(lqr_step_mfma40_kernel<0>, dim3(p.B), dim3(64), 0, st, p);
     hipError_t e = hipGetLastError();
     if (e != hipSuccess) {
-        set_last_error((std::string("lqr_step_mfma40_kernel (narrow): ") + hipGetErrorString(e)).c_str());
+        set_last_error((std::string(tx.launch) + hipGetErrorString(e)).c_str());
         return MPC_E_LAUNCH;
     }
     return MPC_OK;
 }
-}  // namespace mpclqr
-#elif defined(MPC_MFMA40_PAD)
-// ---- the padded instantiation (two more compilations of this file: -DMPC_MFMA40_PAD=4 / =16, both on the two-slot sweep ring) ----
-#if MPC_MFMA40_PAD == 4
-// any n_state <= 32, n_ctrl <= 8 in float32: every staging access is a dword, nothing but 4-byte alignment is asked for
-bool mfma40_pad_supported(const StepParams<float> &p)
-{
-    return p.ns >= 1 && p.ns <= 32 && p.nc >= 1 && p.nc <= 8 && p.T >= 1 && p.max_ls >= 1 && p.max_ls <= 16 && !p.env.kind &&
-           !(p.bound_mode != MPC_BOUND_NONE && p.zero_mask) &&
-           (p.bound_mode != MPC_BOUND_TENSOR || ((((uintptr_t)p.lo | (uintptr_t)p.hi) & 3) == 0));
-}
-// ... with 16-byte gathers: rows of C and F and the x | u boundary on 16 bytes
-bool mfma40_pad16_supported(const StepParams<float> &p)
-{
-    auto al = [](const void *q) { return ((uintptr_t)q & 15) == 0; };
-    return p.ns % 4 == 0 && p.nc % 4 == 0 && al(p.C) && (p.T == 1 || al(p.F)) && p.C_st % 4 == 0 && p.C_sb % 4 == 0 &&
-           p.F_st % 4 == 0 && p.F_sb % 4 == 0;
-}
-#define MPC_MFMA40_LAUNCH launch_step_mfma40_pad4
-#else
-bool mfma40_pad_supported(const StepParams<float> &p);
-#define MPC_MFMA40_LAUNCH launch_step_mfma40_pad16
 #endif
-// p.K / p.k: the kernel's own padded gains [T,B,8,32] / [T,B,8] (16-byte aligned, workspace); p.K_user / p.k_user the caller's
-int MPC_MFMA40_LAUNCH(const StepParams<float> &p, hipStream_t st)
-{
-    if (!mfma40_pad_supported(p)) { set_last_error("mfma40 (padded): needs fp32, n_state <= 32, n_ctrl <= 8, max_linesearch_iter <= 16, no simulator"); return MPC_E_DIMS; }
-    if (!p.K || !p.k || (!p.sweep_only && (!p.new_x || !p.new_u))) { set_last_error("mfma40 (padded): K / k / new_x / new_u missing"); return MPC_E_NULL; }
-    if (((uintptr_t)p.K & 15) || ((uintptr_t)p.k & 15)) { set_last_error("mfma40 (padded): the gain workspace must be 16-byte aligned"); return MPC_E_ARG; }
-    if (p.bound_mode != MPC_BOUND_NONE)
-        hipLaunchKernelGGL(lqr_step_mfma40_kernel<2>, dim3(p.B), dim3(64), 0, st, p);
-    else if (p.zero_mask)
-        hipLaunchKernelGGL(lqr_step_mfma40_kernel<1>, dim3(p.B), dim3(64), 0, st, p);
-    else
-        hipLaunchKernelGGL(lqr_step_mfma40_kernel<0>, dim3(p.B), dim3(64), 0, st, p);
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) {
-        set_last_error((std::string("lqr_step_mfma40_kernel (padded): ") + hipGetErrorString(e)).c_str());
-        return MPC_E_LAUNCH;
-    }
-    return MPC_OK;
-}
-}  // namespace mpclqr
-#else
-#if MPC_MFMA40_SWEEP_NSTAGE == 3
-bool mfma40_supported(const StepParams<float> &p)
-{
-    auto al = [](const void *q) { return ((uintptr_t)q & 15) == 0; };
-    // (the record's per-lane pointers step by 32-bit byte counts, lqr_mfma40_body.h: Stream)
-    auto fits = [](long elems) { return elems >= 0 && elems < (1L << 30); };
-    return p.ns == 32 && p.nc == 8 && p.T >= 1 && p.max_ls >= 1 && p.max_ls <= 16 && !p.env.kind &&
-           fits(p.c_st) && fits(p.f ? p.f_st : 0) && fits((long)p.B * 64) &&
-           !(p.bound_mode != MPC_BOUND_NONE && p.zero_mask) &&
-           al(p.C) && al(p.c) && (p.T == 1 || al(p.F)) && al(p.cur_x) && al(p.cur_u) && p.C_st % 4 == 0 && p.C_sb % 4 == 0 &&
-           p.c_st % 4 == 0 && p.c_sb % 4 == 0 && p.F_st % 4 == 0 && p.F_sb % 4 == 0 &&
-           (!p.f || (al(p.f) && p.f_st % 4 == 0 && p.f_sb % 4 == 0)) && al(p.x_init) &&
-           // mask bytes and bound rows are read as dwords through the scalar path
-           (!p.zero_mask || ((uintptr_t)p.zero_mask & 3) == 0) &&
-           (p.bound_mode != MPC_BOUND_TENSOR || ((((uintptr_t)p.lo | (uintptr_t)p.hi) & 3) == 0));
-}
-
-#define MPC_MFMA40_LAUNCH launch_step_mfma40
-#else
-bool mfma40_supported(const StepParams<float> &p);
-#define MPC_MFMA40_LAUNCH launch_step_mfma40_ring2
-#endif
-int MPC_MFMA40_LAUNCH(const StepParams<float> &p, hipStream_t st)
-{
-    if (!mfma40_supported(p)) { set_last_error("mfma40: needs fp32, n_state = 32, n_ctrl = 8, 16-byte aligned blocks"); return MPC_E_DIMS; }
-    if (!p.K || !p.k || (!p.sweep_only && (!p.new_x || !p.new_u))) { set_last_error("mfma40: K / k / new_x / new_u missing"); return MPC_E_NULL; }
-    if (((uintptr_t)p.K & 15) || ((uintptr_t)p.k & 15) || ((uintptr_t)p.new_x & 15) || ((uintptr_t)p.new_u & 15)) {
-        set_last_error("mfma40: outputs must be 16-byte aligned");
-        return MPC_E_ARG;
-    }
-    if (p.bound_mode != MPC_BOUND_NONE)
-        hipLaunchKernelGGL(lqr_step_mfma40_kernel<2>, dim3(p.B), dim3(64), 0, st, p);
-    else if (p.zero_mask)
-        hipLaunchKernelGGL(lqr_step_mfma40_kernel<1>, dim3(p.B), dim3(64), 0, st, p);
-    else
-        hipLaunchKernelGGL(lqr_step_mfma40_kernel<0>, dim3(p.B), dim3(64), 0, st, p);
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) {
-        set_last_error((std::string("lqr_step_mfma40_kernel: ") + hipGetErrorString(e)).c_str());
-        return MPC_E_LAUNCH;
-    }
-    return MPC_OK;
-}
 
 }  // namespace mpclqr
-#endif
-#endif

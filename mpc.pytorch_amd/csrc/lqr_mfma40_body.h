@@ -167,7 +167,8 @@ struct KktArgs40 {
     float *vgws;                    // workspace [T,B,32 XT]: v_t | g_t
 };
 // words of a problem-step in those two: 1024 and 32 + 32 at two state tiles, 256 and 16 + 16 at one (the narrow workspace is packed)
-constexpr int VWS_WORDS = 256 * XT * XT, VGWS_WORDS = 32 * XT, VGWS_G = 16 * XT;
+// (lqr_params.h: the one description of that workspace, which the host's size rule and the launcher's carving read too)
+constexpr int VWS_WORDS = rules::kf40_words(XT, rules::KF40_V), VGWS_WORDS = rules::kf40_words(XT, rules::KF40_VG), VGWS_G = 16 * XT;
 // pass 2's stage: F | K_t | record (v_{t+1}, g_{t+1}, k_t) | V_{t+1}; three slots, the DMA two timesteps ahead
 constexpr unsigned KOFF_F = 0, KOFF_K = 4 * NS * N, KOFF_R = KOFF_K + KBYTES, KOFF_V = KOFF_R + 512, KSTAGE_BYTES = KOFF_V + 1024 * XT * XT;   // 5120, 6144, 6656, 10752
 #ifdef MPC_KF40_VFULL

@@ -92,4 +92,24 @@ inline StepParams<real> make_params(const mpc_lqr_problem *p, const mpc_lqr_opti
     return s;
 }
 
+// ---- What the host-side rules of the 12/4 and 32/8 families (lqr_rules.hip) share with the kernel bodies and their launchers ----
+// (lqr_dpp16_body.h and lqr_mfma40_body.h keep their own names for these, as aliases)
+namespace rules {
+// 12/4: the timesteps whose gains the step keeps in registers (beyond: mode 3 / the LONG fused backward), and the (V | v) floats a
+// problem-step of the fused backward's workspace
+constexpr int DPP16_RG_STEPS = 64, DPP16_KF_VBLK = 96;
+// 32/8: the fused backward's workspace on `xt` state tiles of 16 rows, in floats a problem-step --
+// K [T,B,8,16 xt] | k [T,B,8] | V [T,B,256 xt^2] | v,g [T,B,32 xt] | (dx [T,B,16 xt] | du [T,B,8] when the caller keeps none)
+enum { KF40_K, KF40_k, KF40_V, KF40_VG, KF40_DX, KF40_DU, KF40_END };
+constexpr int kf40_words(int xt, int part)
+{
+    return part == KF40_K ? 8 * 16 * xt : part == KF40_k ? 8 : part == KF40_V ? 256 * xt * xt : part == KF40_VG ? 32 * xt :
+           part == KF40_DX ? 16 * xt : 8;
+}
+// ... and where a part begins (KF40_END: the whole); array `part` of the workspace starts T B kf40_off(xt, part) floats in
+constexpr int kf40_off(int xt, int part) { return part == 0 ? 0 : kf40_off(xt, part - 1) + kf40_words(xt, part - 1); }
+static_assert(kf40_off(2, KF40_END) == 256 + 8 + 1024 + 64 + 40 && kf40_off(2, KF40_END) == 1392, "two state tiles: 1392 floats a problem-step");
+static_assert(kf40_off(1, KF40_END) == 448, "one state tile: 448 floats a problem-step");
+}  // namespace rules
+
 }  // namespace mpclqr
