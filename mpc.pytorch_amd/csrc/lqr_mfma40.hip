@@ -206,6 +206,8 @@ MPC_DEV float lds_f32(unsigned off) { return *(const float *)(g_stage40 + off); 
 MPC_DEV f32x4 lds_f32x4(unsigned off) { return *(const f32x4 *)(g_stage40 + off); }
 MPC_DEV void lds_store_f32(unsigned off, float v) { *(float *)(g_stage40 + off) = v; }
 MPC_DEV void store_f32x4(float *g, f32x4 v) { *(f32x4 *)g = v; }
+// (the gains the sweep parks for its rollout: a plain store here, a store the emulator can hold back -- tests/emu/emu_mfma16.cpp)
+MPC_DEV void store_f32_out(float *g, float v) { *g = v; }
 MPC_DEV void fence_own_stores()
 {
     // same-CU visibility of this wave's own global stores (the gains) to its later LDS-DMA reads

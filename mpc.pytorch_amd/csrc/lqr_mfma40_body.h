@@ -251,7 +251,20 @@ struct RecMap {
     long step[2];
     int kind[2];
     bool act[2];
+    bool idle[2];           // wave-uniform: NO lane has a word in this half (rec_idle)
 };
+// An LDS-DMA that no lane takes part in is not issued at all -- hipcc keeps an s_cbranch_execz in front of every conditional one -- so it
+// never enters vmcnt, while every counted wait of a pass assumes CH_R instructions a record: with one of them missing per stage, the wait
+// that should mean "stage t has landed" lets the last instructions of stage t (the other half of this very record among them) still be
+// in flight, and the first timestep of the pass, which no earlier store has pushed along, reads the zeros pad_clear left.  On one state
+// tile the second half of the SWEEP's record (words 64..127) carries only tensor bounds (fused backward) or a caller's QP start (step):
+// without them it is such a half.  rec_issue then gathers it from an empty buffer: 64 zeros over 64 zeros, one instruction, counted.
+// (Two state tiles: both halves carry words of x or u at every shape.)
+MPC_DEV void rec_idle(RecMap &m)
+{
+#pragma unroll
+    for (int j = 0; j < 2; ++j) m.idle[j] = XT == 1 && wv::ballot(m.act[j]) == 0ull;
+}
 // x_next: the x segment holds x_{t+1} (rollouts) instead of x_t (sweep); with_c / with_f / kin: which segments this pass reads
 MPC_DEV void rec_init(RecMap &m, const P &p, int lane, long b, bool with_c, bool x_next, bool with_f, const float *kin)
 {
@@ -289,6 +302,7 @@ MPC_DEV void rec_init(RecMap &m, const P &p, int lane, long b, bool with_c, bool
             }
         }
     }
+    rec_idle(m);
 }
 // ... of the fused backward's sweep (stream_init with kk): words 0..39 r = (dl_dx | dl_du) in the padded tau's order, 40..79 tau*, 80..111
 // c_x of the original problem (lambda's constant term)
@@ -318,6 +332,7 @@ MPC_DEV void rec_init_kkt(RecMap &m, const P &p, int lane, long b, const float *
             if (a < nc) { m.act[j] = true; m.ptr[j] = (const char *)((w < RW_K + 8 ? p.lo : p.hi) + b * nc + a); m.step[j] = (long)p.B * nc * 4; }
         }
     }
+    rec_idle(m);
 }
 // The padded fused backward decides its pinned set from LDS: lane a < 8 of the wave looks at u*[a] and its bounds where the stage
 // holds them (byte offsets of the three 8-word blocks), a ballot makes the two flag words kkt_pinned_word would have assembled from
@@ -342,7 +357,9 @@ MPC_DEV void rec_issue(const RecMap &m, long tl, long tf, long tx, unsigned off,
 #pragma unroll
     for (int j = 0; j < 2; ++j) {
         const long ti = m.kind[j] == 1 ? tf : (m.kind[j] == 2 ? tx : tl);
-        wv::dma4_if(m.act[j] && !(skip_c && j == 0 && lane < N), m.ptr[j] + ti * m.step[j], off + 256u * (unsigned)j);
+        // (an idle half: every lane still holds the pointer rec_init gave it first, the same in all)
+        if (XT == 1 && m.idle[j]) wv::dma_buf<4>(true, wv::uniform_ptr(m.ptr[j]), 0u, 0u, off + 256u * (unsigned)j);
+        else wv::dma4_if(m.act[j] && !(skip_c && j == 0 && lane < N), m.ptr[j] + ti * m.step[j], off + 256u * (unsigned)j);
     }
 }
 // every pass of the padded instantiation starts on cleared staging memory: the record words of padded entries are never
@@ -1461,7 +1478,7 @@ MPC_DEV double sweep_wave(const P &p, float *Kout, float *kout, double *w0_out =
 #pragma unroll
                 for (int J = 0; J < XT; ++J)
 #pragma unroll
-                    for (int v = 0; v < 4; ++v) Kout[(tb * NC + 4 * L.q + v) * NS + 16 * J + L.r] = Kd[J][v];
+                    for (int v = 0; v < 4; ++v) wv::store_f32_out(Kout + (tb * NC + 4 * L.q + v) * NS + 16 * J + L.r, Kd[J][v]);
 #ifdef MPC_MFMA40_PAD
                 // (Kout / kout above are the kernel's own padded gains in the workspace; the caller's K [T,B,nc,ns], if asked for:)
                 if (p.K_user) {
@@ -1483,7 +1500,7 @@ MPC_DEV double sweep_wave(const P &p, float *Kout, float *kout, double *w0_out =
 #pragma unroll
             for (int a = 1; a < 8; ++a) kv = pick(L.lane == a, kk[a], kv);
             if (MODE == 2) kv = kqp_v;
-            kout[tb * NC + L.lane] = kv;
+            wv::store_f32_out(kout + tb * NC + L.lane, kv);
 #ifdef MPC_MFMA40_PAD
             if (p.k_user) wv::st_buf(p.k_user + tb * p.nc, (unsigned)(4 * p.nc), (unsigned)(4 * L.lane), kv);
 #endif

@@ -40,7 +40,7 @@ struct Wave {
     unsigned seq[NL];
     // LDS of the (single-wave) workgroup + the in-order queue of LDS-DMA instructions in flight
     alignas(16) unsigned char lds[160 * 1024];   // a CU's whole LDS (the staged kernels' rings use 40 KB of it, lqr_wave1 up to 150)
-    struct Dma { unsigned char data[NL][16]; bool act[NL]; unsigned char seen[NL]; unsigned off; int size; };
+    struct Dma { unsigned char data[NL][16]; const void *src[NL]; bool act[NL]; unsigned char seen[NL]; unsigned off; int size; };
     Dma q[192];      // (the hardware counter holds 63: issuing beyond that stalls until the oldest lands; landing LATER, as here, is the stricter test)
     int qn;
     int region_start;     // queue entries from here on belong to the current lockstep region
@@ -50,12 +50,61 @@ static void (*g_body)(void);
 // 0: DMA data lands at issue (earliest legal time); 1: it lands only when a counted wait forces it
 // (latest legal time).  A correct kernel gives identical results in both.
 static int g_dma_late = 0;
+// Three further ways in which the hardware may be less kind than the model above; each defaults to off (emu_set_model), and a correct
+// kernel gives identical results under every combination:
+//   SRC_LATE     an LDS-DMA reads its source bytes when it LANDS, not when it issues: a source overwritten between the issue and the
+//                covering wait shows (before: only a destination read too early)
+//   STORES_LATE  the wave's global stores (store_f32x4, st_buf, store_f32_out, ...) wait in a buffer that neither an LDS-DMA nor a
+//                load sees; fence_own_stores(), or a wait that drains the counter to zero, writes it out.  A read-back that relies on
+//                less reads what was there before (the drivers pre-fill their workspaces with NaN)
+//   SKIP_IDLE    an LDS-DMA instruction that NO lane takes part in is not issued and takes no place in the counter: the compiler keeps
+//                an s_cbranch_execz in front of every conditional one.  A counted wait that counted it then covers one instruction
+//                less of the stage it is meant to cover
+enum { MODEL_SRC_LATE = 1, MODEL_STORES_LATE = 2, MODEL_SKIP_IDLE = 4 };
+static int g_model = 0;
+struct Store { void *at; int size; unsigned char bytes[16]; };
+static Store *g_stores = nullptr;
+static size_t g_nstores = 0, g_cap_stores = 0;
+static void global_store(void *at, const void *bytes, int size)
+{
+    if (!(g_model & MODEL_STORES_LATE)) { memcpy(at, bytes, size); return; }
+    if (g_nstores == g_cap_stores) {
+        g_cap_stores = g_cap_stores ? 2 * g_cap_stores : 4096;
+        g_stores = (Store *)realloc(g_stores, g_cap_stores * sizeof(Store));
+    }
+    Store &st = g_stores[g_nstores++];
+    st.at = at;
+    st.size = size;
+    memcpy(st.bytes, bytes, size);
+}
+static void stores_out()
+{
+    for (size_t i = 0; i < g_nstores; ++i) memcpy(g_stores[i].at, g_stores[i].bytes, g_stores[i].size);
+    g_nstores = 0;
+}
+// (at a lockstep point: every lane has passed every instruction queued so far)
+static void drop_idle()
+{
+    if (!(g_model & MODEL_SKIP_IDLE)) return;
+    int n = 0;
+    for (int i = 0; i < W.qn; ++i) {
+        bool any = false;
+        for (int l = 0; l < NL; ++l) any = any || W.q[i].act[l];
+        if (!any) {
+            if (i < W.region_start) --W.region_start;      // (entries are kept in order: the index of those behind moves up by one)
+            continue;
+        }
+        if (n != i) W.q[n] = W.q[i];
+        ++n;
+    }
+    W.qn = n;
+}
 static void dma_land(int keep)
 {
     while (W.qn > keep) {
         Wave::Dma &d = W.q[0];
         for (int l = 0; l < NL; ++l)
-            if (d.act[l]) memcpy(W.lds + d.off + (unsigned)l * d.size, d.data[l], d.size);
+            if (d.act[l]) memcpy(W.lds + d.off + (unsigned)l * d.size, (g_model & MODEL_SRC_LATE) ? d.src[l] : d.data[l], d.size);
         memmove(&W.q[0], &W.q[1], sizeof(Wave::Dma) * (W.qn - 1));
         --W.qn;
         if (W.region_start > 0) --W.region_start;
@@ -95,9 +144,11 @@ static void run_wave(int problem, void (*body)(void))
         }
         if (ndone == NL) break;
         // every lane is now parked at the same lockstep point: the region's DMA instructions are complete
+        drop_idle();
         if (!g_dma_late) dma_land(0);
         W.region_start = W.qn;
     }
+    stores_out();        // the end of the kernel makes them visible
 }
 }  // namespace emu
 
@@ -351,7 +402,7 @@ static inline float swap1(float x)
     emu::yield_lane();
     return w.fa[gen][l ^ 1];
 }
-static inline void store_f32x2_out(float *g, float a, float b) { g[0] = a; g[1] = b; }
+static inline void store_f32x2_out(float *g, float a, float b) { const float v[2] = {a, b}; emu::global_store(g, v, 8); }
 static inline void absmax3(float &acc, float a, float b) { acc = fmaxf(acc, fmaxf(fabsf(a), fabsf(b))); }
 // register-resident gains of lqr_dpp16.hip (accumulation registers a[4t..4t+3] there): one array per lane here
 static f32x4 g_rg[64][64];
@@ -436,8 +487,8 @@ static inline bool any(bool c)
     for (int i = 0; i < 64; ++i) if (w.ia[gen][i]) return true;
     return false;
 }
-static inline void store_f32x4(float *g, f32x4 v) { memcpy(g, &v, 16); }
-static inline void store_f32x4_grad(float *g, f32x4 v) { memcpy(g, &v, 16); }
+static inline void store_f32x4(float *g, f32x4 v) { emu::global_store(g, &v, 16); }
+static inline void store_f32x4_grad(float *g, f32x4 v) { emu::global_store(g, &v, 16); }
 // v_readfirstlane: what the hardware would hand every lane is lane 0's value -- a call site whose value is NOT wave-uniform then goes wrong
 // here as it does on the GPU (round 6: st_buf with a per-lane row forced uniform was caught by the GPU fuzzer, not by the identity this was)
 static inline unsigned uniform_u32(unsigned x) { return (unsigned)readlane_i((int)x, 0); }
@@ -447,8 +498,8 @@ static inline const void *uniform_ptr(const void *q)
     const unsigned lo = uniform_u32((unsigned)v), hi = uniform_u32((unsigned)(v >> 32));
     return (const void *)(((unsigned long long)hi << 32) | (unsigned long long)lo);
 }
-static inline void store_f32_out(float *g, float v) { *g = v; }
-static inline void store_f32_grad(float *g, float v) { *g = v; }
+static inline void store_f32_out(float *g, float v) { emu::global_store(g, &v, 4); }
+static inline void store_f32_grad(float *g, float v) { emu::global_store(g, &v, 4); }
 static inline bool uniform(bool c)
 {
     // must be wave-uniform: check it
@@ -485,6 +536,7 @@ static inline void dma_n(const void *g, unsigned off, int size, bool active = tr
     // an exec-masked lane still passes the instruction: it takes its place in program order
     if (!active) return;
     d->act[l] = true;
+    d->src[l] = g;
     memcpy(d->data[l], g, size);
 }
 static inline void dma16(const void *g, unsigned off) { dma_n(g, off, 16); }
@@ -500,14 +552,14 @@ template <int IMM> static inline void dma16_at_if(bool active, const void *g, un
     dma_n((const char *)g + IMM, (unsigned)((int)mid + IMM), 16, active);
 }
 static inline void dma16_once(const void *g, unsigned off) { dma_n(g, off, 16); }
-static inline void store_out(float *g, float v) { *g = v; }
+static inline void store_out(float *g, float v) { emu::global_store(g, &v, 4); }
 static inline void dma16_if(bool active, const void *g, unsigned off) { dma_n(g, off, 16, active); }
 static inline void dma4(const void *g, unsigned off) { dma_n(g, off, 4); }
 static inline void dma4_if(bool active, const void *g, unsigned off) { dma_n(g, off, 4, active); }
 // buffer_store_dword through a raw buffer of `nbytes`: out-of-range lanes store nothing
 static inline void st_buf(float *base, unsigned nbytes, unsigned voff, float v)
 {
-    if ((unsigned long)voff + 4ul <= (unsigned long)nbytes) memcpy((char *)base + voff, &v, 4);
+    if ((unsigned long)voff + 4ul <= (unsigned long)nbytes) emu::global_store((char *)base + voff, &v, 4);
 }
 // (the hardware's v_readfirstlane under a partial exec mask reads the first ACTIVE lane; the emulator's cross-lane operations are wave-wide
 // rendezvous, and these stores sit behind `if (store)` and the like: the uniformity of their rows is the GPU fuzzer's to check)
@@ -539,7 +591,10 @@ template <int N> static inline void dma_wait()
 {
     // lockstep point: every lane has issued its part of the preceding DMA instructions
     (void)readlane_i(0, 0);
-    if (emu::W.cur == 0) emu::dma_land(emu::g_dma_late ? N : 0);
+    if (emu::W.cur == 0) {
+        emu::dma_land(emu::g_dma_late ? N : 0);
+        if (N == 0) emu::stores_out();        // vector stores share the counter: drained to zero, they have all been written
+    }
 }
 static inline unsigned load_uniform_u32(const unsigned *g) { return *g; }
 static inline float bits_f32(unsigned u) { float f; memcpy(&f, &u, 4); return f; }
@@ -581,7 +636,11 @@ static inline void lds_store_r4(unsigned off, f64x4 v) { memcpy(emu::W.lds + off
 // the hardware executes a wave's DS instructions in order; the lane-serial emulator needs every
 // lane to have passed the preceding stores/loads before any lane goes on
 static inline void lds_sync() { (void)readlane_i(0, 0); }
-static inline void fence_own_stores() {}
+static inline void fence_own_stores()
+{
+    (void)readlane_i(0, 0);                   // every lane's stores in front of the fence are in the buffer
+    if (emu::W.cur == 0) emu::stores_out();
+}
 }  // namespace wv
 }  // namespace mpclqr
 
@@ -603,6 +662,8 @@ template <bool FULL> static void body()
 }
 
 extern "C" void emu_set_dma_late(int late) { emu::g_dma_late = late; }
+// bits: 1 SRC_LATE, 2 STORES_LATE, 4 SKIP_IDLE (above); 0 is the emulator as it was
+extern "C" void emu_set_model(int bits) { emu::g_model = bits; }
 
 extern "C" int emu_lqr_step_mfma16(const mpc_lqr_problem *p, const mpc_lqr_options *o, const mpc_lqr_outputs *out,
                                    int force_general)

@@ -233,8 +233,11 @@ def kkt_grads(C, c, F, f, x_star, u_star, dx, du, dl_dx, dma_late=False, ring2=F
     return out
 
 
+MODEL_SRC_LATE, MODEL_STORES_LATE, MODEL_SKIP_IDLE = 1, 2, 4          # emu_set_model (tests/emu/emu_mfma16.cpp); 0: the emulator as it was
+
+
 def kkt_fused(C, c, F, f, x_star, u_star, dl_dx, dl_du, u_lower=None, u_upper=None, dma_late=False, ring2=True,
-              linesearch_decay=0.2, max_linesearch_iter=10, kernel="dpp16"):
+              linesearch_decay=0.2, max_linesearch_iter=10, kernel="dpp16", model=0):
     """ALL of LQRStepFn.backward (mpc/lqr_step.py:312-407) through the emulated fused kernel (kkt_fused_wave,
     lqr_dpp16_body.h): n_state = 12, n_ctrl = 4, float32.  Returns dC, dc, dF, df, dx_init and the KKT
     solve's own (dx, du).  kernel="dpp16_pad": the padded instantiation, any n_state <= 12, n_ctrl <= 4 (the library's
@@ -274,13 +277,17 @@ def kkt_fused(C, c, F, f, x_star, u_star, dl_dx, dl_du, u_lower=None, u_upper=No
     L.emu_set_dma_late(int(bool(dma_late)))
     vp = ctypes.c_void_p
     L.emu_kkt_fused.argtypes = [ctypes.POINTER(N.Problem), ctypes.POINTER(N.Options)] + [vp] * 10
-    rc = L.emu_kkt_fused(ctypes.byref(p), ctypes.byref(o), _ptr(dl_dx), _ptr(dl_du), _ptr(out["dC"]), _ptr(out["dc"]),
-                         _ptr(out["dF"]), _ptr(out["df"]), _ptr(out["dx_init"]), _ptr(out["dx"]), _ptr(out["du"]), _ptr(out["status"]))
+    L.emu_set_model(int(model))
+    try:
+        rc = L.emu_kkt_fused(ctypes.byref(p), ctypes.byref(o), _ptr(dl_dx), _ptr(dl_du), _ptr(out["dC"]), _ptr(out["dc"]),
+                             _ptr(out["dF"]), _ptr(out["df"]), _ptr(out["dx_init"]), _ptr(out["dx"]), _ptr(out["du"]), _ptr(out["status"]))
+    finally:
+        L.emu_set_model(0)              # the libraries are shared: every other driver runs the emulator as it was
     assert rc == 0, rc
     return out
 
 
-def kkt_fused_mfma40(C, c, F, f, x_star, u_star, dl_dx, dl_du, u_lower=None, u_upper=None, dma_late=False, sweep3=True, pad=0):
+def kkt_fused_mfma40(C, c, F, f, x_star, u_star, dl_dx, dl_du, u_lower=None, u_upper=None, dma_late=False, sweep3=True, pad=0, model=0):
     """LQRStepFn.backward (mpc/lqr_step.py:312-407) at n_state = 32, n_ctrl = 8 through the emulated fused kernel
     (kkt_fused_wave, lqr_mfma40_body.h): dx, du, dx_init, df and the two costates from the kernel; dC, dc, dF are then the
     outer products kkt_outer_kernel (kkt_wave.hip) forms from exactly those vectors (:346-353, :387-396), here in numpy."""
@@ -320,8 +327,12 @@ def kkt_fused_mfma40(C, c, F, f, x_star, u_star, dl_dx, dl_du, u_lower=None, u_u
     L.emu_set_dma_late(int(bool(dma_late)))
     vp = ctypes.c_void_p
     L.emu_kkt_fused_mfma40.argtypes = [ctypes.POINTER(N.Problem), ctypes.POINTER(N.Options)] + [vp] * 8
-    rc = L.emu_kkt_fused_mfma40(ctypes.byref(p), ctypes.byref(o), _ptr(dl_dx), _ptr(dl_du), _ptr(out["dF"]), _ptr(out["df"]),
-                                _ptr(out["dx_init"]), _ptr(out["dx"]), _ptr(out["du"]), _ptr(out["status"]))
+    L.emu_set_model(int(model))
+    try:
+        rc = L.emu_kkt_fused_mfma40(ctypes.byref(p), ctypes.byref(o), _ptr(dl_dx), _ptr(dl_du), _ptr(out["dF"]), _ptr(out["df"]),
+                                    _ptr(out["dx_init"]), _ptr(out["dx"]), _ptr(out["du"]), _ptr(out["status"]))
+    finally:
+        L.emu_set_model(0)
     assert rc == 0, rc
     tau = np.concatenate((x_star, u_star), 2)
     dtau = np.concatenate((out["dx"], out["du"]), 2)

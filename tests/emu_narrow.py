@@ -53,9 +53,9 @@ def lib(pad):
 
 
 def step(L, x_init, C, c, F, f, cur_x, cur_u, full=True, u_lower=None, u_upper=None, u_zero_I=None, delta_u=None,
-         nominal_on_dynamics=False, c_symmetric=False, max_linesearch_iter=10, linesearch_decay=0.2, pnqp_iter=20):
+         nominal_on_dynamics=False, c_symmetric=False, max_linesearch_iter=10, linesearch_decay=0.2, pnqp_iter=20, dma_late=False, model=0):
     """emu_lqr_sweep_mfma40 of the emulator library L (full: the whole step; else the sweep alone) on one float32 problem.
-    Returns every output, the caller's K / k among them."""
+    Returns every output, the caller's K / k among them.  dma_late, model: the emulator's switches (emu_backend.MODEL_*)."""
     f32 = np.float32
     C = np.ascontiguousarray(C, f32); c = np.ascontiguousarray(c, f32); x_init = np.ascontiguousarray(x_init, f32)
     T, B, n, _ = C.shape
@@ -100,10 +100,15 @@ def step(L, x_init, C, c, F, f, cur_x, cur_u, full=True, u_lower=None, u_upper=N
     out = N.Outputs()
     for key, arr in res.items():
         setattr(out, key, E._ptr(arr))
-    L.emu_set_dma_late(0)
+    L.emu_set_dma_late(int(bool(dma_late)))
+    L.emu_set_model(int(model))
     L.emu_mfma40_full(int(bool(full)))
     fn = L.emu_lqr_sweep_mfma40
     fn.argtypes = [ctypes.POINTER(N.Problem), ctypes.POINTER(N.Options), ctypes.POINTER(N.Outputs)]
-    rc = fn(ctypes.byref(p), ctypes.byref(o), ctypes.byref(out))
+    try:
+        rc = fn(ctypes.byref(p), ctypes.byref(o), ctypes.byref(out))
+    finally:
+        L.emu_set_dma_late(0)
+        L.emu_set_model(0)
     assert rc == 0, rc
     return res

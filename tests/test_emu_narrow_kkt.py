@@ -87,3 +87,106 @@ def test_emulated_narrow_fused_kkt_backward_matches_oracle_and_the_padded_librar
         rp = E.kkt_fused_mfma40(*args, dma_late=dma_late, pad=pad)
         for k in ("dx", "du", "dx_init", "dC", "dc") + (("dF", "lam1", "dlam1") if T > 1 else ()) + (("df",) if r["df"] is not None and T > 1 else ()):
             assert _same_bits(r[k], rp[k]), (k, dma_late, pad, np.abs(r[k].astype(np.float64) - rp[k]).max())
+
+
+# ---------------------------------------------------------------------------------------------
+# Horizons past pass 2's three-slot ring, under every combination of the emulator's switches (docs/history/r24.md): the DMA landing
+# at issue or at the covering wait, its source read at issue or at landing, the wave's own stores visible at once or at the fence,
+# an LDS-DMA that no lane takes part in counted or not.  A correct kernel gives identical bits under all sixteen.
+# ---------------------------------------------------------------------------------------------
+KSLOTS = 3                                   # lqr_mfma40_body.h
+MODELS = [(late, model) for late in (False, True) for model in range(8)]
+CORNERS = [(False, 0), (True, 0), (False, 7), (True, 7)]      # T = 70: seventy timesteps a run; every switch off / on, with either landing time
+LONG = ["16_4_T%d_bounded" % (2 * KSLOTS + 1), "13_4_T%d_bounded" % (2 * KSLOTS + 1), "16_4_T%d" % (2 * KSLOTS + 1),
+        "12_4_T%d_tensor" % (2 * KSLOTS + 1), "16_4_T70_B1_bounded"]
+
+
+def _long_problem(case):
+    """the recipe of the test above at the case's horizon and batch -> (arguments of the drivers, the oracle's backward, T)"""
+    from oracle import lqr_oracle as O
+    parts = case.split("_")
+    ns, nc = int(parts[0]), int(parts[1])
+    rng = np.random.default_rng(sum(map(ord, case)) + 11)
+    T = next(int(q[1:]) for q in parts[2:] if q[0] == "T")
+    B = next((int(q[1:]) for q in parts[2:] if q[0] == "B"), 3)
+    pr = _shape_problem(rng, T, B, ns, nc)
+    cur_u = np.clip(0.5 * rng.standard_normal((T, B, nc)), -0.4, 0.4)
+    cur_x, _ = O.traj_cost(pr["x_init"], cur_u, pr["F"], pr["f"])
+    lo, hi = (-0.4, 0.4) if "bounded" in parts else (None, None)
+    if "tensor" in parts:
+        lo, hi = -0.3 - 0.2 * rng.random((T, B, nc)), 0.3 + 0.2 * rng.random((T, B, nc))
+        lo, hi = lo.astype(np.float32).astype(np.float64), hi.astype(np.float32).astype(np.float64)
+    x, u = cur_x, cur_u
+    for _ in range(4):
+        sol = O.lqr_step(lockstep=False, cur_x=x, cur_u=u, u_lower=lo, u_upper=hi, **pr)
+        x, u = sol["new_x"], sol["new_u"]
+    x, u = x.astype(np.float32).astype(np.float64), u.astype(np.float32).astype(np.float64)
+    dl_dx, dl_du = rng.standard_normal((T, B, ns)), rng.standard_normal((T, B, nc))
+    o = O.kkt_backward(pr["C"], pr["c"], pr["F"], pr["f"], x, u, dl_dx, dl_du, lo, hi, lockstep=False)
+    return (pr["C"], pr["c"], pr["F"], pr["f"], x, u, dl_dx, dl_du, lo, hi), o, (ns, nc, T)
+
+
+def _models(T):
+    return MODELS if T < 70 else CORNERS
+
+
+def _identical_under_every_model(run, o, keys, what, models=MODELS):
+    """run(dma_late, model) -> outputs; the plain emulator's are held to the oracle (the tolerance of the test above), every other
+    combination's to the plain emulator's, bit for bit, NaN for NaN"""
+    base = run(False, 0)
+    for k in keys:
+        assert np.isfinite(base[k]).all(), (what, k)
+        np.testing.assert_allclose(base[k], o[k], rtol=2e-4, atol=2e-4 * max(1.0, np.abs(o[k]).max()), err_msg="%s %s" % (what, k))
+    for late, model in models[1:]:
+        r = run(late, model)
+        for k in keys:
+            a, b = np.ascontiguousarray(r[k]).view(np.uint32), np.ascontiguousarray(base[k]).view(np.uint32)
+            assert np.array_equal(a, b), "%s %s: dma_late %d, model %d (1 source at landing | 2 own stores late | 4 idle DMAs not counted) " \
+                "differs from the plain emulator in %d words, first at %s" % (what, k, late, model, int((a != b).sum()), np.argwhere(a != b)[0].tolist())
+
+
+KEYS = ("dx", "du", "dx_init", "dC", "dc", "dF", "df")
+
+
+@pytest.mark.parametrize("case", LONG)
+def test_emulated_narrow_fused_kkt_backward_is_the_same_under_every_switch_of_the_emulator(case):
+    args, o, (ns, nc, T) = _long_problem(case)
+    for pad in ((4,) if T < 70 else ()) + ((16,) if ns % 4 == 0 and nc % 4 == 0 else ()):
+        _identical_under_every_model(lambda late, model: _narrow(pad, *args, dma_late=late, model=model), o, KEYS, "narrow pad %d" % pad, _models(T))
+
+
+@pytest.mark.parametrize("case", LONG)
+def test_emulated_padded_fused_kkt_backward_is_the_same_under_every_switch_of_the_emulator(case):
+    """the two-tile padded library on the same problems"""
+    args, o, (ns, nc, T) = _long_problem(case)
+    for pad in ((4,) if T < 70 else ()) + ((16,) if ns % 4 == 0 and nc % 4 == 0 else ()):
+        _identical_under_every_model(lambda late, model: E.kkt_fused_mfma40(*args, dma_late=late, pad=pad, model=model), o, KEYS, "padded pad %d" % pad,
+                                     _models(T))
+
+
+@pytest.mark.parametrize("case", ["12_4_T%d_bounded" % (2 * KSLOTS + 1), "12_4_T%d" % (2 * KSLOTS + 1), "12_4_T%d_tensor" % (2 * KSLOTS + 1),
+                                  "12_4_T70_B4_bounded"])
+def test_emulated_12_4_fused_kkt_backward_is_the_same_under_every_switch_of_the_emulator(case):
+    """E.kkt_fused: kkt_fused_wave of lqr_dpp16_body.h, four problems a wavefront, both horizon modes (T = 70: the record beyond 64 steps)"""
+    args, o, (_, _, T) = _long_problem(case)
+    _identical_under_every_model(lambda late, model: E.kkt_fused(*args, dma_late=late, model=model), o, KEYS, "12/4", _models(T))
+
+
+@pytest.mark.parametrize("case", ["16_4_T%d_bounded" % (2 * KSLOTS + 1), "13_4_T%d" % (2 * KSLOTS + 1)])
+@pytest.mark.parametrize("vouched", [False, True], ids=["bare", "vouched"])
+def test_emulated_narrow_step_is_the_same_under_every_switch_of_the_emulator(case, vouched):
+    """the one-tile STEP kernel (impl 9) on the same problems, from the point the backward was taken at: its sweep stages the same
+    record, and its rollouts read the parked gains back through the ring"""
+    (C, c, F, f, x, u, _, _, lo, hi), _, (ns, nc, T) = _long_problem(case)
+    keys = ("new_x", "new_u", "costs", "old_costs", "full_du_norm", "alpha_du_norm", "alphas", "K", "k")
+    for pad in (4,) + ((16,) if ns % 4 == 0 and nc % 4 == 0 else ()):
+        run = lambda late, model: EN.step(EN.lib(pad), x[0], C, c, F, f, x, u, u_lower=lo, u_upper=hi, nominal_on_dynamics=vouched,
+                                          c_symmetric=vouched, dma_late=late, model=model)
+        base = run(False, 0)
+        for k in keys[:7]:
+            assert np.isfinite(base[k]).all(), (k, pad)
+        for late, model in MODELS[1:]:
+            r = run(late, model)
+            for k in keys:
+                a, b = np.ascontiguousarray(r[k]).view(np.uint32), np.ascontiguousarray(base[k]).view(np.uint32)
+                assert np.array_equal(a, b), "pad %d %s: dma_late %d, model %d differs from the plain emulator in %d words" % (pad, k, late, model, int((a != b).sum()))
