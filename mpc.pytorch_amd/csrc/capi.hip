@@ -71,9 +71,7 @@ static int env_switch(const EnvSwitch &s, int at_load) { return device_facts().s
 
 // The mode-0 12/4 step on the two-slot ring with a share of F kept in LDS between sweep and rollout (lqr_dpp16_res.o): 39 KiB a wave,
 // so only while one wavefront per SIMD holds the batch -- beyond, 40 KiB would halve the occupancy the short ring is there for.
-#ifndef MPC_DPP16_RESIDENT_DEFAULT
-#define MPC_DPP16_RESIDENT_DEFAULT 1
-#endif
+constexpr bool DPP16_RESIDENT_DEFAULT = true;
 static std::atomic<int64_t> g_resident_launches{0};          // mpc_lqr_resident_launches
 static bool dpp16_resident(const StepParams<float> &q)
 {
@@ -83,7 +81,7 @@ static bool dpp16_resident(const StepParams<float> &q)
     // of base and of DMA source at every timestep), which shows wherever the chain is the launch -- paired, MI355X: B = 2048 +3.6 us,
     // 3072 +3.5, 3584 +1.2, 3840 -0.5, 4096 -1.75 (docs/history/r20.md).  Beyond 15/16 of one wavefront per SIMD it pays.
     const int waves = (q.B + 3) / 4;
-    if (on < 0) on = (MPC_DPP16_RESIDENT_DEFAULT && 16 * (long)waves > 15 * (long)f.simds) ? 1 : 0;
+    if (on < 0) on = (DPP16_RESIDENT_DEFAULT && 16 * (long)waves > 15 * (long)f.simds) ? 1 : 0;
     return on != 0 && q.bound_mode == MPC_BOUND_NONE && !q.zero_mask && q.T >= 2 && q.T <= 64 /* dpp16::RG_STEPS */ && !q.sweep_only &&
            (q.B + 3) / 4 <= f.simds;
 }

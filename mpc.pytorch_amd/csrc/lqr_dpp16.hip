@@ -367,63 +367,40 @@ typedef __attribute__((address_space(1))) const void glb_void_t;
 // cache policy bits of the stage DMAs (see dma16_at).  C is read exactly once per launch: nt (measured
 // 129-132 -> 123-124 us).  F in the rollout is its second and last read -- yet nt there is 6 % SLOWER: the first
 // part of the rollout finds the blocks the sweep touched last still in the Infinity Cache.
-#ifndef MPC_DPP16_C_AUX
-#define MPC_DPP16_C_AUX 2
-#endif
-#ifndef MPC_DPP16_FR_AUX
-#define MPC_DPP16_FR_AUX 0
-#endif
+constexpr int C_AUX = 2, FR_AUX = 0;
 // results nobody in this launch reads again
 MPC_DEV void store_out(float *g, float v)
 {
-#ifdef MPC_DPP16_OUT_CACHED
-    *g = v;
-#else
     __builtin_nontemporal_store(v, g);
-#endif
 }
 // KKT kernel: C and F are read exactly once, dC / dF written exactly once -- yet the plain policies win
 // (measured: nt loads +10 us, non-temporal stores +90 us), so these stay default.  What did pay is the shape of
 // the stores: one register = one row segment of 16 consecutive floats per problem, written as a coalesced dword
 // store (184 -> 139 us against four 16-byte stores per lane at a 64-byte stride).
-#ifndef MPC_KKT_LD_AUX
-#define MPC_KKT_LD_AUX 0
-#endif
+constexpr int KKT_LD_AUX = 0;
 MPC_DEV void dma16_once(const void *g, unsigned off)
 {
-    __builtin_amdgcn_global_load_lds((glb_void_t *)g, (lds_void_t *)(g_stage16 + off), 16, 0, MPC_KKT_LD_AUX);
+    __builtin_amdgcn_global_load_lds((glb_void_t *)g, (lds_void_t *)(g_stage16 + off), 16, 0, KKT_LD_AUX);
 }
 MPC_DEV void store_f32_out(float *g, float v) { *g = v; }
 typedef float f32x2 __attribute__((ext_vector_type(2)));
 // Gradients (dC, dF, dc, df, dx, du) are written once and never read back by the kernel: NON-TEMPORAL stores.  Round 4,
 // same box, fused backward at the headline shape: 218 -> 185 us (0.46 -> 0.54 of its roofline) -- as cached stores the 380 MB of
 // gradients pushed the (V, v, lambda, g) records pass 2 reads back, and the F blocks of both passes, out of the Infinity Cache.
-// -DMPC_KF_CACHED_GRADS restores the cached form for the A/B.  (store_f32_out stays cached: the workspace records.)
+// (store_f32_out stays cached: the workspace records.)
 MPC_DEV void store_f32x2_out(float *g, float a, float b)                                        // 8-byte aligned
 {
-#ifdef MPC_KF_CACHED_GRADS
-    *(f32x2 *)g = f32x2{a, b};
-#else
     __builtin_nontemporal_store(f32x2{a, b}, (f32x2 *)g);
-#endif
 }
 MPC_DEV void store_f32_grad(float *g, float v)
 {
-#ifdef MPC_KF_CACHED_GRADS
-    *g = v;
-#else
     __builtin_nontemporal_store(v, g);
-#endif
 }
 // 16 bytes of a gradient block at 4-byte alignment (the padded fused backward's runs: global memory takes unaligned vector accesses)
 typedef float f32x4_a4 __attribute__((ext_vector_type(4), aligned(4)));
 MPC_DEV void store_f32x4_grad(float *g, float __attribute__((ext_vector_type(4))) v)
 {
-#ifdef MPC_KF_CACHED_GRADS
-    *(f32x4_a4 *)g = v;
-#else
     __builtin_nontemporal_store(v, (f32x4_a4 *)g);
-#endif
 }
 // the value of the neighbouring lane j ^ 1 (quad_perm [1,0,3,2])
 MPC_DEV float swap1(float x) { return __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(x), 0xB1, 0xf, 0xf, true)); }
@@ -473,7 +450,7 @@ template <int IMM, int KIND = DMA_PLAIN> MPC_DEV void dma16_at(const void *g, un
 {
     static_assert(IMM >= -4096 && IMM < 4096, "13-bit signed immediate");
     __builtin_amdgcn_global_load_lds((glb_void_t *)g, (lds_void_t *)(g_stage16 + mid), 16, IMM,
-                                     KIND == DMA_C ? MPC_DPP16_C_AUX : (KIND == DMA_LAST ? MPC_DPP16_FR_AUX : 0));
+                                     KIND == DMA_C ? C_AUX : (KIND == DMA_LAST ? FR_AUX : 0));
 }
 template <int IMM> MPC_DEV void dma16_at_if(bool active, const void *g, unsigned mid)
 {

@@ -63,10 +63,6 @@
 #ifndef MPC_DPP16_NSTAGE
 #define MPC_DPP16_NSTAGE 4
 #endif
-// 1: start the box QP of timestep t from the solution of timestep t+1 like the reference (rounds 1-5; kept for the A/B)
-#ifndef MPC_DPP16_QP_WARM
-#define MPC_DPP16_QP_WARM 0
-#endif
 
 // ---- The PADDED instantiation (round 6; -DMPC_DPP16_PAD, the third compilation of lqr_dpp16.hip): any n_state <= 12, n_ctrl <= 4 --
 // Rounds 1-5 ran every shape of that range other than exactly 12/4 on the one-problem-per-wavefront kernel (lqr_mfma16_body.h) at
@@ -87,6 +83,8 @@
 namespace mpclqr {
 namespace dpp16 {
 constexpr bool PADK = MPC_DPP16_PADK != 0;
+// true: start the box QP of timestep t from the solution of timestep t+1 like the reference (rounds 1-5; kept for the A/B)
+constexpr bool QP_WARM = false;
 constexpr unsigned OOB_OFF = 0x7fff0000u;          // a source offset beyond every block: the gather writes zero there
 enum { PAD_BIAS = 4096 };                          // see wv::dma_buf_at: source offsets are stored as offset - IMM + PAD_BIAS (never negative)
 // slot of the padded tau = [x(12); u(4)] -> index in the caller's tau = [x(ns); u(nc)], or -1 (padding)
@@ -178,14 +176,10 @@ MPC_DEV void gj4_solve(const Gj4 &g, float (&z)[4])
 #pragma unroll
     for (int a = 0; a < 4; ++a) z[a] *= g.inv[a];
 }
-#ifdef MPC_DPP16_QP_LDL           // (the round-3 form of the QP's linear algebra, kept for A/B timing)
-using QpFac4 = Ldl4;
-#else
-using QpFac4 = Gj4;
-#endif
+// (the round-3 form, an LDL' on row-uniform scalars, lost the A/B; Ldl4 stays for the unconstrained / masked solve)
 
 MPC_DEV int pnqp4_rows(const Sym4 &s, const float q[4], const float lb[4], const float ub[4], int n_iter, int j,
-                       float x[4], bool fr_out[4], QpFac4 &f, bool &converged)
+                       float x[4], bool fr_out[4], Gj4 &f, bool &converged)
 {
     // Everything that is one number per unknown (x, g, the bounds, the free-set flags, the step) lives as ONE register
     // with unknown a in the lanes of quad a (lanes 4a..4a+3 of the row): a clamp, a compare, a gradient update is one
@@ -199,10 +193,8 @@ MPC_DEV int pnqp4_rows(const Sym4 &s, const float q[4], const float lb[4], const
     const float Hc[4] = {MPC_QV(s.s00, s.s01, s.s02, s.s03), MPC_QV(s.s01, s.s11, s.s12, s.s13),
                          MPC_QV(s.s02, s.s12, s.s22, s.s23), MPC_QV(s.s03, s.s13, s.s23, s.s33)};
     const float lbv = MPC_QV(lb[0], lb[1], lb[2], lb[3]), ubv = MPC_QV(ub[0], ub[1], ub[2], ub[3]);
-#ifndef MPC_DPP16_QP_LDL
     const float dgv = MPC_QV(dg[0], dg[1], dg[2], dg[3]);
     const bool qd[4] = {q0, q1 && !q0, q2 && !q1, !q2};            // "this lane belongs to quad c"
-#endif
     float xv = MPC_QV(x[0], x[1], x[2], x[3]);
     float mv = -1.f;                                                // free set of the last factorisation (none yet)
     float done = 0.f, conv = 0.f, full = 0.f, it_ret = (float)(n_iter - 1);
@@ -234,33 +226,6 @@ MPC_DEV int pnqp4_rows(const Sym4 &s, const float q[4], const float lb[4], const
         if (done == 0.f) MPC_STAT(1);
         MPC_STAT(6);
         // :44-54  H_ = H on the free block (+1e-11 I, identity elsewhere), dx = -H_^-1 g_
-#ifdef MPC_DPP16_QP_LDL
-        const float mn[4] = {wv::bcast<0>(mnv), wv::bcast<4>(mnv), wv::bcast<8>(mnv), wv::bcast<12>(mnv)};
-        Ldl4 fn;
-        {
-            const float a10 = (mn[0] * mn[1]) * s.s01, a20 = (mn[0] * mn[2]) * s.s02, a30 = (mn[0] * mn[3]) * s.s03;
-            const float a21 = (mn[1] * mn[2]) * s.s12, a31 = (mn[1] * mn[3]) * s.s13, a32 = (mn[2] * mn[3]) * s.s23;
-            const float a00 = fmaf(mn[0], dg[0], 1.f), a11 = fmaf(mn[1], dg[1], 1.f);
-            const float a22 = fmaf(mn[2], dg[2], 1.f), a33 = fmaf(mn[3], dg[3], 1.f);
-            fn.i0 = wv::rcp(a00);
-            fn.l10 = a10 * fn.i0; fn.l20 = a20 * fn.i0; fn.l30 = a30 * fn.i0;
-            const float d1 = fmaf(-fn.l10, a10, a11);
-            fn.i1 = wv::rcp(d1);
-            const float t21 = fmaf(-fn.l20, a10, a21);
-            const float t31 = fmaf(-fn.l30, a10, a31);
-            fn.l21 = t21 * fn.i1; fn.l31 = t31 * fn.i1;
-            const float d2 = fmaf(-fn.l21, t21, fmaf(-fn.l20, a20, a22));
-            fn.i2 = wv::rcp(d2);
-            const float t32 = fmaf(-fn.l31, t21, fmaf(-fn.l30, a20, a32));
-            fn.l32 = t32 * fn.i2;
-            const float d3 = fmaf(-fn.l32, t32, fmaf(-fn.l31, t31, fmaf(-fn.l30, a30, a33)));
-            fn.i3 = wv::rcp(d3);
-        }
-        const float rv = mnv * gv;
-        float y[4];
-        ldl4_solve(fn, wv::bcast<0>(rv), wv::bcast<4>(rv), wv::bcast<8>(rv), wv::bcast<12>(rv), y);
-        const float dxv = -(mnv * MPC_QV(y[0], y[1], y[2], y[3]));
-#else
         Gj4 fn;
         float col[4];
 #define MPC_GJ4_COL(c) do { col[c] = (mnv * wv::bcast<4 * (c)>(mnv)) * Hc[c]; col[c] = qd[c] ? dgq : col[c]; } while (0)
@@ -281,7 +246,6 @@ MPC_DEV int pnqp4_rows(const Sym4 &s, const float q[4], const float lb[4], const
 #undef MPC_GJ4_ELIM
 #undef MPC_GJ4_RHS
         const float dxv = -(sol * invd);
-#endif
         const float nrm2 = wv::ring_sum(dxv * dxv);
         // what this trip factorised is what the solve returns for every row (frozen rows recompute their own)
         f = fn;
@@ -346,11 +310,7 @@ enum {
     SC = 0, SF = 4096, SR = 7168, SG = 8192, STAGE_BYTES = 9216, NSTAGE = MPC_DPP16_NSTAGE, AHEAD = NSTAGE - 1,
     R_c = 0, R_tau = 64, R_f = 128, R_qs = 176, R_lo = 192, R_hi = 208,
     LDS_TOTAL = NSTAGE * STAGE_BYTES,
-#if defined(MPC_PAD_PROBE_DUP) && MPC_DPP16_PADK
-    DMA_SWEEP = 48
-#else
     DMA_SWEEP = MPC_DPP16_PADK ? 32 : 8       // 4 C + 3 F + 1 record (padded instantiation, dwords: 16 + 12 + 4)
-#endif
 };
 // ---- Resident F (-DMPC_DPP16_RESIDENT, the compilation lqr_dpp16_res.o: mode 0 on the two-slot ring, one wavefront per SIMD) ----
 // The rollout's second read of F is the only traffic of the step the result does not need.  With one wavefront per SIMD a wave may
@@ -400,13 +360,8 @@ MPC_DEV bool res_alias(unsigned long long mask, int t, int T) { return t >= T - 
 
 // DMA instructions of one rollout stage: F, record, gains (+ C when priced directly, + (m, M) otherwise
 // when constraints are present)
-#if defined(MPC_PAD_PROBE_DUP) && MPC_DPP16_PADK
-#define MPC_PAD_NF 12
-#define MPC_PAD_NC 32
-#else
 #define MPC_PAD_NF 12
 #define MPC_PAD_NC 16
-#endif
 template <int MODE, bool DIRECT> struct RollDma { enum { N = (MPC_DPP16_PADK ? MPC_PAD_NF + 4 : 3 + 1) + (rgm(MODE) ? 0 : 1) + (DIRECT ? (MPC_DPP16_PADK ? MPC_PAD_NC : 4) : (con(MODE) ? 1 : 0)) }; };
 // The identity-priced rollout does not stage C: its stage is [(m, M)] | gains | F | record = 5 (6) KiB, packed
 // back to back so the same LDS holds 7 (6) stages instead of 4 and the DMA runs 6 (5) timesteps ahead -- a
@@ -418,11 +373,7 @@ template <int MODE, bool DIRECT> struct RollRing {
     enum {
         // (register-resident gains: the stage is F | record = 4 KiB, nine stages in flight)
         BYTES = DIRECT ? (int)STAGE_BYTES : (con(MODE) ? 6144 : (rgm(MODE) ? 4096 : 5120)),
-#ifdef MPC_DPP16_RSLOTS
-        SLOTS = DIRECT ? (int)NSTAGE : (MPC_DPP16_RSLOTS),
-#else
         SLOTS = DIRECT ? (int)NSTAGE : (int)LDS_TOTAL / (con(MODE) ? 6144 : (rgm(MODE) ? 4096 : 5120)),
-#endif
         FOFF = DIRECT ? (int)SF : (con(MODE) ? 2048 : (rgm(MODE) ? 0 : 1024)),        // F block inside a slot
         GADJ = DIRECT ? 0 : (int)SF - 1024 - (int)SG,                // gains / (m, M) relative to the lane offsets,
         MADJ = DIRECT ? 0 : (int)SF - 2048 - (int)SC                 // which are written for the sweep's layout
@@ -461,9 +412,6 @@ MPC_DEV int src_granule_cols(int g, int problem_slot) { return g ^ ((problem_slo
 // C: position (row r', quarter q') of problem slot k holds source row R = r' ^ k, quarter q' ^ s(R)
 MPC_DEV int src_granule_C(int g, int problem_slot)
 {
-#ifdef MPC_DPP16_NO_CPERM          // diagnostic build (tools/ab_sym.py): rows where they were, column reads 4-way conflicted
-    problem_slot = 0;
-#endif
     const int R = (g >> 2) ^ (problem_slot & 3);
     return 4 * R + ((g & 3) ^ quarter_swizzle(R));
 }
@@ -528,11 +476,7 @@ MPC_DEV void lane_init(Lane &L, int lane, int wave, int B, bool cperm = true)
     L.lane = lane;
     L.p = lane >> 4;
     L.j = lane & 15;
-#ifdef MPC_DPP16_NO_CPERM
-    const int cp = 0;
-#else
     const int cp = cperm ? L.p : 0;          // row permutation of this problem slot's C block (src_granule_C)
-#endif
     const int pb = 4 * wave + L.p;
     L.b0 = 4 * wave;
     L.live = pb < B;
@@ -615,9 +559,6 @@ MPC_DEV void dma_seek(Dma &d, const P &p, const Lane &L, int wave)
     const long tf0 = (ROLL || T < 2) ? 0 : T - 2;
     d.c_step = 4 * p.C_st;
     d.f_step = T > 1 ? 4 * p.F_st : 0;
-#ifdef MPC_DPP16_PROBE_ROLL_F          // (diagnostic build only: the rollouts read timestep 0's F at every timestep -- WRONG results, the time of a
-    if (ROLL) d.f_step = 0;            //  step whose rollout costs no HBM traffic for F: the bound of every scheme that keeps F on chip)
-#endif
     d.g_step = 4 * B * 64;
     d.g2_step = 4 * B * 4;
 #pragma unroll
@@ -739,14 +680,8 @@ template <int MODE, bool ROLL, bool DIRECT, int K> MPC_DEV void pad_part(const D
     constexpr bool WITH_C = !ROLL || DIRECT;
     // sweep / direct rollout: C 0-7 | C 8-15 | F 0-7 | F 8-11 + record;   packed rollout: F 0-5 | F 6-11 | record | -
     // (ONE LDS anchor per block -- the stage's C block, its F block -- and the gather's place as the instruction's immediate)
-#if defined(MPC_PAD_PROBE_DUP) && MPC_DPP16_PADK          // (diagnostic build only: every gather of C issued twice -- the same results, the time of a stage of 48 instead of 32 instructions)
-#define MPC_PAD_C(kk) do { wv::dma_buf_at<256 * (kk), PAD_BIAS>(d.Cb[(kk) >> 2], d.cbytes, d.coff[kk], mid - 4096); \
-                           wv::dma_buf_at<256 * (kk), PAD_BIAS>(d.Cb[(kk) >> 2], d.cbytes, d.coff[kk], mid - 4096); } while (0)
-#define MPC_PAD_F(kk) wv::dma_buf_at<256 * (kk), PAD_BIAS>(d.Fb[(kk) / 3], d.fbytes, d.foff[kk], mid)
-#else
 #define MPC_PAD_C(kk) wv::dma_buf_at<256 * (kk), PAD_BIAS>(d.Cb[(kk) >> 2], d.cbytes, d.coff[kk], mid - 4096)
 #define MPC_PAD_F(kk) wv::dma_buf_at<256 * (kk), PAD_BIAS>(d.Fb[(kk) / 3], d.fbytes, d.foff[kk], mid)
-#endif
 #define MPC_PAD_R(kk) wv::dma4_at_if<3072 + 256 * (kk)>(d.rq_act[kk], d.rq[kk], mid)
     if (WITH_C) {
         if (K == 0) { MPC_PAD_C(0); MPC_PAD_C(1); MPC_PAD_C(2); MPC_PAD_C(3); MPC_PAD_C(4); MPC_PAD_C(5); MPC_PAD_C(6); MPC_PAD_C(7); }
@@ -1107,15 +1042,9 @@ MPC_DEV void sweep_step(const P &p, const Lane &L, const SwStage &s, SwState &st
     // ---- the 4x4 control block: row-uniform copies out of lanes 12..15 --------------------------
     Sym4 S;
     float qu[4];
-#ifdef MPC_DPP16_DPP_BCAST          // (rounds 1-3: fourteen DPP row broadcasts, each a v_mov_b32_dpp behind its wait states)
-    S.s00 = wv::bcast<12>(Q[12]); S.s01 = wv::bcast<13>(Q[12]); S.s02 = wv::bcast<14>(Q[12]); S.s03 = wv::bcast<15>(Q[12]);
-    S.s11 = wv::bcast<13>(Q[13]); S.s12 = wv::bcast<14>(Q[13]); S.s13 = wv::bcast<15>(Q[13]);
-    S.s22 = wv::bcast<14>(Q[14]); S.s23 = wv::bcast<15>(Q[14]);
-    S.s33 = wv::bcast<15>(Q[15]);
-    qu[0] = wv::bcast<12>(q); qu[1] = wv::bcast<13>(q); qu[2] = wv::bcast<14>(q); qu[3] = wv::bcast<15>(q);
-#else
     // Round 4: the 4x4x1 outer product with a unit B operand IS a broadcast -- d[v] (every lane of the row) = a (lane 12 + v) * 1:
-    // four lanes' values in one instruction (exact: one multiplication by 1, + 0).  Five instructions for Quu and qu.
+    // four lanes' values in one instruction (exact: one multiplication by 1, + 0).  Five instructions for Quu and qu; the DPP form
+    // of rounds 1-3 was fourteen `v_mov_b32_dpp`, each behind its wait states.
     {
         const f32x4 z4 = {0.f, 0.f, 0.f, 0.f};
         const f32x4 r0 = wv::mfma4<3>(Q[12], 1.f, z4), r1 = wv::mfma4<3>(Q[13], 1.f, z4);
@@ -1126,12 +1055,11 @@ MPC_DEV void sweep_step(const P &p, const Lane &L, const SwStage &s, SwState &st
         S.s33 = r3[3];
         qu[0] = rq[0]; qu[1] = rq[1]; qu[2] = rq[2]; qu[3] = rq[3];
     }
-#endif
 
     bool fr[4] = {true, true, true, true};
     const bool valid[4] = {true, true, true, true};
     Ldl4 f;
-    QpFac4 qf;                      // box QP: the factorisation of its last trip
+    Gj4 qf;                         // box QP: the factorisation of its last trip
     float kq[4] = {0.f, 0.f, 0.f, 0.f};
     if (!con(MODE)) {
         float sing = 0.f;
@@ -1145,14 +1073,10 @@ MPC_DEV void sweep_step(const P &p, const Lane &L, const SwStage &s, SwState &st
     } else {
         // :128-141 box constraints in delta space
         float lb[4], ub[4], ubar[4];
-#ifdef MPC_DPP16_DPP_BCAST
-        ubar[0] = wv::bcast<12>(s.tb); ubar[1] = wv::bcast<13>(s.tb); ubar[2] = wv::bcast<14>(s.tb); ubar[3] = wv::bcast<15>(s.tb);
-#else
         {
             const f32x4 ru = wv::mfma4<3>(s.tb, 1.f, f32x4{0.f, 0.f, 0.f, 0.f});
             ubar[0] = ru[0]; ubar[1] = ru[1]; ubar[2] = ru[2]; ubar[3] = ru[3];
         }
-#endif
         const float dlt = p.has_delta ? p.delta_u : 3.0e38f;       // :132-134 (no trust region: never the tighter bound)
 #pragma unroll
         for (int a = 0; a < 4; ++a) {
@@ -1164,7 +1088,7 @@ MPC_DEV void sweep_step(const P &p, const Lane &L, const SwStage &s, SwState &st
             // (a NaN start would survive the clamp and poison the QP: such an entry falls back to the middle of the box's reach)
 #pragma unroll
             for (int a = 0; a < 4; ++a) kq[a] = (s.qs[a] == s.qs[a]) ? s.qs[a] : 0.f;
-        } else if (!MPC_DPP16_QP_WARM || !st.warm) {
+        } else if (!QP_WARM || !st.warm) {
             // cold start x = -H^-1 q (mpc/pnqp.py:14-19) -- at EVERY timestep whose Quu is positive definite (round 6).  The reference
             // hands timestep t the solution of timestep t+1 (mpc/lqr_step.py:137,141); a strictly convex QP has ONE minimiser, so
             // the start decides the trip count and nothing else (qp_start), and the clamped unconstrained minimiser is the
@@ -1208,9 +1132,6 @@ MPC_DEV void sweep_step(const P &p, const Lane &L, const SwStage &s, SwState &st
 #pragma unroll
             for (int a = 0; a < 4; ++a) K[a] = -y[a];
         } else {
-#ifdef MPC_DPP16_QP_LDL
-            ldl4_solve(MODE == 2 ? qf : f, fr[0] ? rhs[0] : 0.f, fr[1] ? rhs[1] : 0.f, fr[2] ? rhs[2] : 0.f, fr[3] ? rhs[3] : 0.f, y);
-#else
             if (MODE == 2) {
 #pragma unroll
                 for (int a = 0; a < 4; ++a) y[a] = fr[a] ? rhs[a] : 0.f;
@@ -1218,7 +1139,6 @@ MPC_DEV void sweep_step(const P &p, const Lane &L, const SwStage &s, SwState &st
             } else {
                 ldl4_solve(f, fr[0] ? rhs[0] : 0.f, fr[1] ? rhs[1] : 0.f, fr[2] ? rhs[2] : 0.f, fr[3] ? rhs[3] : 0.f, y);
             }
-#endif
 #pragma unroll
             for (int a = 0; a < 4; ++a) K[a] = fr[a] ? -y[a] : 0.f;
             if (MODE == 2) {
@@ -1235,33 +1155,20 @@ MPC_DEV void sweep_step(const P &p, const Lane &L, const SwStage &s, SwState &st
     float M[4] = {0.f, 0.f, 0.f, 0.f};
     if (con(MODE)) {
         // with a full free set Qux + Quu K vanishes; with masked / clamped controls it does not
-#ifdef MPC_DPP16_DPP_BCAST
-        M[0] = fmaf(S.s03, K[3], fmaf(S.s02, K[2], fmaf(S.s01, K[1], fmaf(S.s00, K[0], rhs[0]))));
-        M[1] = fmaf(S.s13, K[3], fmaf(S.s12, K[2], fmaf(S.s11, K[1], fmaf(S.s01, K[0], rhs[1]))));
-        M[2] = fmaf(S.s23, K[3], fmaf(S.s22, K[2], fmaf(S.s12, K[1], fmaf(S.s02, K[0], rhs[2]))));
-        M[3] = fmaf(S.s33, K[3], fmaf(S.s23, K[2], fmaf(S.s13, K[1], fmaf(S.s03, K[0], rhs[3]))));
-#else
         // M = Qux + Quu K as four rank-1 updates on the matrix core: column b of Quu sits in lanes 12..15 of register Q[12 + b]
         // (Quu symmetric), row b of K one entry per lane -- the same multiply-adds in the same order, four instructions for sixteen
         f32x4 Mv = {rhs[0], rhs[1], rhs[2], rhs[3]};
 #pragma unroll
         for (int b = 0; b < 4; ++b) Mv = wv::mfma4<3>(Q[12 + b], K[b], Mv);
         M[0] = Mv[0]; M[1] = Mv[1]; M[2] = Mv[2]; M[3] = Mv[3];
-#endif
     }
     wv::sched_fence();
     feed.template part<3>();
     wv::sched_fence();              // the matrix-core block of the value update, undivided
 #pragma unroll
     for (int a = 0; a < 4; ++a) outer_acc(Vn, Q[12 + a], K[a]);      // += Qux[a][i] K[a][j]  (Qux = Qxu')
-#ifdef MPC_DPP16_KEEP_KM
-    // K'(Qux + Quu K) is zero but for rounding: a pinned row of K is exactly zero, a free row of the bracket is what the
-    // solve above enforced (lqr_mfma40_body.h dropped the term in round 3; diagnostic switch for the A/B)
-    if (con(MODE)) {
-#pragma unroll
-        for (int a = 0; a < 4; ++a) outer_acc(Vn, K[a], M[a]);       // += K[a][i] M[a][j]
-    }
-#endif
+    // (K'(Qux + Quu K) is zero but for rounding -- a pinned row of K is exactly zero, a free row of the bracket is what the solve
+    // above enforced -- and is not added, as in lqr_mfma40_body.h since round 3)
     wv::sched_fence();
     float vn = q;
     // (K and M were finished in front of the matrix-core block above: settled sources, no wait states)
@@ -2571,11 +2478,7 @@ MPC_DEV void kkt_fused_wave(const P &p, const KktFusedArgs &k)
                 lam = ln;
                 gv = gn;
                 // V_t (upper triangle: register r of lane j is V[r][j], kept for j >= r), v_t, lambda_t, g_t -> workspace
-#ifdef MPC_KF_SKIP           // diagnostic builds (tools/ab_kkt_phases.sh): 1 no workspace stores, 2 no gradient stores, 4 pass 1 only
-                if (xs_lane && !(MPC_KF_SKIP & 1)) {
-#else
                 if (xs_lane) {
-#endif
 #pragma unroll
                     for (int r = 0; r < 12; ++r)
                         if (L.j >= r) wv::store_f32_out(vp + (tri_off(r) - r), Vn[r]);
@@ -2602,9 +2505,6 @@ MPC_DEV void kkt_fused_wave(const P &p, const KktFusedArgs &k)
     // dx_init = -dlambda_0 = -(V_0 0 + v_0 + (1 - alpha) g_0)   (:404)
     if (L.live && xs_lane && (!PADK || L.ovalid)) k.dx_init[pb * ns_o + L.j] = -fmaf(1.f - alpha, gv, vv);
     wv::fence_own_stores();            // (V, v, lambda, g) come back through the DMA
-#ifdef MPC_KF_SKIP
-    if (MPC_KF_SKIP & 4) return;
-#endif
 
     // ---- pass 2: rollout of the nested solve + every gradient of the timestep -------------------------------------
     // stage (5.5 KiB): F (row order) | record: granules 4-6 x*, 7 u*, 8-10 lambda_{t+1}, 11-13 g_{t+1} | (V | v)_{t+1} x 4
@@ -2781,12 +2681,7 @@ MPC_DEV void kkt_fused_wave(const P &p, const KktFusedArgs &k)
                 wv::dma_wait<(KF_P2_AHEAD - 1) * KF_P2_DMA>();
                 read2(s2, (i + 1) % KF_P2_SLOTS);
 #ifdef MPC_DPP16_PAD
-#ifdef MPC_KF_SKIP
-                const bool skip_ = (MPC_KF_SKIP & 2) && t != T - 1;
-#else
-                const bool skip_ = false;
-#endif
-                if (full4 && !skip_) {
+                if (full4) {
                     // dC_t: park the columns, gather the run, 16 bytes a lane (DS instructions of a wave execute in order)
                     wv::lds_sync();
 #pragma unroll
@@ -2809,7 +2704,7 @@ MPC_DEV void kkt_fused_wave(const P &p, const KktFusedArgs &k)
                         }
                     }
                 }
-                if (L.live && L.ovalid && !skip_) {
+                if (L.live && L.ovalid) {
                     if (so_p) wv::store_f32_grad(so_p, dj);
                     if (have) {
                         if (!full4) {
@@ -2850,11 +2745,7 @@ MPC_DEV void kkt_fused_wave(const P &p, const KktFusedArgs &k)
                     pC0[r / 2] = odd ? n1 : colC[r];
                     pC1[r / 2] = odd ? colC[r + 1] : n0;
                 }
-#ifdef MPC_KF_SKIP
-                if (L.live && (!(MPC_KF_SKIP & 2) || t == T - 1)) {
-#else
                 if (L.live) {
-#endif
                     if (so_p) wv::store_f32_grad(so_p, dj);
                     if (have) {
 #pragma unroll

@@ -69,13 +69,10 @@
 #define MPC_M16_NS mfma16
 #endif
 
-// 1: start the box QP of timestep t from the solution of timestep t+1 like the reference (rounds 1-5; kept for the A/B)
-#ifndef MPC_MFMA16_QP_WARM
-#define MPC_MFMA16_QP_WARM 0
-#endif
-
 namespace mpclqr {
 namespace MPC_M16_NS {
+// true: start the box QP of timestep t from the solution of timestep t+1 like the reference (rounds 1-5; kept for the A/B)
+constexpr bool QP_WARM = false;
 
 typedef StepParams<real> P;
 typedef typename wv::vec4_of<real>::type rx4;
@@ -424,7 +421,7 @@ MPC_DEV void sweep_step(const P &p, const Lane &L, const SwStage &s, SwState &st
         // WITHOUT taking that step (mpc/pnqp.py:56-59), so where the reference ends -- to within 1e-4 -- does depend on where it
         // started, and the float64 instantiation is held to the reference at 1e-9; in float32 that 1e-4 is inside the tolerance
         // and inside what the reference's own float32 and float64 runs differ by)
-        constexpr bool REF_START = MPC_MFMA16_QP_WARM || sizeof(real) == 8;
+        constexpr bool REF_START = QP_WARM || sizeof(real) == 8;
         if (!REF_START || !st.warm) {
             // cold start x = -H^-1 q (mpc/pnqp.py:14-19) at EVERY timestep whose Quu is positive definite (round 6, see
             // lqr_dpp16_body.h: a better guess of the active set than the reference's start k_{t+1} by a whole trip per QP; a convex

@@ -150,14 +150,12 @@ template <int IMM> MPC_DEV void dma16_at_if(bool active, const void *g, unsigned
 {
     if (active) __builtin_amdgcn_global_load_lds((glb_void_t *)g, (lds_void_t *)(g_stage40 + off), 16, IMM, 0);
 }
-// ... of a block read exactly once per launch: the non-temporal policy (aux bit 1; -DMPC_MFMA40_C_AUX=0 for the A/B)
-#ifndef MPC_MFMA40_C_AUX
-#define MPC_MFMA40_C_AUX 2
-#endif
+// ... of a block read exactly once per launch: the non-temporal policy (aux bit 1)
+constexpr int C_AUX = 2;
 template <int IMM> MPC_DEV void dma16_once_at(const void *g, unsigned off)
 {
     static_assert(IMM >= 0 && IMM < 4096, "13-bit signed immediate");
-    __builtin_amdgcn_global_load_lds((glb_void_t *)g, (lds_void_t *)(g_stage40 + off), 16, IMM, MPC_MFMA40_C_AUX);
+    __builtin_amdgcn_global_load_lds((glb_void_t *)g, (lds_void_t *)(g_stage40 + off), 16, IMM, C_AUX);
 }
 // ---- the padded instantiation's staging (lqr_mfma40_body.h, PADK) -------------------------------------------------------------
 // G bytes per lane from `base + voff` (base wave-uniform: a raw buffer of `nbytes`, voff per lane) to LDS offset `off` + G * lane.
@@ -308,9 +306,6 @@ int MPC_MFMA40_KF_LAUNCH(const StepParams<float> &p_in, const float *dl_dx, cons
         set_last_error((std::string("lqr_kkt_fused_mfma40_kernel: ") + hipGetErrorString(e)).c_str());
         return MPC_E_LAUNCH;
     }
-#ifdef MPC_KF40_NO_OUTER          // (diagnostic build: the fused kernel without its memory-bound neighbour, tools/ab_cfg5b.py)
-    return MPC_OK;
-#endif
     return launch_kkt_outer(p, dx, du, dC, dc, dF, st);
 }
 #else

@@ -33,16 +33,13 @@
 #define MPC_DEVM MPC_DEV
 #endif
 
-// 1: start the box QP of timestep t from the solution of timestep t+1 like the reference (the product).
-// 0: pnqp's cold start at every timestep whose Quu is positive definite, as the 12/4 kernel does since round 6 -- measured level
-// here: 3.27 -> 2.41 trips per QP, but the 8 x 8 LDL' and its solve cost what the saved trip costs (box-constrained step at
-// B = 1024: 396 us against 394, gpurun_out r06b) -- so this kernel keeps the reference's start and the reference's path.
-#ifndef MPC_MFMA40_QP_WARM
-#define MPC_MFMA40_QP_WARM 1
-#endif
-
 namespace mpclqr {
 namespace mfma40 {
+// true: start the box QP of timestep t from the solution of timestep t+1 like the reference (the product).
+// false: pnqp's cold start at every timestep whose Quu is positive definite, as the 12/4 kernel does since round 6 -- measured level
+// here: 3.27 -> 2.41 trips per QP, but the 8 x 8 LDL' and its solve cost what the saved trip costs (box-constrained step at
+// B = 1024: 396 us against 394, round 6) -- so this kernel keeps the reference's start and the reference's path.
+constexpr bool QP_WARM = true;
 
 // c ? a : b on two values that both sit in registers.  Written through wv::pin because hipcc otherwise folds a
 // select of two elements of a small local array into ONE dynamically indexed load, which puts the array in scratch
@@ -171,19 +168,13 @@ struct KktArgs40 {
 constexpr int VWS_WORDS = rules::kf40_words(XT, rules::KF40_V), VGWS_WORDS = rules::kf40_words(XT, rules::KF40_VG), VGWS_G = 16 * XT;
 // pass 2's stage: F | K_t | record (v_{t+1}, g_{t+1}, k_t) | V_{t+1}; three slots, the DMA two timesteps ahead
 constexpr unsigned KOFF_F = 0, KOFF_K = 4 * NS * N, KOFF_R = KOFF_K + KBYTES, KOFF_V = KOFF_R + 512, KSTAGE_BYTES = KOFF_V + 1024 * XT * XT;   // 5120, 6144, 6656, 10752
-#ifdef MPC_KF40_VFULL
-constexpr int KSLOTS = 3, KDMA_PER_STAGE = 11;                 // 5 (F) + 1 (K) + 1 (record) + 4 (V)
-#else
 constexpr int KSLOTS = 3, KDMA_PER_STAGE_EXACT = 10;           // 5 (F) + 1 (K) + 1 (record) + 3 (V: tiles (0,0), (1,0), (1,1))
-#endif
-#ifndef MPC_KF40_VFULL
 // pass 2 of the fused backward: F (gathered in the padded instantiation: CH_F instructions) + K + record + three V tiles
 // (+ 3 in the padded instantiation: u*_t and its tensor bounds, words 0..23 of the record, for the pinned set -- kkt_pinned_lds);
 // one state tile has the one V tile (0,0)
 constexpr int KDMA_V = XT > 1 ? 3 : 1;
 constexpr int KDMA_PER_STAGE = PADK ? CH_F + 5 + KDMA_V : KDMA_PER_STAGE_EXACT;
 static_assert((KSLOTS - 2) * KDMA_PER_STAGE < 64, "vmcnt is 6 bits");
-#endif
 // the constrained modes' record for the rollout that prices without C (rollout_priced): floats per problem-step
 constexpr int PREC = NC * NS + NC * NC + NC;                   // M [8][32] | Quu [8][8] | m [8]: 328
 constexpr int PSCR = N;                                      // behind the records [T,B,PREC]: the second line-search trial's x' | u' [T,B,40]
@@ -725,11 +716,7 @@ MPC_DEV void gj8v_solve(const Gj8V &f, float (&z)[8])
 #pragma unroll
     for (int a = 0; a < 8; ++a) z[a] *= f.inv[a];
 }
-#ifdef MPC_MFMA40_QP_LDL          // (the round-3 form of the QP's linear algebra, kept for A/B timing)
-using QpFac = Ldl8V;
-#else
-using QpFac = Gj8V;
-#endif
+// (the round-3 form, an LDL' per trip, lost the A/B; Ldl8V stays for the cold start and the unconstrained / masked solve)
 
 MPC_DEV float clampf(float x, float lo, float hi)
 {
@@ -835,7 +822,7 @@ MPC_DEV float gather8(const float (&y)[8], int r)
     return v;
 }
 MPC_DEV int pnqp8v(const float (&col0)[8], float diagv, float qv, float lbv, float ubv, int n_iter, int r, float &xv,
-                   float &mv, QpFac &f, bool &converged)
+                   float &mv, Gj8V &f, bool &converged)
 {
     int it_ret = n_iter - 1;
     converged = false;
@@ -859,20 +846,11 @@ MPC_DEV int pnqp8v(const float (&col0)[8], float diagv, float qv, float lbv, flo
         }
         float colm[8];
         Pnqp8vMat<0>::run(col0, mnv, fmaf(mnv, dgm, 1.f), r, colm);   // :44-48
-#ifdef MPC_MFMA40_QP_LDL
-        Ldl8V fn;
-        ldl8v(fn, colm);
-        float y[8];
-        Pnqp8vSpread<0>::run(mnv * gv, y);
-        ldl8v_solve(fn, y);                                        // :50-54
-        const float dxv = -(mnv * gather8(y, r));
-#else
         // (rows off the free set are identity rows with a zero right-hand side: their entry of the solution is 0 as it comes)
         Gj8V fn;
         float sol = mnv * gv;
         gj8v(fn, colm, sol, r);                                    // :50-54
         const float dxv = -sol;
-#endif
         const float nrm2 = wv::row_sum8(dxv * dxv);       // (the vectors live in lanes 0..7; lane 0 reads the sums)
         float mxv = xv + dxv;
         const bool outside = wv::any((mxv < lbv) | (mxv > ubv));
@@ -908,19 +886,14 @@ MPC_DEV int pnqp8v(const float (&col0)[8], float diagv, float qv, float lbv, flo
 MPC_DEV void kkt_store_vvg(const KktArgs40 &kx, long tb, const Lane &L, const wv::f32x4 (&Vd)[XT][XT], const float (&vcol)[XT][4],
                            const float (&gcol)[XT][4])
 {
-#ifdef MPC_KF40_NOVS              // (diagnostic build: what the V stores cost)
-    if (tb < 0)
-#endif
     // (round 4) V is symmetric: tile (0, 1) is the transpose of tile (1, 0) and stays home -- pass 2 reads it out of the staged
-    // (1, 0) tile with the indices swapped (`-DMPC_KF40_VFULL`: all four tiles, as in round 3).  3 KiB per problem-step each way
+    // (1, 0) tile with the indices swapped (round 3 stored all four tiles).  3 KiB per problem-step each way
     // instead of 4 in a kernel that moves 1.9 GB at 5 TB/s.
 #pragma unroll
     for (int I = 0; I < XT; ++I)
 #pragma unroll
         for (int J = 0; J < XT; ++J) {
-#ifndef MPC_KF40_VFULL
             if (I == 0 && J == 1) continue;
-#endif
             wv::store_f32x4(kx.Vws + tb * VWS_WORDS + (XT * I + J) * 256 + 4 * L.lane, Vd[I][J]);
         }
     if (L.r == 0) {
@@ -1215,7 +1188,7 @@ MPC_DEV double sweep_wave(const P &p, float *Kout, float *kout, double *w0_out =
         // identity rows and columns of the factorised matrix (Pnqp8vMat).  (Round 2 read Quu out with 36 readlanes and
         // factorised on wave-uniform values in the constrained modes.)
         Ldl8V facv;
-        QpFac qpf;                      // box QP: the factorisation of its last trip
+        Gj8V qpf;                       // box QP: the factorisation of its last trip
         float kqp_v = 0.f, frq_v = 1.f; // box QP: its solution k and its free set (1 / 0), lane a of every row: entry a
         float qu[8], kk[8];
         bool fr[8];
@@ -1308,9 +1281,9 @@ MPC_DEV double sweep_wave(const P &p, float *Kout, float *kout, double *w0_out =
                 xv = wv::lds_f32(base + OFF_R + 4 * RW_K + 4u * (unsigned)(r8 ? L.r : 0));
                 xv = (r8 && (!PADK || L.r < p.nc)) ? xv : 0.f;
                 xv = (xv == xv) ? xv : 0.f;              // (a NaN would survive the clamp)
-            } else if (!MPC_MFMA40_QP_WARM || !warm) {
-                // cold start x = -H^-1 q (mpc/pnqp.py:14-19): the first QP of the sweep -- or, with MPC_MFMA40_QP_WARM = 0, every QP
-                // whose Quu is positive definite (see the switch's comment: measured level at this shape, not the product)
+            } else if (!QP_WARM || !warm) {
+                // cold start x = -H^-1 q (mpc/pnqp.py:14-19): the first QP of the sweep -- or, with QP_WARM = false, every QP
+                // whose Quu is positive definite (see the constant's comment: measured level at this shape, not the product)
                 float colc[8], y[8];
 #pragma unroll
                 for (int a = 0; a < 8; ++a) colc[a] = col0[a];
@@ -1366,11 +1339,7 @@ MPC_DEV double sweep_wave(const P &p, float *Kout, float *kout, double *w0_out =
                     sol[a] = fr[a] ? x : 0.f;                                                         // :142-143
                 }
                 if (MODE == 2) free_rows<0>(frq_v, rhs, sol);
-#ifdef MPC_MFMA40_QP_LDL
-                ldl8v_solve(MODE == 2 ? qpf : facv, sol);
-#else
                 if (MODE == 2) gj8v_solve(qpf, sol); else ldl8v_solve(facv, sol);
-#endif
                 if (MODE == 2) {
                     free_rows<0>(frq_v, sol, sol);
                 } else {
@@ -1413,7 +1382,6 @@ MPC_DEV double sweep_wave(const P &p, float *Kout, float *kout, double *w0_out =
                 Kd[0][v] = L.q < 2 ? k0 : 0.f;
                 if (XT > 1) Kd[XT - 1][v] = L.q < 2 ? k1 : 0.f;
             }
-#ifndef MPC_MFMA40_KPAD
             // (round 4) A contraction over the eight controls is register v of the operand tiles for v = 0..3, and in each only
             // lane groups q = 0, 1 (controls v and 4 + v) are not padding: half of every MFMA's k.  Moving the lower halves of
             // registers v, v + 1 side by side (one v_permlane32_swap each) makes it TWO full MFMAs per output tile instead of four:
@@ -1454,26 +1422,6 @@ MPC_DEV double sweep_wave(const P &p, float *Kout, float *kout, double *w0_out =
 #pragma unroll
                     for (int J = 0; J < XT; ++J) Vd[I][J] = wv::mfma(Ap[I][h], Kp[J][h], Vd[I][J]);
             wv::sched_fence();
-#else
-            if (MODE != 0) {
-#pragma unroll
-                for (int J = 0; J < XT; ++J) {
-                    Md[J] = Qd[XT][J];
-#pragma unroll
-                    for (int v = 0; v < 4; ++v) Md[J] = wv::mfma(Qd[XT][XT][v], Kd[J][v], Md[J]);
-                }
-            }
-#pragma unroll
-            for (int I = 0; I < XT; ++I)
-#pragma unroll
-                for (int J = 0; J < XT; ++J) Vd[I][J] = Qd[I][J];
-#pragma unroll
-            for (int v = 0; v < 4; ++v)
-#pragma unroll
-                for (int I = 0; I < XT; ++I)
-#pragma unroll
-                    for (int J = 0; J < XT; ++J) Vd[I][J] = wv::mfma(Qd[XT][I][v], Kd[J][v], Vd[I][J]);
-#endif
             if (L.q < 2) {
 #pragma unroll
                 for (int J = 0; J < XT; ++J)
@@ -2500,9 +2448,6 @@ MPC_DEV void kstage_issue(const P &p, const RStream &d, const char *v_ptr, long 
         wv::dma4_if(act, (tb_ ? p.lo : p.cur_u) + o, base + KOFF_R + 32);
         wv::dma4_if(act, (tb_ ? p.hi : p.cur_u) + o, base + KOFF_R + 64);
     }
-#ifdef MPC_KF40_VFULL
-    dma_kib<4>(v_ptr + tx * v_step + d.lo, base + KOFF_V);
-#else
     {
         // tiles (0,0), (1,0), (1,1): KiB 0, 2, 3 of the record (the slot keeps its 4 KiB; KiB 1 is never written nor read)
         const char *vp = v_ptr + tx * v_step + d.lo;
@@ -2513,7 +2458,6 @@ MPC_DEV void kstage_issue(const P &p, const RStream &d, const char *v_ptr, long 
             wv::dma16_at<3072>(vp, base + KOFF_V);
         }
     }
-#endif
 }
 
 template <int MODE>
@@ -2625,19 +2569,15 @@ MPC_DEV void kkt_pass2(const P &p, const Lane &L, const float *Kin, const float 
         for (int I = 0; I < XT; ++I)
 #pragma unroll
             for (int J = 0; J < XT; ++J) {
-#ifndef MPC_KF40_VFULL
                 if (I == 0 && J == 1) continue;
-#endif
                 Vt[I][J] = wv::lds_f32x4(base + KOFF_V + 1024u * (unsigned)(XT * I + J) + 16u * (unsigned)L.lane);
             }
-#ifndef MPC_KF40_VFULL
         // tile (0,1), register v of lane (q,r) = V[4q+v][16+r] = V[16+r][4q+v] = register r & 3 of lane (r >> 2, 4q + v) of tile (1,0)
         if (XT > 1) {
 #pragma unroll
             for (int v = 0; v < 4; ++v)
                 Vt[0][XT - 1][v] = wv::lds_f32(base + KOFF_V + 2048u + 16u * (unsigned)(16 * (L.r >> 2) + 4 * L.q + v) + 4u * (unsigned)(L.r & 3));
         }
-#endif
         f32x4 DL[XT];
 #pragma unroll
         for (int Im = 0; Im < XT; ++Im) {
@@ -2743,9 +2683,6 @@ template <int MODE> MPC_DEV void kkt_fused_wave(const P &p, float *K, float *k, 
     float v0g0[4] = {0.f, 0.f, 0.f, 0.f};
     (void)sweep_wave<MODE, true>(p, K, k, &w0, &kx, v0g0);
     wv::fence_own_stores();            // K, k, V, v, g come back through the DMA
-#ifdef MPC_KF40_P1_ONLY                 // (diagnostic build: where the time goes, tools/ab_kkt40_phases.sh)
-    if (w0 != 1.2345e300) return;
-#endif
     kkt_pass2<MODE>(p, L, K, k, kx, w0, v0g0);
 }
 
@@ -2773,10 +2710,6 @@ template <int MODE> MPC_DEV void step_wave(const P &p, float *K, float *k)
 #endif
     if (p.sweep_only) return;           // MPC_OPT_SWEEP_ONLY (the sweep has written K, k, old_costs, qp_iters, status)
     wv::fence_own_stores();
-#ifdef MPC_CFG5_SWEEP_ONLY
-    if (old_cost == 1.2345e300) return;    // (diagnostic build: the sweep alone; keeps old_cost / w0 alive)
-    if (old_cost != 1.2345e300) { if (wv::lane() == 0 && p.costs) p.costs[wv::problem()] = (float)(old_cost + w0); return; }
-#endif
     if (MODE == 0 && on_dyn) {          // vouched for by the caller, or verified by the sweep
         Lane L;
         L.lane = wv::lane();

@@ -203,10 +203,7 @@ template <int NS> MPC_DEV void step_wave(const StepParams<float> &p)
 
     // ------------------------------------------------------------------ P2: the Riccati recursion
     int status = 0, qp_total = 0;
-#ifndef MPC_W1_SKIP                                            // (diagnostic builds, tools/ab_w1_phases.sh: bit 0 = no P2, 1 = no P3, 2 = no P4)
-#define MPC_W1_SKIP 0
-#endif
-    if (!(MPC_W1_SKIP & 1)) {
+    {
         const int jc = j < N ? j : N - 1;                     // (columns >= N idle along on column N - 1's data)
         float Vc[NS], vj = 0;                                 // column j of V_{t+1}, element j of v_{t+1}
         for (int i = 0; i < NS; ++i) Vc[i] = 0;
@@ -223,16 +220,7 @@ template <int NS> MPC_DEV void step_wave(const StepParams<float> &p)
             g.hi = bounded ? wv::sm(L.hi + t) : 0.f;
             g.mask = masked_call ? wv::sm(L.mask + t) : 0.f;
         };
-#ifdef MPC_W1_PROF                                             // (diagnostic build: clock stamps of one timestep of wavefront 0 into qp_iters[8..])
-#define W1_STAMP(k) do { if (t == T / 2) stamp[k] = wv::clock(); } while (0)
-#define W1_STAMP5 stamp[5] = wv::clock()
-        long long stamp[8] = {0, 0, 0, 0, 0, 0, 0, 0};
-#else
-#define W1_STAMP(k) do { } while (0)
-#define W1_STAMP5 (void)0
-#endif
         auto riccati = [&](int t, const Stage &now) {
-            W1_STAMP(0);
             float qj = now.cb, Qc[N], Qjn = now.Crn;          // q[j]; column j of Q; Q[j][NS]
             for (int i = 0; i < N; ++i) Qc[i] = now.Cc[i];
             if (t < T - 1) {                                  // Q = C + F'VF, q = c_back + F'v (:65-70)
@@ -247,7 +235,6 @@ template <int NS> MPC_DEV void step_wave(const StepParams<float> &p)
                 }
                 static_for<0, NS>([&](auto m) { wv::fmac_bcast<m.value>(qj, vj, now.Fc[m.value]); });
             }
-            W1_STAMP(1);
             const float Quu = wv::bcast<NS>(Qc[NS]), qu = wv::bcast<NS>(qj);
             float Kj, k;
             if (!bounded) {
@@ -272,7 +259,6 @@ template <int NS> MPC_DEV void step_wave(const StepParams<float> &p)
                 Kj = is_free ? -(Qc[NS] * env_inv(Hf)) : 0.f; // :142-146
             }
             kprev = k;
-            W1_STAMP(2);
             wv::sm(L.K + t * N + jc) = j < NS ? Kj : k;       // (every lane stores: columns >= N repeat k in column N - 1's slot)
             if ((p.K || p.k) && active) {                     // (a wavefront-uniform test first: mpc.MPC's loop asks for no gains)
                 const long tb = (long)t * B + b;
@@ -283,7 +269,6 @@ template <int NS> MPC_DEV void step_wave(const StepParams<float> &p)
                 }
             }
             // :155-158 V = Qxx + Qxu K + K'Qux + K'Quu K, v likewise (unmasked Quu, qu)
-            W1_STAMP(3);
             const float Mj = Qc[NS] + Quu * Kj, mk = qu + Quu * k;
             static_for<0, NS>([&](auto i) {
                 float v = Qc[i.value];
@@ -292,8 +277,6 @@ template <int NS> MPC_DEV void step_wave(const StepParams<float> &p)
                 Vc[i.value] = v;
             });
             vj = qj + Qjn * k + Kj * mk;
-            W1_STAMP(4);
-            if (t == T / 2 - 1) W1_STAMP5;
         };
         // two stages that take turns (the body is compiled twice): the operands of step t - 1 are read from LDS while step t
         // is computed, and nothing is copied from one stage to the other
@@ -306,17 +289,13 @@ template <int NS> MPC_DEV void step_wave(const StepParams<float> &p)
             if (t > 1) fetch(t - 2, sa);
             riccati(t - 1, sb);
         }
-#ifdef MPC_W1_PROF
-        if (wv::problem() == 0 && lane == 0 && p.qp_iters)
-            for (int k = 0; k < 5; ++k) p.qp_iters[8 + k] = (int)(stamp[k + 1] - stamp[k]);
-#endif
     }
     wv::lds_sync();
 
     // ------------------------------------------------------------------ P3: every line-search trial at once
     float alpha = 1, dun = 0;
     for (int i = 0; i < j && i < ntr; ++i) alpha *= p.ls_decay;         // the same products the sequential search forms
-    if (j < ntr && !(MPC_W1_SKIP & 2)) {
+    if (j < ntr) {
         const int xo = L.X + j * T * N;
         float x[NS], dx[NS], da = 0;
         for (int i = 0; i < NS; ++i) {
@@ -397,7 +376,7 @@ template <int NS> MPC_DEV void step_wave(const StepParams<float> &p)
     double cost = 0;
     {
         const int g = j & (Gp - 1), slice = j / Gp, nsl = 16 / Gp;
-        if (g < ntr && !(MPC_W1_SKIP & 4))
+        if (g < ntr)
             for (int t = slice; t < T; t += nsl) {
                 float tau[N];
                 for (int i = 0; i < N; ++i) tau[i] = wv::sm(L.X + (g * T + t) * N + i);
@@ -431,9 +410,6 @@ template <int NS> MPC_DEV void step_wave(const StepParams<float> &p)
     if (p.full_du_norm) p.full_du_norm[b] = full;
     if (p.alpha_du_norm) p.alpha_du_norm[b] = win_dun;
     if (p.alphas) p.alphas[b] = win_alpha;
-#ifdef MPC_W1_PROF
-    if (b >= 8 && b < 16) return;
-#endif
     if (p.qp_iters) p.qp_iters[b] = qp_total;
     if (p.status) p.status[b] = status;
 }

@@ -12,7 +12,6 @@ extern __shared__ float g_sm[];
 MPC_DEV float &sm(int i) { return g_sm[i]; }
 MPC_DEV int lane() { return (int)threadIdx.x; }
 MPC_DEV int problem() { return (int)blockIdx.x; }
-MPC_DEV long long clock() { return (long long)__builtin_readcyclecounter(); }
 // lane N of the caller's 16-lane row (DPP row_newbcast)
 template <int N> MPC_DEV float bcast(float x)
 {
