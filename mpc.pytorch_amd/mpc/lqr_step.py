@@ -12,6 +12,7 @@ Module-valued `true_dynamics` / `true_cost` keep the sweep on the kernel; the sh
 `mpc.dynamics.NNDynamics` (fp32) also roll out inside kernels, any other module is called timestep by
 timestep in a loop of device ops.
 """
+import copy
 import os
 import weakref
 from collections import OrderedDict, namedtuple
@@ -470,16 +471,15 @@ def LQRStep(n_state,
                 rp = (tC, tc, tF, tf)     # true cost / dynamics differ from the quadratic model
             o = opts
             if sim:                        # a shipped simulator rolls out inside the kernel (:223-225)
-                o = StepOptions(u_lower=u_lower, u_upper=u_upper, u_zero_I=u_zero_I, delta_u=delta_u,
-                                linesearch_decay=linesearch_decay, max_linesearch_iter=max_linesearch_iter,
-                                true_dynamics=true_dynamics.native_env(), c_symmetric=c_symmetric)
+                o = copy.copy(opts)
+                o.true_dynamics = true_dynamics.native_env()
             r = be.lqr_step(x_init, C, c, F, f_in, current_x, current_u, o, rollout_problem=rp, want_gains=ref_norm)
             fdn = r["full_du_norm"]
             if ref_norm:
                 # the controls of the FULL step for every problem (the accepted trajectory of a problem that backtracked is
                 # another one): lqr_forward once more with max_linesearch_iter = 1, then the reference's mixed-up norm
-                o1 = StepOptions(u_lower=u_lower, u_upper=u_upper, u_zero_I=u_zero_I, delta_u=delta_u,
-                                 linesearch_decay=linesearch_decay, max_linesearch_iter=1, c_symmetric=c_symmetric)
+                o1 = copy.copy(opts)
+                o1.max_linesearch_iter = 1
                 full = be.lqr_rollout(x_init.detach(), tC.detach(), tc.detach(), tF.detach(), None if tf is None else tf.detach(),
                                       current_x.detach(), current_u.detach(), r["K"], r["k"], o1, old_costs=r["old_costs"])
                 fdn = be.du_norm_reference(current_u.detach(), full["new_u"])

@@ -22,6 +22,9 @@ QuadCost = namedtuple("QuadCost", "C c")
 LinDx = namedtuple("LinDx", "F f")
 QuadCost.__new__.__defaults__ = (None,) * len(QuadCost._fields)
 LinDx.__new__.__defaults__ = (None,) * len(LinDx._fields)
+# What `MPC._route` decides, once per solve (`MPC.solve_route`).  loop: "planned", "slew", "network" or "general"; dynamics: what
+# that loop runs on -- None (general), "lin", an EnvSpec or an MlpSpec; ref_norm: `reference_du_norm` with a batch
+SolveRoute = namedtuple("SolveRoute", "loop dynamics ref_norm shared_ending")
 
 
 class GradMethods(Enum):
@@ -31,34 +34,27 @@ class GradMethods(Enum):
     ANALYTIC_CHECK = 4
 
 
+def _grad_tensors(module):
+    """The tensors of a module that ask for a gradient: parameters and plain tensor attributes (the shipped simulators keep
+    `params` as one), lists and tuples of them included, recursively over sub-modules."""
+    for m in module.modules():
+        for v in list(m.parameters(recurse=False)) + list(vars(m).values()):
+            for t in (v if isinstance(v, (list, tuple)) else (v,)):
+                if torch.is_tensor(t) and t.requires_grad:
+                    yield t
+
+
 def _any_requires_grad(obj):
-    """Does a QuadCost / LinDx / module carry a tensor that asks for a gradient?  Modules are searched
-    through parameters, buffers and plain tensor attributes (the shipped simulators keep `params` as
-    one), recursively over sub-modules."""
+    """Does a QuadCost / LinDx / module (searched by `_grad_tensors`) carry a tensor that asks for a gradient?"""
     if isinstance(obj, (QuadCost, LinDx)):
         return any(torch.is_tensor(t) and t.requires_grad for t in obj)
-    if isinstance(obj, Module):
-        for m in obj.modules():
-            for v in list(m.parameters(recurse=False)) + list(vars(m).values()):
-                if torch.is_tensor(v) and v.requires_grad:
-                    return True
-                if isinstance(v, (list, tuple)) and any(torch.is_tensor(t) and t.requires_grad for t in v):
-                    return True
-        return False
-    return False
+    return isinstance(obj, Module) and any(True for _ in _grad_tensors(obj))
 
 
 def _only_params_require_grad(dx):
-    """Is `dx.params` the one tensor of the module (searched like _any_requires_grad) that asks for a gradient?"""
+    """Is `dx.params` the one tensor of the module (searched by `_grad_tensors`) that asks for a gradient?"""
     prm = getattr(dx, "params", None)
-    if not (torch.is_tensor(prm) and prm.requires_grad):
-        return False
-    for m in dx.modules():
-        for v in list(m.parameters(recurse=False)) + list(vars(m).values()):
-            for t in (v if isinstance(v, (list, tuple)) else (v,)):
-                if torch.is_tensor(t) and t.requires_grad and t is not prm:
-                    return False
-    return True
+    return torch.is_tensor(prm) and prm.requires_grad and all(t is prm for t in _grad_tensors(dx))
 
 
 _PINNED = collections.OrderedDict()     # (device, stream, host thread) -> [pinned block, its int32 view, tag counter]; LRU, see _FlagReader
@@ -210,16 +206,15 @@ class MPC(Module):
         # module route at (12, 4, [100]) but slower at (32, 8, [100]) (docs/history/r10.md)
         self.weight_grad_kernel = bool(weight_grad_kernel)
         # OPT-IN: a slew-rate penalty around an NNDynamics on the pre-bound device loop (`_iterate_slew` -> `_iterate_network` on the
-        # augmented problem, mpc_mlp_linearize_carry) instead of `_iterate_general`.  Off by default whatever it measures:
-        # tests/test_gpu_nn.py::test_slew_rate_penalty_on_the_network_kernels and tests/test_gpu_nn_wide.py::
+        # augmented problem, mpc_mlp_linearize_carry) instead of `_iterate_general` (which networks: `solve_route`).  Off by default
+        # whatever it measures: tests/test_gpu_nn.py::test_slew_rate_penalty_on_the_network_kernels and tests/test_gpu_nn_wide.py::
         # test_slew_rate_penalty_on_a_wide_network pin the general route by spying on HipBackend.mlp_rollout, a method a pre-bound
         # iteration never goes through (it calls mpc_mlp_rollout itself), and existing tests are the yardstick of every change
         self.planned_network_slew = bool(planned_network_slew)
         # OPT-IN: the pre-bound loops (`_iterate_planned`, through it `_iterate_slew`, and `_iterate_network`) bind their step plans
-        # with _native.IMPL_MFMA40_NARROW -- the padded 32/8 kernel on one 16-row state tile -- instead of IMPL_AUTO.  The
-        # criterion (`_narrow_impl_kw`), at the sizes the loop runs at (n_state + n_ctrl states on the slew route: 12/4 becomes
-        # 16/4): the backend's `impl_supported` takes them for impl 9 AND does not take them for IMPL_DPP16_PAD -- shapes up to
-        # 12/4 have faster kernels of their own and stay auto's.  Everywhere else IMPL_AUTO, as ever.
+        # with _native.IMPL_MFMA40_NARROW -- the padded 32/8 kernel on one 16-row state tile -- instead of IMPL_AUTO, where
+        # `_forced_impl` says so at the sizes the loop runs at (n_state + n_ctrl states on the slew route: 12/4 becomes 16/4) --
+        # shapes up to 12/4 have faster kernels of their own and stay auto's.  Everywhere else IMPL_AUTO, as ever.
         # A forced kernel reads C through its symmetry and only FLAGS a C that is not symmetric, where impl 0 solves such a
         # problem again: a narrow-bound loop whose first step reports the bit starts over on IMPL_AUTO plans (`_drive`), so x, u
         # and costs are the flag-off solve's for every C.  The price: iteration 1 is launched after the flags of iteration 0 are
@@ -239,18 +234,16 @@ class MPC(Module):
         self.narrow_kkt_kernel = bool(narrow_kkt_kernel)
         # OPT-IN: a slew-rate solve around a shipped simulator (`_iterate_slew` -> `_iterate_planned` with the simulator behind
         # ENV_CTRL_CARRY) binds its step plans with _native.IMPL_WAVE1_CARRY -- a 16-lane row per problem instead of a lane per
-        # problem -- where the backend's `impl_supported` takes the step for impl 10 AND its `row_carry_pays` says the batch is small
-        # enough for the row kernel to hold it resident at once, at the sizes the loop runs at (`_row_carry_impl_kw`).  Everywhere
-        # else -- float64, a LinDx slew solve, a larger batch, a backend without the query -- IMPL_AUTO, as ever: bitwise the
-        # flag-off solve.  Off by default: auto routes every carry call to the lane-per-problem kernel and existing tests pin that;
-        # the row kernel's time against it is a measurement of docs/history/r21.md, not a promise.  The differentiable ending does
-        # not look at the flag
+        # problem -- where `_forced_impl` says so at the sizes the loop runs at.  Everywhere else -- float64, a LinDx slew solve, a
+        # larger batch, a backend without the query -- IMPL_AUTO, as ever: bitwise the flag-off solve.  Off by default: auto routes
+        # every carry call to the lane-per-problem kernel and existing tests pin that; the row kernel's time against it is a
+        # measurement of docs/history/r21.md, not a promise.  The differentiable ending does not look at the flag
         self.row_carry_kernel = bool(row_carry_kernel)
         # OPT-IN: a QuadCost / LinDx given in batch-shared form (C [T,n,n] or [n,n], c [T,n] or [n], F [T-1,ns,n] or [ns,n], f
         # likewise) reaches the final no-op step UN-expanded, whose backward then sums the gradients over the batch inside the
         # kernels (lqr_step._LQRStepSharedFn, mpc_lqr_kkt_grads_shared) instead of writing one [n,n] block per problem for
-        # autograd's expand to add up.  The iterations are untouched.  Slew-rate solves, module costs, `reference_du_norm` with a
-        # batch and views the caller expanded themselves keep the per-problem route.  Off by default (docs/history/r14.md)
+        # autograd's expand to add up.  The iterations are untouched.  Which solves (`solve_route`: `shared_ending`); views the
+        # caller expanded themselves keep the per-problem route.  Off by default (docs/history/r14.md)
         self.shared_grad_kernel = bool(shared_grad_kernel)
         self.flag_reducer = None     # set by mpc.shard for lock-step sharded solves
         self.prev_ctrl = prev_ctrl
@@ -293,7 +286,8 @@ class MPC(Module):
             raise ValueError("MPC Error: Unexpected LinDx shape.")
         return LinDx(F, f)
 
-    def forward(self, x_init, cost, dx):
+    def _expand_args(self, x_init, cost, dx):
+        """What `forward` and `solve_route` start from -> (n_batch, cost, dx), a QuadCost / LinDx as [T,B,...] views."""
         assert isinstance(cost, (QuadCost, Module)) or callable(cost)
         assert isinstance(dx, (LinDx, Module)) or callable(dx)
         if self.n_batch is not None:
@@ -302,12 +296,70 @@ class MPC(Module):
             n_batch = cost.C.size(1)
         else:
             raise ValueError("MPC Error: Could not infer batch size, pass in as n_batch")
-        given_cost, given_dx = cost, dx           # as the caller gave them: what `shared_grad_kernel` hands to the final step
         if isinstance(cost, QuadCost):
             cost = self._expand_cost(cost, n_batch)
         if isinstance(dx, LinDx) and torch.is_tensor(dx.F) and dx.F.ndimension() < 4:
             dx = self._expand_dx(dx, n_batch)
         assert x_init.ndimension() == 2 and x_init.size(0) == n_batch
+        return n_batch, cost, dx
+
+    def solve_route(self, x_init, cost, dx):
+        """The `SolveRoute` that `forward(x_init, cost, dx)` would take; nothing runs.  The rules, the first that holds:
+        general   a module cost, or `reference_du_norm` with a batch: every pre-bound loop below needs a QuadCost and each
+                  problem's own du norm.  `_iterate_general`: linearisation and cost expansion through torch, an LQRStep a turn.
+        slew      a `slew_rate_penalty`, T > 1 and dynamics `_slew_plan` names: "lin" for a LinDx; the augmented EnvSpec of a
+                  shipped simulator with one control under ANALYTIC / AUTO_DIFF (FINITE_DIFF keeps the reference's central
+                  differences) on a backend whose lane-per-problem kernel carries the control; with `planned_network_slew` the
+                  augmented MlpSpec of a network as under `network`, n_state + n_ctrl <= 32, whose rollout kernels take the
+                  augmented widths.  The loop of `planned` / `network` on the augmented problem, built once (round 11).
+                  Any other penalty: general.
+        planned   a LinDx (any T); or T > 1 and a shipped simulator (`native_env`) under ANALYTIC / AUTO_DIFF: closed-form
+                  linearisation and the simulator inside the step kernel.
+        network   T > 1, ANALYTIC, a backend with `plan_network_iteration` and an NNDynamics the kernels take (`native_net`: fp32
+                  on the device, <= 4 layers, n_state <= 32) that is not elu (no grad_input in the reference: the module refuses,
+                  mpc/dynamics.py:113-114): the whole iteration is three pre-bound C calls (round 5).
+        general   everything else.
+        `shared_ending`: `shared_grad_kernel` on a pre-bound loop without a penalty.  Which kernel such a loop forces
+        (`narrow_step_kernel`, `row_carry_kernel`) is `_forced_impl`'s answer, at the sizes the loop runs at."""
+        _, cost, dx = self._expand_args(x_init, cost, dx)
+        return self._route(x_init, cost, dx, _native.backend())
+
+    def _route(self, x_init, cost, dx, be):
+        """`solve_route` on expanded arguments: the one place that chooses the loop.  Launches nothing."""
+        ref_norm, penalty = self._ref_norm(x_init), self.slew_rate_penalty is not None
+        prebound = isinstance(cost, QuadCost) and not ref_norm           # what every pre-bound loop needs
+        loop, dynamics = "general", None
+        if not prebound:
+            pass
+        elif penalty:
+            loop, dynamics = "slew", self._slew_plan(cost, dx, be, x_init)
+        elif isinstance(dx, LinDx):
+            loop, dynamics = "planned", "lin"
+        elif self.T > 1 and self._closed_form_env(dx):
+            loop, dynamics = "planned", dx.native_env()
+        elif self.T > 1:
+            loop, dynamics = "network", self._kernel_net(dx, be, x_init)
+        if dynamics is None:                                             # (`_slew_plan` / `_kernel_net` declined)
+            loop = "general"
+        return SolveRoute(loop, dynamics, ref_norm, self.shared_grad_kernel and prebound and not penalty)
+
+    def _ref_norm(self, x_init):
+        return self.reference_du_norm and x_init.size(0) > 1
+
+    def _closed_form_env(self, dx):
+        """A shipped simulator (mpc.env_dx) under a grad method for which the kernels' closed-form linearisation stands in?"""
+        return hasattr(dx, "native_env") and self.grad_method in (GradMethods.ANALYTIC, GradMethods.AUTO_DIFF)
+
+    def _kernel_net(self, dx, be, x_init):
+        """The MlpSpec of an NNDynamics the pre-bound network iterations run (see `solve_route`: network), else None."""
+        if self.grad_method != GradMethods.ANALYTIC or not hasattr(dx, "native_net") or not hasattr(be, "plan_network_iteration"):
+            return None
+        net = dx.native_net(x_init)
+        return None if net is None or net.activation == "elu" else net
+
+    def forward(self, x_init, cost, dx):
+        given_cost, given_dx = cost, dx           # as the caller gave them: what `shared_grad_kernel` hands to the final step
+        n_batch, cost, dx = self._expand_args(x_init, cost, dx)
 
         T, ns, nc = self.T, self.n_state, self.n_ctrl
         if self.u_init is None:
@@ -322,37 +374,14 @@ class MPC(Module):
             print("Initial mean(cost): {:.4e}".format(
                 util.get_cost(T, u, cost, dx, x_init=x_init).mean().item()))
 
-        ref_norm = self.reference_du_norm and n_batch > 1
-        fast = (isinstance(cost, QuadCost) and isinstance(dx, LinDx) and self.slew_rate_penalty is None and not ref_norm)
-        # a shipped simulator (mpc.env_dx): closed-form linearisation kernel + the simulator inside the
-        # rollout kernel; FINITE_DIFF keeps the reference's central differences
-        sim = None
-        if (isinstance(cost, QuadCost) and hasattr(dx, "native_env") and self.slew_rate_penalty is None
-                and self.grad_method in (GradMethods.ANALYTIC, GradMethods.AUTO_DIFF) and T > 1 and not ref_norm):
-            sim = dx.native_env()
         be = _native.backend()
-        # NNDynamics the kernels take (fp32 on the device, <= 4 layers, n_state <= 32), ANALYTIC linearisation: the whole
-        # iteration is three pre-bound C calls (round 5; the general loop below pays allocations, struct rebuilds, an autograd
-        # node and a device synchronisation per iteration: 1.1 ms an iteration for 0.52 ms of kernels at the headline shape)
-        net = None
-        if (sim is None and not fast and isinstance(cost, QuadCost) and self.slew_rate_penalty is None and T > 1
-                and self.grad_method == GradMethods.ANALYTIC and hasattr(dx, "native_net")
-                and hasattr(be, "plan_network_iteration") and not ref_norm):
-            net = dx.native_net(x_init)
-            if net is not None and net.activation == "elu":      # (no grad_input in the reference: the module refuses, mpc/dynamics.py:113-114)
-                net = None
-        # a slew-rate penalty on a QuadCost with LinDx or a shipped simulator (or, with `planned_network_slew`, an NNDynamics):
-        # the same device-side loop on the augmented problem, which does not depend on the iterate and is built once (round 11;
-        # _iterate_general rebuilt it per iteration)
-        slew = self._slew_plan(cost, dx, be, x_init)
-        if fast or sim is not None:
-            best = self._iterate_planned(be, x_init, u, cost, dx, sim, n_batch)
-        elif slew is not None:
-            best = self._iterate_slew(be, x_init, u, cost, dx, slew, n_batch)
-        elif net is not None:
-            best = self._iterate_network(be, x_init, u, cost, dx, net, n_batch)
-        else:
+        route = self._route(x_init, cost, dx, be)
+        if route.loop == "general":
             best = self._iterate_general(be, x_init, u, cost, dx)
+        else:
+            iterate = (self._iterate_planned if route.loop == "planned" else
+                       self._iterate_slew if route.loop == "slew" else self._iterate_network)
+            best = iterate(be, x_init, u, cost, dx, route.dynamics, n_batch)
 
         x, u = best["x"], best["u"]
         full_du_norm = best["full_du_norm"]
@@ -363,12 +392,12 @@ class MPC(Module):
             return (x, u, best["costs"])
         # batch-shared arguments stay un-expanded for the final step (its Function expands them itself and returns their
         # gradients summed over the batch); everything that keeps the per-problem route gets the views as before
-        shared = (self.shared_grad_kernel and isinstance(cost, QuadCost) and self.slew_rate_penalty is None and not ref_norm)
+        shared = route.shared_ending
         if isinstance(dx, LinDx):
             F, f = (given_dx.F, given_dx.f) if shared else (dx.F, dx.f)
-        elif sim is not None and not _any_requires_grad(dx):
-            # the simulator's parameters are constants here: closed-form kernel instead of autograd
-            Fl, fl = be.env_linearize(sim, x[:-1].reshape(-1, ns), u[:-1].reshape(-1, nc))
+        elif route.loop == "planned" and not _any_requires_grad(dx):
+            # a simulator whose parameters are constants here: closed-form kernel instead of autograd
+            Fl, fl = be.env_linearize(route.dynamics, x[:-1].reshape(-1, ns), u[:-1].reshape(-1, nc))
             F, f = Fl.view(T - 1, n_batch, ns, ns + nc), fl.view(T - 1, n_batch, ns)
         else:
             F, f = self.linearize_dynamics(x, u, dx, diff=True)
@@ -386,21 +415,17 @@ class MPC(Module):
             u = u * keep + u.detach() * (1. - keep)
         return (x, u, best["costs"])
 
-    def _iterate_planned(self, be, x_init, u, cost, dx, sim, n_batch):
-        """The iLQR loop (mpc/mpc.py:245-306) when the whole iteration lives on the device: QuadCost with
-        LinDx or a shipped simulator.  Inner iterations are never differentiated (the reference detaches
+    def _iterate_planned(self, be, x_init, u, cost, dx, dynamics, n_batch):
+        """The iLQR loop (mpc/mpc.py:245-306) when the whole iteration lives on the device: QuadCost with a LinDx
+        (`dynamics` "lin") or a shipped simulator (its EnvSpec).  Inner iterations are never differentiated (the reference detaches
         them too).  Two pre-bound step plans ping-pong the nominal between two buffers, so an iteration is
         one C call (a simulator is linearised inside that call) -- no allocation, no autograd node.
         The states of a rollout ARE get_traj of its controls (:251 recomputes them).
         The convergence flags of iteration i are read back while iteration i+1 already runs: the next
         step is launched speculatively and simply not used if the flags say stop."""
-        T, ns, nc = self.T, self.n_state, self.n_ctrl
+        T, sim = self.T, None if dynamics == "lin" else dynamics
         xi = util.detach_maybe(x_init)
-        # the ping-pong plans WRITE into `ua`: it must be this solve's own buffer, never the caller's u_init
-        # (detach / to / contiguous all return the same storage for a contiguous tensor)
-        ua = util.detach_maybe(u).contiguous()
-        if self.u_init is not None and ua.untyped_storage().data_ptr() == self.u_init.untyped_storage().data_ptr():
-            ua = ua.clone()
+        ua = self._own_nominal(u)
         opts = self._step_options()
         if sim is not None:
             xa, _ = be.env_traj_cost(xi, ua, sim)                         # util.get_traj, :251
@@ -414,13 +439,8 @@ class MPC(Module):
             # every nominal of this loop obeys (F, f) by construction: get_traj above, then each step's own rollout
             opts.nominal_on_dynamics = True
         xb, ub = torch.empty_like(xa), torch.empty_like(ua)
-        # (`narrow_step_kernel`: the forced kernel rides in the plan; its variants below keep it)
-        kwi = self._narrow_impl_kw(be, xi.shape[1], ua.shape[2], xi.dtype, opts)
-        # (`row_carry_kernel`: likewise, for a simulator behind the carry.  That kernel keeps Q and V general like the lane-per-problem
-        # one and sets no MPC_ST_C_ASYMMETRIC, so there is nothing to start over from: no `on_asymmetric`)
-        kwr = self._row_carry_impl_kw(be, xi, ua, sim, opts) if not kwi else {}
-        restart = bool(kwi)
-        kwi = kwi or kwr
+        # (a forced kernel rides in the plan; its variants below keep it)
+        kwi, restart = self._forced_impl(be, xi, ua, sim, opts)
         variant = getattr(be, "plan_variant", None)      # (the test backends build every plan from scratch)
         # the raw stream handle, looked up once (torch.cuda.current_stream costs 4 us a call, two calls an iteration)
         stream = torch.cuda.current_stream(xa.device).cuda_stream if xa.is_cuda and variant is not None else None
@@ -460,62 +480,57 @@ class MPC(Module):
                 else:
                     sym_plans = (be.plan_step(xi, cost.C, cost.c, F, f, xa, ua, so, out_x=xb, out_u=ub, **kwi),
                                  be.plan_step(xi, cost.C, cost.c, F, f, xb, ub, so, out_x=xa, out_u=ua, **kwi))
-        # A FORCED kernel reads C through its symmetry and only flags a problem whose C is not symmetric; it is impl 0 that solves
-        # such a problem again on the generic kernel inside the call (include/mpc_lqr.h, MPC_ST_C_ASYMMETRIC).  So a loop bound to
-        # the narrow kernel whose first step reports the bit starts over on IMPL_AUTO plans: the nominal of iteration 0 is still
-        # in (xa, ua) -- `_drive` holds iteration 1 back until the flags are in -- and the solve is the flag-off solve from there on
+        # `restart` (see `narrow_step_kernel` in __init__): a loop whose first step reports MPC_ST_C_ASYMMETRIC starts over on IMPL_AUTO
+        # plans; the nominal of iteration 0 is still in (xa, ua) -- `_drive` holds iteration 1 back until the flags are in
         return self._drive(be, launch, outputs, r, xa, ua, n_batch, stream, on_symmetric,
                            on_asymmetric=(lambda: bind({})) if restart else None)
 
-    def _narrow_impl_kw(self, be, ns, nc, dtype, opts):
-        """`narrow_step_kernel`: dict(impl=IMPL_MFMA40_NARROW) where the backend's narrow kernel takes a step of these sizes and
-        options, else {} -- the plan is bound as ever, with IMPL_AUTO."""
-        if (self.narrow_step_kernel and hasattr(be, "impl_supported")
-                and be.impl_supported(int(ns), int(nc), dtype, _native.IMPL_MFMA40_NARROW, opts)
-                # (up to 12/4 the 4-problems-per-wave kernels are auto's choice and stay it: the narrow kernel is for the shapes
-                # auto gives to the padded 32/8 kernel)
-                and not be.impl_supported(int(ns), int(nc), dtype, _native.IMPL_DPP16_PAD, opts)):
-            return dict(impl=_native.IMPL_MFMA40_NARROW)
-        return {}
+    def _own_nominal(self, u):
+        """The nominal controls of a pre-bound loop, whose iterations WRITE into them: this solve's own buffer, never the caller's
+        u_init (detach / to / contiguous all return the same storage for a contiguous tensor)."""
+        ua = util.detach_maybe(u).contiguous()
+        if self.u_init is not None and ua.untyped_storage().data_ptr() == self.u_init.untyped_storage().data_ptr():
+            ua = ua.clone()
+        return ua
 
-    def _row_carry_impl_kw(self, be, xi, ua, sim, opts):
-        """`row_carry_kernel`: dict(impl=IMPL_WAVE1_CARRY) for a simulator behind ENV_CTRL_CARRY where the backend's row-per-problem
-        carry kernel takes the step (`impl_supported`) and pays at this horizon and batch (`row_carry_pays`), else {} -- the plan is
-        bound as ever, with IMPL_AUTO.  Flag off, neither predicate is asked."""
-        if not (self.row_carry_kernel and sim is not None and getattr(sim, "carry", False) and xi.dtype == torch.float32
-                and hasattr(be, "impl_supported") and hasattr(be, "row_carry_pays")):
-            return {}
+    def _forced_impl(self, be, xi, ua, sim, opts):
+        """The kernel forced on the plans of a pre-bound loop, at the sizes it runs at -> (dict(impl=...) or {} = IMPL_AUTO as ever,
+        does the loop start over on an asymmetric C).  Flag off, its predicates are not asked.  `narrow_step_kernel` first:
+        IMPL_MFMA40_NARROW where the backend takes the step for it and NOT for IMPL_DPP16_PAD (up to 12/4 the 4-problems-per-wave
+        kernels are auto's choice and stay it).  Where that declined, `row_carry_kernel`: IMPL_WAVE1_CARRY for a float32 simulator
+        behind ENV_CTRL_CARRY where the row-per-problem carry kernel takes the step and pays at this horizon and batch; it keeps Q
+        and V general like the lane-per-problem one and sets no MPC_ST_C_ASYMMETRIC: nothing to start over from."""
+        if not (self.narrow_step_kernel or self.row_carry_kernel):
+            return {}, False
+        asks = hasattr(be, "impl_supported")
         ns, nc, T, B = int(xi.shape[1]), int(ua.shape[2]), int(ua.shape[0]), int(ua.shape[1])
-        if (be.impl_supported(ns, nc, xi.dtype, _native.IMPL_WAVE1_CARRY, opts)
+        if (self.narrow_step_kernel and asks and be.impl_supported(ns, nc, xi.dtype, _native.IMPL_MFMA40_NARROW, opts)
+                and not be.impl_supported(ns, nc, xi.dtype, _native.IMPL_DPP16_PAD, opts)):
+            return dict(impl=_native.IMPL_MFMA40_NARROW), True
+        if (self.row_carry_kernel and sim is not None and getattr(sim, "carry", False) and xi.dtype == torch.float32
+                and asks and hasattr(be, "row_carry_pays") and be.impl_supported(ns, nc, xi.dtype, _native.IMPL_WAVE1_CARRY, opts)
                 and be.row_carry_pays(ns, nc, xi.dtype, T, B, opts, like=xi)):
-            return dict(impl=_native.IMPL_WAVE1_CARRY)
-        return {}
+            return dict(impl=_native.IMPL_WAVE1_CARRY), False
+        return {}, False
 
     def _slew_plan(self, cost, dx, be, x_init):
         """Does this slew-rate solve run on the device-side loop (`_iterate_slew`)?  None = no: `_iterate_general`, as before
         round 11.  Else what the dynamics are there: "lin" (LinDx), the simulator's EnvSpec behind MPC_ENV_CTRL_CARRY, or the
-        augmented MlpSpec of an NNDynamics (`ctrl_carry`).
-        All of: a QuadCost, a penalty, T > 1, each problem's own du norm (not `reference_du_norm` with B > 1), and either LinDx
-        or a shipped simulator under ANALYTIC / AUTO_DIFF on a backend whose lane-per-problem kernel carries the control
-        (`impl_supported`; FINITE_DIFF keeps the reference's central differences, module costs are not augmented by the
-        reference either) or -- `planned_network_slew` only -- an NNDynamics the kernels take (`native_net`, not elu) under
-        ANALYTIC with n_state + n_ctrl <= 32 on a backend with `plan_network_iteration`, whose rollout kernels take the
-        augmented widths (`MlpSpec.augmented()` does not ask the LDS budget again: mpc_mlp_supported's rollout bit does here)."""
-        if (not isinstance(cost, QuadCost) or self.slew_rate_penalty is None or self.T <= 1
-                or (self.reference_du_norm and x_init.size(0) > 1)):
+        augmented MlpSpec of an NNDynamics (`ctrl_carry`).  The rules: `solve_route`.  (Module costs are not augmented by the
+        reference either; `MlpSpec.augmented()` does not ask the LDS budget again: mpc_mlp_supported's rollout bit does here.)"""
+        if not isinstance(cost, QuadCost) or self._ref_norm(x_init) or self.slew_rate_penalty is None or self.T <= 1:
             return None
         if isinstance(dx, LinDx):
             return "lin"
-        if (hasattr(dx, "native_env") and self.n_ctrl == 1 and self.grad_method in (GradMethods.ANALYTIC, GradMethods.AUTO_DIFF)
-                and hasattr(be, "impl_supported") and x_init.dtype in (torch.float32, torch.float64)):
+        if (self._closed_form_env(dx) and self.n_ctrl == 1 and hasattr(be, "impl_supported")
+                and x_init.dtype in (torch.float32, torch.float64)):
             env = dx.native_env().augmented()
             if env.n_state == self.n_state + 1 and be.impl_supported(
                     env.n_state, 1, x_init.dtype, _native.IMPL_TINY, StepOptions(true_dynamics=env)):
                 return env
-        if (self.planned_network_slew and self.grad_method == GradMethods.ANALYTIC and hasattr(dx, "native_net")
-                and hasattr(be, "plan_network_iteration") and self.n_state + self.n_ctrl <= 32):
-            net = dx.native_net(x_init)
-            if net is not None and net.activation != "elu" and net.n_state == self.n_state and net.n_ctrl == self.n_ctrl:
+        if self.planned_network_slew and self.n_state + self.n_ctrl <= 32:
+            net = self._kernel_net(dx, be, x_init)
+            if net is not None and net.n_state == self.n_state and net.n_ctrl == self.n_ctrl:
                 aug = net.augmented()
                 # (bit 0 only: the augmented network is rolled out, never linearised -- that is `net` itself, which native_net vouched for)
                 if _native.MlpSpec.supported(aug.weights, aug.activation, x_init, bits=1):
@@ -528,27 +543,24 @@ class MPC(Module):
         (mpc_slew_augment where the backend has it, else the torch composition); the augmented rollout of a step IS the next
         augmented nominal, so nothing is re-packed between iterations.  A simulator is carried through the kernels by
         MPC_ENV_CTRL_CARRY (its F, f never exist); an NNDynamics (`plan` = its augmented MlpSpec) runs `_iterate_network` on the
-        augmented problem, whose linearisation kernel writes (aF, af) at every nominal.  `costs` include the penalty, as the reference's (its line search prices the
-        augmented QuadCost); the first n_ctrl state columns are stripped from the best iterate."""
+        augmented problem, whose linearisation kernel writes (aF, af) at every nominal.  `costs` include the penalty, as the
+        reference's (its line search prices the augmented QuadCost); the first n_ctrl state columns are stripped from the best iterate."""
         nc = self.n_ctrl
         C, c = util.detach_maybe(cost.C), util.detach_maybe(cost.c)
         lin = isinstance(dx, LinDx)
-        network = isinstance(plan, _native.MlpSpec)
-        F = util.detach_maybe(dx.F) if lin else None
-        f = util.detach_maybe(dx.f) if lin else None
+        F, f = (util.detach_maybe(dx.F), util.detach_maybe(dx.f)) if lin else (None, None)
         if hasattr(be, "slew_augment") and C.is_cuda:
             aC, ac, aF, af = be.slew_augment(C, c, F, f, self.n_state, nc, self.slew_rate_penalty)
         else:
             _, aC, ac, aF, af = self._slew_compose(C, c, F, f)
         prev_u = self._slew_prev_u(n_batch, dict(dtype=C.dtype, device=C.device))
         ax_init = torch.cat((prev_u[0], util.detach_maybe(x_init)), 1)
-        if network:
+        if isinstance(plan, _native.MlpSpec):
             from .dynamics import CtrlPassthroughDynamics
             # (the module serves the first get_traj only; every later nominal is a rollout of the kernels)
             best = self._iterate_network(be, ax_init, u, QuadCost(aC, ac), CtrlPassthroughDynamics(dx), plan, n_batch)
         else:
-            best = self._iterate_planned(be, ax_init, u, QuadCost(aC, ac), LinDx(aF, af) if lin else None,
-                                         None if lin else plan, n_batch)
+            best = self._iterate_planned(be, ax_init, u, QuadCost(aC, ac), LinDx(aF, af) if lin else None, plan, n_batch)
         best["x"] = best["x"][:, :, nc:].contiguous()
         return best
 
@@ -620,9 +632,7 @@ class MPC(Module):
         Inner iterations are never differentiated (the reference detaches them too)."""
         T = self.T
         xi = util.detach_maybe(x_init).contiguous()
-        ua = util.detach_maybe(u).contiguous()
-        if self.u_init is not None and ua.untyped_storage().data_ptr() == self.u_init.untyped_storage().data_ptr():
-            ua = ua.clone()               # the iterations WRITE into the nominal buffers: never the caller's u_init
+        ua = self._own_nominal(u)
         if hasattr(be, "mlp_traj_cost"):
             # util.get_traj's own call for such a module, with the spec already in hand (`dx.native_net` would build it again --
             # for the slew-rate augmentation a second set of concatenated weights)
@@ -631,7 +641,7 @@ class MPC(Module):
             xa = util.get_traj(T, ua, x_init=xi, dynamics=dx).contiguous()
         xb, ub = torch.empty_like(xa), torch.empty_like(ua)
         nopts = self._step_options()
-        kwi = self._narrow_impl_kw(be, xi.shape[1], ua.shape[2], xi.dtype, nopts)
+        kwi, restart = self._forced_impl(be, xi, ua, None, nopts)
         stream = torch.cuda.current_stream(xa.device).cuda_stream if xa.is_cuda else None
         bound = [None, None]
 
@@ -647,7 +657,7 @@ class MPC(Module):
         # (a sweep forced onto the narrow kernel that reports a non-symmetric C: the loop starts over on IMPL_AUTO, see
         # `_iterate_planned`)
         return self._drive(be, lambda i: bound[0](i % 2, stream), outs, r, xa, ua, n_batch, stream, on_symmetric,
-                           on_asymmetric=(lambda: bind({})) if kwi else None)
+                           on_asymmetric=(lambda: bind({})) if restart else None)
 
     def _iterate_general(self, be, x_init, u, cost, dx):
         """The same loop with module-valued cost / dynamics or a slew penalty: linearisation and cost
@@ -732,17 +742,19 @@ class MPC(Module):
         """Build the LQRStep for the current nominal (x,u) and apply it (mpc/mpc.py:339-361)."""
         if self.slew_rate_penalty is not None and not isinstance(cost, Module):
             return self._solve_slew_subproblem(x_init, C, c, F, f, cost, dynamics, x, u, no_op_forward)
-        step = LQRStep(
-            n_state=self.n_state, n_ctrl=self.n_ctrl, T=self.T,
-            u_lower=self.u_lower, u_upper=self.u_upper, u_zero_I=self.u_zero_I,
-            true_cost=cost, true_dynamics=dynamics, delta_u=self.delta_u,
+        step = self._lqr_step(self.n_state, cost, dynamics, x, u, no_op_forward, dict(
+            c_symmetric=no_op_forward and getattr(self, "_c_symmetric", False), shared_grad_kernel=shared_grad_kernel,
+            **(dict(narrow_kkt_kernel=True) if self.narrow_kkt_kernel else {})))
+        return step(x_init, C, c, F, f if f is not None else x_init.new_empty(0))
+
+    def _lqr_step(self, n_state, true_cost, true_dynamics, current_x, current_u, no_op_forward, extra):
+        """The LQRStep of this controller's options on `n_state` states; `extra`: the keywords only one caller passes."""
+        return LQRStep(
+            n_state=n_state, n_ctrl=self.n_ctrl, T=self.T, u_lower=self.u_lower, u_upper=self.u_upper, u_zero_I=self.u_zero_I,
+            true_cost=true_cost, true_dynamics=true_dynamics, delta_u=self.delta_u,
             linesearch_decay=self.linesearch_decay, max_linesearch_iter=self.max_linesearch_iter,
-            delta_space=True, current_x=x, current_u=u, back_eps=self.back_eps,
-            no_op_forward=no_op_forward, c_symmetric=no_op_forward and getattr(self, "_c_symmetric", False),
-            reference_du_norm=self.reference_du_norm and not no_op_forward, shared_grad_kernel=shared_grad_kernel,
-            **(dict(narrow_kkt_kernel=True) if self.narrow_kkt_kernel else {}))
-        empty = torch.empty(0, dtype=x_init.dtype, device=x_init.device)
-        return step(x_init, C, c, F, f if f is not None else empty)
+            delta_space=True, current_x=current_x, current_u=current_u, back_eps=self.back_eps, no_op_forward=no_op_forward,
+            reference_du_norm=self.reference_du_norm and not no_op_forward, **extra)
 
     def _solve_slew_subproblem(self, x_init, C, c, F, f, cost, dynamics, x, u, no_op_forward):
         """slew_rate_penalty: the same LQR step on the state augmented with the previous control,
@@ -750,27 +762,17 @@ class MPC(Module):
         (reference mpc/mpc.py:362-445).  Pure re-packing around the kernel; autograd reaches C, c, F, f
         through the padding ops."""
         from .dynamics import CtrlPassthroughDynamics
-        T, ns, nc = self.T, self.n_state, self.n_ctrl
-        B = C.size(1)
-        n = ns + nc
-        kw = dict(dtype=C.dtype, device=C.device)
+        ns, nc = self.n_state, self.n_ctrl
         slew_C, aC, ac, aF, af = self._slew_compose(C, c, F, f)
-        prev_u = self._slew_prev_u(B, kw)
+        prev_u = self._slew_prev_u(C.size(1), dict(dtype=C.dtype, device=C.device))
         ax = torch.cat((torch.cat((prev_u, util.detach_maybe(u)[:-1])), x), 2)
         ax_init = torch.cat((prev_u[0], x_init), 1)
         a_dyn = None if isinstance(dynamics, LinDx) else CtrlPassthroughDynamics(dynamics)
         a_cost = QuadCost(aC, ac) if isinstance(cost, QuadCost) else SlewRateCost(cost, slew_C, ns, nc)
-        step = LQRStep(
-            n_state=n, n_ctrl=nc, T=T, u_lower=self.u_lower, u_upper=self.u_upper, u_zero_I=self.u_zero_I,
-            true_cost=a_cost, true_dynamics=a_dyn, delta_u=self.delta_u,
-            linesearch_decay=self.linesearch_decay, max_linesearch_iter=self.max_linesearch_iter,
-            delta_space=True, current_x=ax, current_u=u, back_eps=self.back_eps, no_op_forward=no_op_forward,
-            reference_du_norm=self.reference_du_norm and not no_op_forward,
-            # (`narrow_kkt_kernel` only: the promise of the plain ending, see __init__)
-            **(dict(narrow_kkt_kernel=True, c_symmetric=no_op_forward and getattr(self, "_c_symmetric", False))
-               if self.narrow_kkt_kernel else {}))
-        empty = torch.empty(0, **kw)
-        out = step(ax_init, aC, ac, aF, af if af is not None else empty)
+        # (`narrow_kkt_kernel` only: the promise of the plain ending, see __init__)
+        step = self._lqr_step(ns + nc, a_cost, a_dyn, ax, u, no_op_forward, dict(
+            narrow_kkt_kernel=True, c_symmetric=no_op_forward and getattr(self, "_c_symmetric", False)) if self.narrow_kkt_kernel else {})
+        out = step(ax_init, aC, ac, aF, af if af is not None else aC.new_empty(0))
         return (out[0][:, :, nc:],) + tuple(out[1:])
 
     def _slew_compose(self, C, c, F, f):
@@ -858,11 +860,8 @@ class MPC(Module):
         if len(params) != 2 * len(net.weights) or any(a is not b for a, b in zip(params[0::2], net.weights)) \
                 or any(a is not b for a, b in zip(params[1::2], net.biases)):
             return None
-        for m in dynamics.modules():
-            for v in list(m.parameters(recurse=False)) + list(vars(m).values()):
-                for t in (v if isinstance(v, (list, tuple)) else (v,)):
-                    if torch.is_tensor(t) and t.requires_grad and not any(t is p for p in params):
-                        return None
+        if any(not any(t is p for p in params) for t in _grad_tensors(dynamics)):
+            return None
         return net, params
 
     def linearize_dynamics(self, x, u, dynamics, diff):

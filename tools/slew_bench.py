@@ -110,20 +110,18 @@ def main():
     ap.add_argument("--rounds-off", type=int, default=3, help="repeats of the route-off solve of the simulator rows (seconds each)")
     a = ap.parse_args()
     assert torch.cuda.is_available(), "this benchmark needs the MI355X"
-    from mpc import _native
     dev = "cuda:0"
     res = {"device": torch.cuda.get_device_name(0), "rows": {}}
     for row in a.rows.split(","):
         if row.startswith("nn"):
             make, args, meta = nn_row(row, dev)
             on, off = make(True), make(False)          # (the route is opt-in: off is the constructor's default)
-            assert off._slew_plan(off._expand_cost(args[1], meta["B"]), args[2], _native.backend(), args[0]) is None
         else:
             make, args, meta = (lin_row(row == "lin_box", dev) if row.startswith("lin") else sim_row(row, dev))
             on, off = make(), make()
             off._slew_plan = lambda *x, **k: None
-        assert on._slew_plan(on._expand_cost(args[1], meta["B"]), args[2], _native.backend(), args[0]) is not None, \
-            "the predicate must fire on the new route"
+        assert off.solve_route(*args).loop == "general"
+        assert on.solve_route(*args).loop == "slew", "the predicate must fire on the new route"
         _, o_on = solve_ms(on, args)           # warm-up of either route at this shape
         _, o_off = solve_ms(off, args)
         rounds_off = a.rounds if row.startswith(("lin", "nn")) else a.rounds_off
