@@ -288,7 +288,9 @@ int mpc_lqr_rollout(const mpc_lqr_problem *p, const mpc_lqr_options *o, const mp
 /* (4) The closed-form part of LQRStepFn.backward, mpc/lqr_step.py:346-404: given the
  *     solution (x*,u*) and the KKT solve's (dx,du) [= mpc_lqr_step on (C,-r,F), :328-340],
  *     emit dC [T,B,n,n], dc [T,B,n], dF [T-1,B,ns,n], df [T-1,B,ns] (NULL if f empty),
- *     dx_init [B,ns].  r = [dl_dx; dl_du] is passed as its two halves. */
+ *     dx_init [B,ns].  r = [dl_dx; dl_du] is passed as its two halves.
+ *     float32 with n_state + n_ctrl <= 64 runs on wavefront kernels; float64 always runs on the generic kernel here -- its wavefront
+ *     kernels (n_state + n_ctrl <= 64) are asked for by name: mpc_lqr_kkt_grads_kernel below. */
 int mpc_lqr_kkt_grads(const mpc_lqr_problem *p, /* C,c,F (+strides); cur_x/cur_u = x*,u* */
                       const void *dx, const void *du, const void *dl_dx, const void *dl_du,
                       void *dC, void *dc, void *dF, void *df, void *dx_init, void *stream);
@@ -300,6 +302,26 @@ int mpc_lqr_kkt_grads(const mpc_lqr_problem *p, /* C,c,F (+strides); cur_x/cur_u
 enum { MPC_KKT_GRADS_DPP16 = 1, MPC_KKT_GRADS_WAVE = 2, MPC_KKT_GRADS_GENERIC = 3 };
 int mpc_lqr_kkt_grads_route(const mpc_lqr_problem *p, const void *dx, const void *du, const void *dl_dx, const void *dl_du,
                             const void *dC, const void *dc, const void *dF, const void *df, const void *dx_init);
+
+/* (ABI 9, additive) (4) with the kernel named by the caller.  kernel = 0: the two entries above, unchanged in code, text and result.
+ * kernel = MPC_KKT_GRADS_WAVE64: the wavefront-per-problem kernels in float64 -- the costate recursion on one wavefront a problem
+ * (row i of C as given, [C_t | F_t | x*, u*, dx, du, c, dl_dx] by LDS-DMA ahead of the recursion), then the outer products on one
+ * wavefront per (t, b) -- for 2 <= n_state + n_ctrl <= 64.  The shared argument checks of (4) come first, in its order and with its
+ * texts; then the kernel's own refusals as MPC_E_DIMS, the text naming the kernel and the first thing it misses: float64, its sizes,
+ * every pointer on 8 bytes (the entry carries no options, so its model is always the linear one: F).  Nothing is launched on a
+ * refusal, nothing else is tried.  Views on the 16-byte grid (n_state and n_ctrl even, C, F, c, x*, u*, dx, du, dl_dx, dC, dF on
+ * 16 bytes, even strides) move 16 bytes a lane, everything else 4; both give the same bits.  B = 0 succeeds and launches nothing; at
+ * T = 1, F and dF may be NULL; p's T and B strides of C, c, F are honoured, 0 = broadcast.  Any other code: MPC_E_ARG.  The code
+ * is never chosen by kernel = 0, whose float64 calls stay on the generic kernel.
+ * _supported: 1 where the named kernel has these sizes and this dtype, else 0 (sizes and dtype only; 0 for every other code).
+ * _route: the code that would launch, 0 for B = 0, or the call's negative code with the same text; no pointer is dereferenced, no
+ * device is needed to ask. */
+#define MPC_KKT_GRADS_WAVE64 4   /* forced only: float64, 2 <= n_state + n_ctrl <= 64 */
+int mpc_lqr_kkt_grads_kernel_supported(const mpc_lqr_problem *p, int kernel);
+int mpc_lqr_kkt_grads_kernel(const mpc_lqr_problem *p, int kernel, const void *dx, const void *du, const void *dl_dx, const void *dl_du,
+                             void *dC, void *dc, void *dF, void *df, void *dx_init, void *stream);
+int mpc_lqr_kkt_grads_kernel_route(const mpc_lqr_problem *p, int kernel, const void *dx, const void *du, const void *dl_dx,
+                                   const void *dl_du, const void *dC, const void *dc, const void *dF, const void *df, const void *dx_init);
 
 /* (4b) r -> -r packing and the active-bound mask of mpc/lqr_step.py:316-326:
  *     negr [T,B,n] = -[dl_dx; dl_du];  mask [T,B,nc] = |u*-lo|<=1e-8 | |u*-hi|<=1e-8

@@ -852,7 +852,7 @@ int mpc_lqr_abi_version(void) { return MPC_LQR_ABI_VERSION; }
 const char *mpc_lqr_build_info(void)
 {
     return "libmpc_lqr_hip gfx950 (CDNA4) | kernels: lqr_step_generic<f32,f64>, lqr_step_mfma16<f32,f64>, lqr_step_dpp16<f32>, lqr_step_dpp16_padded<f32>, "
-           "lqr_step_tiny<f32,f64>, lqr_step_wave1<f32>, lqr_step_wave1_carry<f32>, lqr_step_mfma40<f32>, lqr_step_mfma40_padded<f32>, lqr_step_mfma40_narrow<f32>, nn_rollout<f32>, nn_linearize<f32>, nn_param_grad<f32>, env_linearize, env_param_grad<f32,f64>, kkt_grads, kkt_grads_shared<f32>, kkt_fused<f32>, kkt_fused_padded<f32>, kkt_fused_narrow<f32>, pnqp, traj_cost, select_best, slew_augment<f32,f64> | built " __DATE__ " " __TIME__;
+           "lqr_step_tiny<f32,f64>, lqr_step_wave1<f32>, lqr_step_wave1_carry<f32>, lqr_step_mfma40<f32>, lqr_step_mfma40_padded<f32>, lqr_step_mfma40_narrow<f32>, nn_rollout<f32>, nn_linearize<f32>, nn_param_grad<f32>, env_linearize, env_param_grad<f32,f64>, kkt_grads, kkt_grads_shared<f32>, kkt_fused<f32>, kkt_fused_padded<f32>, kkt_fused_narrow<f32>, pnqp, traj_cost, select_best, slew_augment<f32,f64>, kkt_grads_wave<f64> | built " __DATE__ " " __TIME__;
 }
 
 const char *mpc_lqr_last_error(void) { return g_last_error.c_str(); }
@@ -970,6 +970,43 @@ int mpc_lqr_kkt_grads_route(const mpc_lqr_problem *p, const void *dx, const void
     if (p->dtype != MPC_F32) return MPC_KKT_GRADS_GENERIC;
     return kkt_grads_route(make_params<float>(p, nullptr, nullptr), (const float *)dx, (const float *)du, (const float *)dl_dx,
                            (const float *)dC, (const float *)dF);
+}
+
+// (4) with the kernel named by the caller.  MPC_KKT_GRADS_WAVE64 is the one code there is: the float64 wavefront kernels
+// (kkt_wave64.hip), which kernel = 0 never picks -- float64 stays on the generic kernel there, the recorded routes stay.
+int mpc_lqr_kkt_grads_kernel_supported(const mpc_lqr_problem *p, int kernel)
+{
+    if (!p || kernel != MPC_KKT_GRADS_WAVE64 || p->B < 0 || p->T < 1 || p->ns < 1 || p->nc < 1) return 0;
+    return (p->dtype == MPC_F64 && kkt_wave64_sizes(p->ns, p->nc)) ? 1 : 0;
+}
+
+int mpc_lqr_kkt_grads_kernel_route(const mpc_lqr_problem *p, int kernel, const void *dx, const void *du, const void *dl_dx,
+                                   const void *dl_du, const void *dC, const void *dc, const void *dF, const void *df, const void *dx_init)
+{
+    if (kernel == 0) return mpc_lqr_kkt_grads_route(p, dx, du, dl_dx, dl_du, dC, dc, dF, df, dx_init);
+    const int rc = check_kkt_grads(p, dx, du, dl_dx, dl_du, dC, dc, dF, dx_init);
+    if (rc) return rc;
+    if (kernel != MPC_KKT_GRADS_WAVE64) return fail(MPC_E_ARG, "mpc_lqr_kkt_grads_kernel: unknown kernel code (MPC_KKT_GRADS_WAVE64)");
+    if (p->B == 0) return 0;                 // (mpc_lqr_kkt_grads_kernel succeeds and launches nothing)
+    // the kernel's own refusals, the first thing it misses.  (A linear model: this entry carries no options, so no simulator can be
+    // named to it -- F is the model, and check_kkt_grads has asked for it.)
+    if (p->dtype != MPC_F64) return fail(MPC_E_DIMS, "mpc_lqr_kkt_grads_kernel: MPC_KKT_GRADS_WAVE64 needs float64");
+    if (!kkt_wave64_sizes(p->ns, p->nc))
+        return fail(MPC_E_DIMS, "mpc_lqr_kkt_grads_kernel: MPC_KKT_GRADS_WAVE64 needs 2 <= n_state + n_ctrl <= 64");
+    uintptr_t bits = 0;
+    for (const void *q : {p->C, p->c, p->F, p->cur_x, p->cur_u, dx, du, dl_dx, dC, dc, dF, df, dx_init}) bits |= (uintptr_t)q;
+    if (bits & 7) return fail(MPC_E_DIMS, "mpc_lqr_kkt_grads_kernel: MPC_KKT_GRADS_WAVE64 needs every pointer 8-byte aligned");
+    return MPC_KKT_GRADS_WAVE64;
+}
+
+int mpc_lqr_kkt_grads_kernel(const mpc_lqr_problem *p, int kernel, const void *dx, const void *du, const void *dl_dx,
+                             const void *dl_du, void *dC, void *dc, void *dF, void *df, void *dx_init, void *stream)
+{
+    if (kernel == 0) return mpc_lqr_kkt_grads(p, dx, du, dl_dx, dl_du, dC, dc, dF, df, dx_init, stream);
+    const int route = mpc_lqr_kkt_grads_kernel_route(p, kernel, dx, du, dl_dx, dl_du, dC, dc, dF, df, dx_init);
+    if (route <= 0) return route;            // (a refusal, or B = 0: nothing is launched)
+    return launch_kkt_wave64(make_params<double>(p, nullptr, nullptr), (const double *)dx, (const double *)du, (const double *)dl_dx,
+                             (double *)dC, (double *)dc, (double *)dF, (double *)df, (double *)dx_init, (hipStream_t)stream);
 }
 
 int mpc_lqr_kkt_shared_supported(const mpc_lqr_problem *p)

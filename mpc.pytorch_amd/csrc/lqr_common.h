@@ -132,6 +132,11 @@ bool kkt_wave_supported(const StepParams<float> &p, const float *dx, const float
                         const float *dF);
 int launch_kkt_wave(const StepParams<float> &p, const float *dx, const float *du, const float *dl_dx, float *dC,
                     float *dc, float *dF, float *df, float *dx_init, hipStream_t st);
+// ... the same two kernels in float64, 2 <= n <= 64 (kkt_wave64.hip); forced only: mpc_lqr_kkt_grads_kernel(MPC_KKT_GRADS_WAVE64).
+// Every pointer on 8 bytes; what is also on the 16-byte grid moves 16 bytes a lane, everything else 4.
+bool kkt_wave64_sizes(int ns, int nc);
+int launch_kkt_wave64(const StepParams<double> &p, const double *dx, const double *du, const double *dl_dx, double *dC,
+                      double *dc, double *dF, double *df, double *dx_init, hipStream_t st);
 
 // the costate recursion alone, parked in a compact [T-1,B,2 ns] area (kkt_wave.hip), and the batch-summed gradients of a shared
 // C, c, F, f built on it (kkt_shared.hip): outputs [T,n,n], [T,n], [T-1,ns,n], [T-1,ns], each may be NULL

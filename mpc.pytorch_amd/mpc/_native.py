@@ -25,6 +25,7 @@ KKT_NONE, KKT_DPP16, KKT_DPP16_PAD, KKT_MFMA40, KKT_MFMA40_PAD16, KKT_MFMA40_PAD
 KKT_MFMA40_NARROW16, KKT_MFMA40_NARROW4 = 6, 7     # forced only: the padded 32/8 backward on one state tile (mpc_lqr_kkt_fused_kernel)
 KKT_PREFER_NARROW = 100                            # ... asked for as a family: 6, else 7, where they take the call and no 12/4 kernel its sizes
 KKT_GRADS_DPP16, KKT_GRADS_WAVE, KKT_GRADS_GENERIC = 1, 2, 3                                            # mpc_lqr_kkt_grads_route
+KKT_GRADS_WAVE64 = 4        # forced only: the float64 wavefront kernels, 2 <= n_state + n_ctrl <= 64 (mpc_lqr_kkt_grads_kernel)
 
 ABI_VERSION = 9      # include/mpc_lqr.h: MPC_LQR_ABI_VERSION
 
@@ -226,7 +227,8 @@ EXPORTS = ("mpc_lqr_abi_version", "mpc_lqr_build_info", "mpc_lqr_last_error", "m
            "mpc_du_norm_reference", "mpc_slew_augment",
            "mpc_lqr_kkt_shared_supported", "mpc_lqr_kkt_shared_workspace_bytes", "mpc_lqr_kkt_grads_shared",
            "mpc_lqr_kkt_fused_route", "mpc_lqr_kkt_grads_route",
-           "mpc_lqr_kkt_fused_kernel", "mpc_lqr_kkt_fused_kernel_route", "mpc_lqr_kkt_fused_kernel_workspace_bytes")
+           "mpc_lqr_kkt_fused_kernel", "mpc_lqr_kkt_fused_kernel_route", "mpc_lqr_kkt_fused_kernel_workspace_bytes",
+           "mpc_lqr_kkt_grads_kernel_supported", "mpc_lqr_kkt_grads_kernel", "mpc_lqr_kkt_grads_kernel_route")
 
 _lib = None
 
@@ -275,6 +277,9 @@ def load():
     L.mpc_lqr_kkt_fused.argtypes = [PP, OP] + [_vp] * 11 + [_i64, _vp]
     L.mpc_lqr_kkt_fused_route.argtypes = [PP, OP] + [_vp] * 11 + [_i64]
     L.mpc_lqr_kkt_grads_route.argtypes = [PP] + [_vp] * 9
+    L.mpc_lqr_kkt_grads_kernel_supported.argtypes = [PP, ctypes.c_int]
+    L.mpc_lqr_kkt_grads_kernel.argtypes = [PP, ctypes.c_int] + [_vp] * 10
+    L.mpc_lqr_kkt_grads_kernel_route.argtypes = [PP, ctypes.c_int] + [_vp] * 9
     L.mpc_lqr_kkt_fused_kernel.argtypes = [PP, OP, ctypes.c_int] + [_vp] * 11 + [_i64, _vp]
     L.mpc_lqr_kkt_fused_kernel_route.argtypes = [PP, OP, ctypes.c_int] + [_vp] * 11 + [_i64]
     L.mpc_lqr_kkt_fused_kernel_workspace_bytes.restype = _i64
@@ -746,9 +751,11 @@ class HipBackend:
         p, keep = self._problem(self._zero_nominal(T, B, ns, nc, kw)[2] if nominal else x_star[0], C, c, F, f, x_star, u_star)
         return load(), dev, (T, B, ns, nc, n), kw, (x_star, u_star, dl_dx, dl_du), has_f, p, keep
 
-    def kkt_backward(self, C, c, F, f, x_star, u_star, dl_dx, dl_du, opts, impl=IMPL_AUTO, kernel=KKT_NONE):
+    def kkt_backward(self, C, c, F, f, x_star, u_star, dl_dx, dl_du, opts, impl=IMPL_AUTO, kernel=KKT_NONE, grads_kernel=0):
         """dx_init, dC, dc, dF, df of mpc/lqr_step.py:312-407 (reference), all on device.  kernel: a KKT_* code or KKT_PREFER_NARROW
-        for the fused call (plan_kkt_backward); where no fused kernel takes the call the three-call route does, as without it."""
+        for the fused call (plan_kkt_backward); where no fused kernel takes the call the three-call route does, as without it.
+        grads_kernel: 0, or a code for the closed-form part of that three-call route (KKT_GRADS_WAVE64: float64, n_state + n_ctrl
+        <= 64) -- mpc_lqr_kkt_grads_kernel wherever mpc_lqr_kkt_grads_kernel_supported says yes, mpc_lqr_kkt_grads everywhere else."""
         if impl == IMPL_AUTO:
             # the whole backward in one call where a fused kernel takes it (up to 32/8, fp32, C vouched symmetric)
             if kernel != KKT_NONE:
@@ -764,9 +771,12 @@ class HipBackend:
         dF = torch.empty(F.shape, **kw)          # every kernel writes all of it (t < T-1 is all there is)
         df = torch.empty(T - 1, B, ns, **kw) if has_f else None
         dx_init = torch.empty(B, ns, **kw)
-        _check(L.mpc_lqr_kkt_grads(ctypes.byref(p), sol["new_x"].data_ptr(), sol["new_u"].data_ptr(),
-                                   dl_dx.data_ptr(), dl_du.data_ptr(), dC.data_ptr(), dc.data_ptr(),
-                                   dF.data_ptr(), _ptr(df), dx_init.data_ptr(), _stream(dev)), "mpc_lqr_kkt_grads")
+        tail = (sol["new_x"].data_ptr(), sol["new_u"].data_ptr(), dl_dx.data_ptr(), dl_du.data_ptr(), dC.data_ptr(), dc.data_ptr(),
+                dF.data_ptr(), _ptr(df), dx_init.data_ptr(), _stream(dev))
+        if grads_kernel and L.mpc_lqr_kkt_grads_kernel_supported(ctypes.byref(p), grads_kernel):
+            _check(L.mpc_lqr_kkt_grads_kernel(ctypes.byref(p), grads_kernel, *tail), "mpc_lqr_kkt_grads_kernel")
+        else:
+            _check(L.mpc_lqr_kkt_grads(ctypes.byref(p), *tail), "mpc_lqr_kkt_grads")
         return dict(dx_init=dx_init, dC=dC, dc=dc, dF=dF, df=df, dx=sol["new_x"], du=sol["new_u"],
                     _keep=(keep, keep_o, negr, mask, sol))
 

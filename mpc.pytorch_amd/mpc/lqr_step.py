@@ -267,7 +267,8 @@ def _host_scalar_async(dev_scalar):
 
 class _StepConfig:
     """What one LQRStep(...) call fixes for its autograd node (closure state of the reference's factory)."""
-    __slots__ = ("solve", "no_op_forward", "delta_space", "current_x", "current_u", "u_lower", "u_upper", "c_symmetric", "T", "narrow_kkt_kernel")
+    __slots__ = ("solve", "no_op_forward", "delta_space", "current_x", "current_u", "u_lower", "u_upper", "c_symmetric", "T", "narrow_kkt_kernel",
+                 "f64_grad_kernel")
 
 
 def _step_forward(ctx, cfg, x_init, given, views):
@@ -279,6 +280,7 @@ def _step_forward(ctx, cfg, x_init, given, views):
     ctx.u_lower, ctx.u_upper = cfg.u_lower, cfg.u_upper
     ctx.c_symmetric = cfg.c_symmetric
     ctx.narrow_kkt_kernel = cfg.narrow_kkt_kernel
+    ctx.f64_grad_kernel = cfg.f64_grad_kernel
     if cfg.no_op_forward:
         ctx.save_for_backward(x_init, *given, cfg.current_x, cfg.current_u)
         return cfg.current_x, cfg.current_u
@@ -325,6 +327,8 @@ class _LQRStepFn(Function):
         x_init, C, c, F, f, new_x, new_u, dl_dx, dl_du, opts = _open_backward(ctx, dl_dx, dl_du)
         # (the keyword only where the flag is on: a backend that knows none is never handed it)
         kw = dict(kernel=_native.KKT_PREFER_NARROW) if ctx.narrow_kkt_kernel else {}
+        if ctx.f64_grad_kernel:
+            kw["grads_kernel"] = _native.KKT_GRADS_WAVE64
         g = _native.backend().kkt_backward(C, c, F, None if _is_empty(f) else f, new_x, new_u, dl_dx, dl_du, opts, **kw)
         df = g["df"] if g["df"] is not None else torch.Tensor()
         return None, g["dx_init"], g["dC"], g["dc"], g["dF"], df
@@ -384,7 +388,8 @@ class _LQRStepSharedFn(Function):
             g = be.kkt_backward_shared(Ce, ce, Fe, fe, new_x, new_u, dl_dx, dl_du, opts, tuple(bool(n) for n in needs))
             grads = [g["sum_dC"], g["sum_dc"], g["sum_dF"], g["sum_df"]]
         else:
-            g = be.kkt_backward(Ce, ce, Fe, fe, new_x, new_u, dl_dx, dl_du, opts)
+            kw = dict(grads_kernel=_native.KKT_GRADS_WAVE64) if ctx.f64_grad_kernel else {}
+            g = be.kkt_backward(Ce, ce, Fe, fe, new_x, new_u, dl_dx, dl_du, opts, **kw)
             grads = [g["dC"], g["dc"], g["dF"], g["df"]]
             grads = [v.sum(1) if (v is not None and s) else v for v, s in zip(grads, shared)]
         out = []
@@ -417,7 +422,8 @@ def LQRStep(n_state,
             c_symmetric=False,
             reference_du_norm=False,
             shared_grad_kernel=False,
-            narrow_kkt_kernel=False):
+            narrow_kkt_kernel=False,
+            f64_grad_kernel=False):
     """A single step of the box-constrained iLQR solver.
 
     Required: n_state, n_ctrl, T.  The returned callable takes (x_init [B,ns], C [T,B,n,n],
@@ -446,6 +452,11 @@ def LQRStep(n_state,
     narrow_kkt_kernel (not in the reference; off by default): the fused backward asks for the one-state-tile kernels
     (`KKT_PREFER_NARROW`, mpc_lqr_kkt_fused_kernel) -- 13 to 16 states, and smaller shapes no 12/4 kernel takes, in float32 under
     `c_symmetric`; every other backward is routed as without it.  The batch-shared backward keeps its route.
+
+    f64_grad_kernel (not in the reference; off by default): the closed-form part of a float64 backward with n_state + n_ctrl <= 64
+    runs on the float64 wavefront kernels (`KKT_GRADS_WAVE64`, mpc_lqr_kkt_grads_kernel) instead of the generic kernel; the nested
+    solve is the one it was.  Float32 problems and n_state + n_ctrl > 64 are routed as without it.  The batch-shared backward passes
+    the code on where it calls `kkt_backward` itself.
     """
     opts = StepOptions(u_lower=u_lower, u_upper=u_upper, u_zero_I=u_zero_I, delta_u=delta_u,
                        linesearch_decay=linesearch_decay, max_linesearch_iter=max_linesearch_iter,
@@ -517,6 +528,7 @@ def LQRStep(n_state,
     cfg.c_symmetric = bool(c_symmetric)
     cfg.T = T
     cfg.narrow_kkt_kernel = bool(narrow_kkt_kernel)
+    cfg.f64_grad_kernel = bool(f64_grad_kernel)
 
     def apply(x_init, C, c, F, f=None):
         if shared_grad_kernel and any(_is_shared(t, k) for k, t in enumerate((C, c, F, f))):

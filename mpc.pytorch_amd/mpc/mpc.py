@@ -172,7 +172,7 @@ class MPC(Module):
                  exit_unconverged=True, detach_unconverged=True, backprop=True, slew_rate_penalty=None,
                  prev_ctrl=None, not_improved_lim=5, best_cost_eps=1e-4, reference_du_norm=False,
                  narrow_step_kernel=False, narrow_kkt_kernel=False, row_carry_kernel=False, shared_grad_kernel=False,
-                 weight_grad_kernel=False, planned_network_slew=False):
+                 f64_grad_kernel=False, weight_grad_kernel=False, planned_network_slew=False):
         super().__init__()
         assert (u_lower is None) == (u_upper is None)
         assert max_linesearch_iter > 0
@@ -245,6 +245,12 @@ class MPC(Module):
         # autograd's expand to add up.  The iterations are untouched.  Which solves (`solve_route`: `shared_ending`); views the
         # caller expanded themselves keep the per-problem route.  Off by default (docs/history/r14.md)
         self.shared_grad_kernel = bool(shared_grad_kernel)
+        # OPT-IN: the differentiable ending's backward runs the closed-form part of a float64 problem with n_state + n_ctrl <= 64
+        # (the augmented sizes on the slew ending) on the float64 wavefront kernels (LQRStep(f64_grad_kernel=True):
+        # _native.KKT_GRADS_WAVE64, mpc_lqr_kkt_grads_kernel) instead of the generic kernel.  Float32 solves and larger shapes are
+        # routed as without it; the iterations and the nested solve are untouched.  Off by default: mpc_lqr_kkt_grads in float64 is
+        # pinned to the generic kernel by existing tests (docs/history/r27.md has the times)
+        self.f64_grad_kernel = bool(f64_grad_kernel)
         self.flag_reducer = None     # set by mpc.shard for lock-step sharded solves
         self.prev_ctrl = prev_ctrl
 
@@ -744,7 +750,8 @@ class MPC(Module):
             return self._solve_slew_subproblem(x_init, C, c, F, f, cost, dynamics, x, u, no_op_forward)
         step = self._lqr_step(self.n_state, cost, dynamics, x, u, no_op_forward, dict(
             c_symmetric=no_op_forward and getattr(self, "_c_symmetric", False), shared_grad_kernel=shared_grad_kernel,
-            **(dict(narrow_kkt_kernel=True) if self.narrow_kkt_kernel else {})))
+            **(dict(narrow_kkt_kernel=True) if self.narrow_kkt_kernel else {}),
+            **(dict(f64_grad_kernel=True) if self.f64_grad_kernel else {})))
         return step(x_init, C, c, F, f if f is not None else x_init.new_empty(0))
 
     def _lqr_step(self, n_state, true_cost, true_dynamics, current_x, current_u, no_op_forward, extra):
@@ -770,8 +777,10 @@ class MPC(Module):
         a_dyn = None if isinstance(dynamics, LinDx) else CtrlPassthroughDynamics(dynamics)
         a_cost = QuadCost(aC, ac) if isinstance(cost, QuadCost) else SlewRateCost(cost, slew_C, ns, nc)
         # (`narrow_kkt_kernel` only: the promise of the plain ending, see __init__)
-        step = self._lqr_step(ns + nc, a_cost, a_dyn, ax, u, no_op_forward, dict(
-            narrow_kkt_kernel=True, c_symmetric=no_op_forward and getattr(self, "_c_symmetric", False)) if self.narrow_kkt_kernel else {})
+        extra = dict(narrow_kkt_kernel=True, c_symmetric=no_op_forward and getattr(self, "_c_symmetric", False)) if self.narrow_kkt_kernel else {}
+        if self.f64_grad_kernel:
+            extra["f64_grad_kernel"] = True
+        step = self._lqr_step(ns + nc, a_cost, a_dyn, ax, u, no_op_forward, extra)
         out = step(ax_init, aC, ac, aF, af if af is not None else aC.new_empty(0))
         return (out[0][:, :, nc:],) + tuple(out[1:])
 
