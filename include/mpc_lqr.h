@@ -535,6 +535,30 @@ int mpc_mlp_linearize(const mpc_mlp_dynamics *net, int n_state, int n_ctrl, int6
 int mpc_mlp_linearize_carry(const mpc_mlp_dynamics *net, int n_state, int n_ctrl, int64_t N, const void *z, const void *u,
                             void *aF, void *af, void *workspace, int64_t workspace_bytes, void *stream);
 
+/* (6d') The network entries with a dtype (additive, the ABI number stays).  MPC_F32: each IS the entry above -- same codes, the
+ *      same bits from `supported`.  MPC_F64: W[l], b[l] and every array are doubles, and the work is done by kernels of their own
+ *      (csrc/nn_dynamics64.hip): ONE WAVEFRONT PER PROBLEM (per point) on plain float64 FMA, lanes across a layer's outputs, exp /
+ *      expm1 / a real division for the activations, the network read from nn.Linear's own tensors (staged in LDS by each block
+ *      when it fits).  Same semantics as (6d): the control update, u_zero_I, bounds intersected with delta_u, the line search
+ *      decided on J(trial) - J(nominal) summed by the kernel from p->C, p->c, `ctrl_carry`, K == NULL = util.get_traj (+ get_cost).
+ *      alpha of trial i is the running product alpha *= decay (mpc/lqr_step.py:247).  No atomics; results are bitwise
+ *      reproducible and depend on the prior contents of neither the outputs nor the workspace -- with one exception, shared with
+ *      (6d): out->status is OR-ed into (MPC_ST_NONFINITE is added to what the word held), so the caller zeroes it first.
+ *      mpc_mlp_supported_dtype(MPC_F64) answers bits 0 and 1 only (n_state <= 32, 1..4 layers, widths 1..4096 whose per-wavefront
+ *      areas fit 160 KiB of LDS); bit 2, the weight gradient, stays float32, as does mpc_mlp_linearize_carry.  Any other dtype: 0.
+ *      mpc_mlp_workspace_bytes_dtype(MPC_F64): a small positive size for a legal layer count (0 otherwise); the float64 kernels
+ *      keep no packed copy, the workspace is checked (shorter, NULL or not 16-byte aligned: MPC_E_ARG, as in (6d)) and reserved.
+ *      Refusals -- NULL, sizes, the workspace, options.true_dynamics, ctrl_carry handed to the linearisation, a dtype that is
+ *      neither (MPC_E_DTYPE) -- come before anything touches the device, with (6d)'s codes; B = 0 / N = 0 succeed and write
+ *      nothing.  mpc_mlp_rollout_dtype takes its dtype from p->dtype. */
+int mpc_mlp_supported_dtype(const mpc_mlp_dynamics *net, int n_state, int n_ctrl, int dtype);
+int64_t mpc_mlp_workspace_bytes_dtype(const mpc_mlp_dynamics *net, int dtype);
+int mpc_mlp_rollout_dtype(const mpc_lqr_problem *p, const mpc_lqr_options *o, const mpc_mlp_dynamics *net, const void *K,
+                          const void *k, const void *old_costs, const mpc_lqr_outputs *out, void *workspace,
+                          int64_t workspace_bytes, void *stream);
+int mpc_mlp_linearize_dtype(const mpc_mlp_dynamics *net, int dtype, int n_state, int n_ctrl, int64_t N, const void *x, const void *u,
+                            void *F, void *f, void *workspace, int64_t workspace_bytes, void *stream);
+
 /*      The backward of mpc_mlp_linearize with respect to the network's weights and biases -- what makes a solve through a
  *      trainable NNDynamics trainable on the device (GradMethods.ANALYTIC with diff=True, mpc/mpc.py:625-635).  With x, u
  *      constants and cotangents gF [N,ns,ns+nc], gf [N,ns] of F, f, and tau = [x;u], a_0 = tau, h_l = W_l a_{l-1} + b_l,

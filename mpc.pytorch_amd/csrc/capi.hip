@@ -845,6 +845,32 @@ static int check_kkt_grads(const mpc_lqr_problem *p, const void *dx, const void 
 
 using namespace mpclqr;
 
+// The argument checks of mpc_mlp_rollout and mpc_mlp_rollout_dtype behind their NULL / size / dtype tests, written once for both
+// reals; fills `sp`.  `empty`: B = 0, nothing to launch.
+template <typename real>
+static int mlp_rollout_params(const mpc_lqr_problem *p, const mpc_lqr_options *o, const void *K, const void *k, const void *old_costs,
+                              const mpc_lqr_outputs *out, StepParams<real> &sp, bool &empty)
+{
+    empty = p->B == 0;
+    if (empty) return MPC_OK;
+    if (!p->x_init || !p->cur_u) return fail(MPC_E_NULL, "x_init / current_u is NULL");
+    if ((p->C == nullptr) != (p->c == nullptr)) return fail(MPC_E_NULL, "pass both C and c, or neither");
+    if (!out->new_x) return fail(MPC_E_NULL, "new_x is NULL");
+    if ((K == nullptr) != (k == nullptr)) return fail(MPC_E_NULL, both_gains);
+    if (K) {
+        if (!p->cur_x || !p->C || !old_costs || !out->new_u)
+            return fail(MPC_E_NULL, "line search needs current_x, C, c, old_costs and new_u");
+        int rc = check_options(p, o);
+        if (rc) return rc;
+        if (o && o->true_dynamics) return fail(MPC_E_ARG, "mpc_mlp_rollout: options.true_dynamics must be NULL");
+    }
+    sp = make_params<real>(p, K ? o : nullptr, out);
+    sp.K = (real *)K;
+    sp.k = (real *)k;
+    sp.old_costs_in = (const real *)old_costs;
+    return MPC_OK;
+}
+
 extern "C" {
 
 int mpc_lqr_abi_version(void) { return MPC_LQR_ABI_VERSION; }
@@ -852,7 +878,7 @@ int mpc_lqr_abi_version(void) { return MPC_LQR_ABI_VERSION; }
 const char *mpc_lqr_build_info(void)
 {
     return "libmpc_lqr_hip gfx950 (CDNA4) | kernels: lqr_step_generic<f32,f64>, lqr_step_mfma16<f32,f64>, lqr_step_dpp16<f32>, lqr_step_dpp16_padded<f32>, "
-           "lqr_step_tiny<f32,f64>, lqr_step_wave1<f32>, lqr_step_wave1_carry<f32>, lqr_step_mfma40<f32>, lqr_step_mfma40_padded<f32>, lqr_step_mfma40_narrow<f32>, nn_rollout<f32>, nn_linearize<f32>, nn_param_grad<f32>, env_linearize, env_param_grad<f32,f64>, kkt_grads, kkt_grads_shared<f32>, kkt_fused<f32>, kkt_fused_padded<f32>, kkt_fused_narrow<f32>, pnqp, traj_cost, select_best, slew_augment<f32,f64>, kkt_grads_wave<f64> | built " __DATE__ " " __TIME__;
+           "lqr_step_tiny<f32,f64>, lqr_step_wave1<f32>, lqr_step_wave1_carry<f32>, lqr_step_mfma40<f32>, lqr_step_mfma40_padded<f32>, lqr_step_mfma40_narrow<f32>, nn_rollout<f32,f64>, nn_linearize<f32,f64>, nn_param_grad<f32>, env_linearize, env_param_grad<f32,f64>, kkt_grads, kkt_grads_shared<f32>, kkt_fused<f32>, kkt_fused_padded<f32>, kkt_fused_narrow<f32>, pnqp, traj_cost, select_best, slew_augment<f32,f64>, kkt_grads_wave<f64> | built " __DATE__ " " __TIME__;
 }
 
 const char *mpc_lqr_last_error(void) { return g_last_error.c_str(); }
@@ -1199,22 +1225,10 @@ int mpc_mlp_rollout(const mpc_lqr_problem *p, const mpc_lqr_options *o, const mp
     if (!p || !out) return fail(MPC_E_NULL, "problem / outputs is NULL");
     if (p->B < 0 || p->T < 1 || p->ns < 1 || p->nc < 1) return fail(MPC_E_DIMS, "need B>=0, T>=1, ns>=1, nc>=1");
     if (p->dtype != MPC_F32) return fail(MPC_E_DTYPE, "the network kernels are fp32 only");
-    if (p->B == 0) return MPC_OK;
-    if (!p->x_init || !p->cur_u) return fail(MPC_E_NULL, "x_init / current_u is NULL");
-    if ((p->C == nullptr) != (p->c == nullptr)) return fail(MPC_E_NULL, "pass both C and c, or neither");
-    if (!out->new_x) return fail(MPC_E_NULL, "new_x is NULL");
-    if ((K == nullptr) != (k == nullptr)) return fail(MPC_E_NULL, both_gains);
-    if (K) {
-        if (!p->cur_x || !p->C || !old_costs || !out->new_u)
-            return fail(MPC_E_NULL, "line search needs current_x, C, c, old_costs and new_u");
-        int rc = check_options(p, o);
-        if (rc) return rc;
-        if (o && o->true_dynamics) return fail(MPC_E_ARG, "mpc_mlp_rollout: options.true_dynamics must be NULL");
-    }
-    StepParams<float> sp = make_params<float>(p, K ? o : nullptr, out);
-    sp.K = (float *)K;
-    sp.k = (float *)k;
-    sp.old_costs_in = (const float *)old_costs;
+    StepParams<float> sp;
+    bool empty;
+    const int rc = mlp_rollout_params<float>(p, o, K, k, old_costs, out, sp, empty);
+    if (rc || empty) return rc;
     return launch_nn_rollout(sp, net, workspace, workspace_bytes, (hipStream_t)stream);
 }
 
@@ -1237,6 +1251,44 @@ int mpc_mlp_linearize_carry(const mpc_mlp_dynamics *net, int n_state, int n_ctrl
     if (!z || !u || !aF || !af) return fail(MPC_E_NULL, "mlp_linearize_carry: NULL argument");
     return launch_nn_linearize_carry(net, (long)N, n_state, n_ctrl, (const float *)z, (const float *)u, (float *)aF, (float *)af,
                                      workspace, workspace_bytes, (hipStream_t)stream);
+}
+
+// (6d') the entries above with a dtype: MPC_F32 is the entry above itself, MPC_F64 the plain-FMA kernels of nn_dynamics64.hip
+int mpc_mlp_supported_dtype(const mpc_mlp_dynamics *net, int n_state, int n_ctrl, int dtype)
+{
+    return dtype == MPC_F32 ? nn_budget(net, n_state, n_ctrl) : (dtype == MPC_F64 ? nn64_budget(net, n_state, n_ctrl) : 0);
+}
+
+int64_t mpc_mlp_workspace_bytes_dtype(const mpc_mlp_dynamics *net, int dtype)
+{
+    return dtype == MPC_F32 ? nn_workspace_bytes(net) : (dtype == MPC_F64 ? nn64_workspace_bytes(net) : 0);
+}
+
+int mpc_mlp_rollout_dtype(const mpc_lqr_problem *p, const mpc_lqr_options *o, const mpc_mlp_dynamics *net, const void *K,
+                          const void *k, const void *old_costs, const mpc_lqr_outputs *out, void *workspace,
+                          int64_t workspace_bytes, void *stream)
+{
+    if (!p || !out) return fail(MPC_E_NULL, "problem / outputs is NULL");
+    if (p->dtype == MPC_F32) return mpc_mlp_rollout(p, o, net, K, k, old_costs, out, workspace, workspace_bytes, stream);
+    if (p->B < 0 || p->T < 1 || p->ns < 1 || p->nc < 1) return fail(MPC_E_DIMS, "need B>=0, T>=1, ns>=1, nc>=1");
+    if (p->dtype != MPC_F64) return fail(MPC_E_DTYPE, "bad dtype");
+    StepParams<double> sp;
+    bool empty;
+    const int rc = mlp_rollout_params<double>(p, o, K, k, old_costs, out, sp, empty);
+    if (rc || empty) return rc;
+    return launch_nn64_rollout(sp, net, workspace, workspace_bytes, (hipStream_t)stream);
+}
+
+int mpc_mlp_linearize_dtype(const mpc_mlp_dynamics *net, int dtype, int n_state, int n_ctrl, int64_t N, const void *x, const void *u,
+                            void *F, void *f, void *workspace, int64_t workspace_bytes, void *stream)
+{
+    if (dtype == MPC_F32) return mpc_mlp_linearize(net, n_state, n_ctrl, N, x, u, F, f, workspace, workspace_bytes, stream);
+    if (dtype != MPC_F64) return fail(MPC_E_DTYPE, "bad dtype");
+    if (n_state < 1 || n_ctrl < 1 || N < 0) return fail(MPC_E_DIMS, "need n_state>=1, n_ctrl>=1, N>=0");
+    if (N == 0) return MPC_OK;
+    if (!x || !u || !F || !f) return fail(MPC_E_NULL, "mlp_linearize: NULL argument");
+    return launch_nn64_linearize(net, (long)N, n_state, n_ctrl, (const double *)x, (const double *)u, (double *)F, (double *)f,
+                                 workspace, workspace_bytes, (hipStream_t)stream);
 }
 
 int64_t mpc_mlp_param_grad_workspace_bytes(const mpc_mlp_dynamics *net, int64_t N) { return nn_param_grad_workspace_bytes(net, N); }

@@ -206,6 +206,14 @@ int64_t nn_param_grad_workspace_bytes(const mpc_mlp_dynamics *net, int64_t N);  
 int launch_nn_param_grad(const mpc_mlp_dynamics *net, long N, int ns, int nc, const float *x, const float *u, const float *gF,
                          const float *gf, const mpc_mlp_param_grads *out, void *workspace, int64_t bytes, hipStream_t st);
 
+// ... and the same network in float64 on plain FMA, one wavefront per problem / point (nn_dynamics64.hip): rollout / line search and the
+// dense linearisation; no weight gradient, no augmented-layout linearisation
+int nn64_budget(const mpc_mlp_dynamics *net, int ns, int nc);   // bits 0 and 1 as nn_budget
+int64_t nn64_workspace_bytes(const mpc_mlp_dynamics *net);       // 0: illegal layer count
+int launch_nn64_rollout(const StepParams<double> &p, const mpc_mlp_dynamics *net, void *workspace, int64_t bytes, hipStream_t st);
+int launch_nn64_linearize(const mpc_mlp_dynamics *net, long N, int ns, int nc, const double *x, const double *u, double *F, double *f,
+                          void *workspace, int64_t bytes, hipStream_t st);
+
 // fused MFMA path for n <= 16, f32 (lqr_mfma16.hip)
 bool mfma16_supported(const StepParams<float> &p);
 int launch_step_mfma16(const StepParams<float> &p, hipStream_t st);

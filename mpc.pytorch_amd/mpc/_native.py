@@ -161,23 +161,25 @@ class MlpSpec:
 
     @staticmethod
     def supported(weights, activation, like, bits=3):
-        """fp32 on the device of `like`, at most four layers, n_state <= 32, and layer widths whose staging areas fit the
-        160 KiB of LDS the kernels work in -- the library's own test (mpc_mlp_supported: both the rollout and the
-        linearisation kernel must take the network, e.g. NNDynamics(4, 1, [1024]) does not and keeps the module path;
-        `bits=1`: the rollout kernels alone, for a spec that is only ever rolled out -- `augmented()`)."""
-        if not (like.is_cuda and like.dtype == torch.float32 and 1 <= len(weights) <= MLP_MAX_LAYERS
+        """float32 or float64 on the device of `like` (network and `like` in the SAME dtype), at most four layers, n_state <= 32,
+        and layer widths whose staging areas fit the 160 KiB of LDS the kernels work in -- the library's own test
+        (mpc_mlp_supported_dtype: both the rollout and the linearisation kernel of that dtype must take the network, e.g. a
+        float32 NNDynamics(4, 1, [1024]) does not and keeps the module path; `bits=1`: the rollout kernels alone, for a spec
+        that is only ever rolled out -- `augmented()`)."""
+        if not (like.is_cuda and like.dtype in (torch.float32, torch.float64) and 1 <= len(weights) <= MLP_MAX_LAYERS
                 and activation in ACT_CODES and weights[-1].shape[0] <= 32
                 and all(W.shape[0] <= 4096 for W in weights)
-                and all(W.is_cuda and W.dtype == torch.float32 for W in weights)):
+                and all(W.is_cuda and W.dtype == like.dtype for W in weights)):
             return False
-        return MlpSpec.widths_supported([weights[0].shape[1]] + [W.shape[0] for W in weights], bits)
+        return MlpSpec.widths_supported([weights[0].shape[1]] + [W.shape[0] for W in weights], bits, like.dtype)
 
     @staticmethod
-    def widths_supported(widths, bits=3):
-        """mpc_mlp_supported for a network of these layer widths ([n_state + n_ctrl, hidden..., n_state]): every bit of `bits`
-        (1 = rollout, 2 = linearisation) must be set."""
+    def widths_supported(widths, bits=3, dtype=torch.float32):
+        """mpc_mlp_supported_dtype for a network of these layer widths ([n_state + n_ctrl, hidden..., n_state]) in `dtype`: every
+        bit of `bits` (1 = rollout, 2 = linearisation) must be set."""
         ns = int(widths[-1])
-        return (int(load().mpc_mlp_supported(ctypes.byref(MlpSpec._describe(widths)), ns, int(widths[0]) - ns)) & bits) == bits
+        code = MPC_F64 if dtype == torch.float64 else MPC_F32
+        return (int(load().mpc_mlp_supported_dtype(ctypes.byref(MlpSpec._describe(widths)), ns, int(widths[0]) - ns, code)) & bits) == bits
 
     @staticmethod
     def _describe(widths, activation=0, passthrough=0, ctrl_carry=0, pointers=()):
@@ -201,11 +203,17 @@ class MlpSpec:
         e = self._complete([(W.data_ptr() or 16, b.data_ptr() or 16) for W, b in zip(self.weights, self.biases)])
         return bool(int(load().mpc_mlp_supported(ctypes.byref(e), self.n_state, self.n_ctrl)) & 4)
 
+    @staticmethod
+    def dtype_of(like):
+        """The dtype of the network kernels that take `like`'s arrays: float64 for a double tensor, float32 for anything else."""
+        return torch.float64 if like.dtype == torch.float64 else torch.float32
+
     def to_struct(self, like):
-        keep = [t.detach().to(device=like.device, dtype=torch.float32).contiguous()
+        dt = MlpSpec.dtype_of(like)
+        keep = [t.detach().to(device=like.device, dtype=dt).contiguous()
                 for Wb in zip(self.weights, self.biases) for t in Wb]          # W_1, b_1, W_2, ...: the struct holds raw pointers
         e = self._complete([(W.data_ptr(), b.data_ptr()) for W, b in zip(keep[0::2], keep[1::2])])
-        nbytes = int(load().mpc_mlp_workspace_bytes(ctypes.byref(e)))
+        nbytes = int(load().mpc_mlp_workspace_bytes_dtype(ctypes.byref(e), MPC_F64 if dt == torch.float64 else MPC_F32))
         ws = torch.empty(nbytes, device=like.device, dtype=torch.uint8)
         keep.append(ws)
         return e, ws, nbytes, keep
@@ -223,7 +231,8 @@ EXPORTS = ("mpc_lqr_abi_version", "mpc_lqr_build_info", "mpc_lqr_last_error", "m
            "mpc_env_param_grad_workspace_bytes", "mpc_env_param_grad",
            "mpc_mlp_workspace_bytes", "mpc_mlp_rollout", "mpc_mlp_linearize", "mpc_mlp_linearize_carry",
            "mpc_mlp_param_grad_workspace_bytes", "mpc_mlp_param_grad",
-           "mpc_mlp_supported", "mpc_lqr_kkt_fused_supported", "mpc_lqr_kkt_fused_workspace_bytes", "mpc_lqr_kkt_fused",
+           "mpc_mlp_supported", "mpc_mlp_supported_dtype", "mpc_mlp_workspace_bytes_dtype", "mpc_mlp_rollout_dtype", "mpc_mlp_linearize_dtype",
+           "mpc_lqr_kkt_fused_supported", "mpc_lqr_kkt_fused_workspace_bytes", "mpc_lqr_kkt_fused",
            "mpc_du_norm_reference", "mpc_slew_augment",
            "mpc_lqr_kkt_shared_supported", "mpc_lqr_kkt_shared_workspace_bytes", "mpc_lqr_kkt_grads_shared",
            "mpc_lqr_kkt_fused_route", "mpc_lqr_kkt_grads_route",
@@ -305,6 +314,11 @@ def load():
     L.mpc_mlp_rollout.argtypes = [PP, OP, MP, _vp, _vp, _vp, UP, _vp, _i64, _vp]
     L.mpc_mlp_linearize.argtypes = [MP, ctypes.c_int, ctypes.c_int, _i64, _vp, _vp, _vp, _vp, _vp, _i64, _vp]
     L.mpc_mlp_linearize_carry.argtypes = [MP, ctypes.c_int, ctypes.c_int, _i64, _vp, _vp, _vp, _vp, _vp, _i64, _vp]
+    L.mpc_mlp_supported_dtype.argtypes = [MP, ctypes.c_int, ctypes.c_int, ctypes.c_int]
+    L.mpc_mlp_workspace_bytes_dtype.restype = _i64
+    L.mpc_mlp_workspace_bytes_dtype.argtypes = [MP, ctypes.c_int]
+    L.mpc_mlp_rollout_dtype.argtypes = [PP, OP, MP, _vp, _vp, _vp, UP, _vp, _i64, _vp]
+    L.mpc_mlp_linearize_dtype.argtypes = [MP, ctypes.c_int, ctypes.c_int, ctypes.c_int, _i64, _vp, _vp, _vp, _vp, _vp, _i64, _vp]
     L.mpc_mlp_param_grad_workspace_bytes.restype = _i64
     L.mpc_mlp_param_grad_workspace_bytes.argtypes = [MP, _i64]
     L.mpc_mlp_param_grad.argtypes = [MP, ctypes.c_int, ctypes.c_int, _i64, _vp, _vp, _vp, _vp, ctypes.POINTER(MlpParamGrads), _vp, _i64, _vp]
@@ -994,6 +1008,11 @@ class HipBackend:
         return out
 
     # -- (6d) NNDynamics in the kernels --------------------------------------------------------
+    # float32 on MFMA (csrc/nn_dynamics.hip) and float64 on plain FMA (csrc/nn_dynamics64.hip: rollout and dense linearisation).
+    # The augmented-layout linearisation and the weight gradient exist in float32 only: `_slew_plan` asks this before it puts a
+    # network's slew-rate solve on the pre-bound loop
+    carry_linearize_dtypes = (torch.float32,)
+
     def mlp_rollout(self, x_init, C, c, K, k, cur_x, cur_u, old_costs, opts, net, out_x=None, out_u=None):
         """lqr_forward with the network as true_dynamics (mpc/lqr_step.py:164-261): gains K, k and the nominal's
         cost come from a sweep (`lqr_step(..., want_gains=True)`).  `old_costs` MUST be the cost of (cur_x, cur_u) under the
@@ -1014,9 +1033,10 @@ class HipBackend:
                    alphas=torch.empty(B, **kw), status=torch.zeros(B, device=dev, dtype=torch.int32))
         out = self._bind_outputs(res)
         Kc, kc, oc = K.detach().contiguous(), k.detach().contiguous(), old_costs.detach().contiguous()
-        _check(L.mpc_mlp_rollout(ctypes.byref(p), ctypes.byref(o), ctypes.byref(e), Kc.data_ptr(), kc.data_ptr(),
-                                 oc.data_ptr(), ctypes.byref(out), ws.data_ptr(), nbytes, _stream(dev)),
-               "mpc_mlp_rollout")
+        # (float64: the entry with a dtype, which reads it off the problem; float32 stays on the entry it always called)
+        entry = "mpc_mlp_rollout_dtype" if C.dtype == torch.float64 else "mpc_mlp_rollout"
+        _check(getattr(L, entry)(ctypes.byref(p), ctypes.byref(o), ctypes.byref(e), Kc.data_ptr(), kc.data_ptr(),
+                                 oc.data_ptr(), ctypes.byref(out), ws.data_ptr(), nbytes, _stream(dev)), entry)
         res["_keep"] = (keep, keep_o, keep_e, Kc, kc, oc)
         return res
 
@@ -1033,8 +1053,9 @@ class HipBackend:
         cost = torch.empty(B, **kw) if C is not None else None
         out = Outputs()
         out.new_x, out.costs = x.data_ptr(), _ptr(cost)
-        _check(L.mpc_mlp_rollout(ctypes.byref(p), None, ctypes.byref(e), None, None, None, ctypes.byref(out),
-                                 ws.data_ptr(), nbytes, _stream(dev)), "mpc_mlp_rollout")
+        entry = "mpc_mlp_rollout_dtype" if u.dtype == torch.float64 else "mpc_mlp_rollout"
+        _check(getattr(L, entry)(ctypes.byref(p), None, ctypes.byref(e), None, None, None, ctypes.byref(out),
+                                 ws.data_ptr(), nbytes, _stream(dev)), entry)
         return x, cost
 
     def mlp_linearize(self, net, x, u, out_F=None, out_f=None):
@@ -1046,6 +1067,8 @@ class HipBackend:
         """`mlp_linearize` of the network itself (`net`: no ctrl_carry) at the augmented points z = (u_prev, x) [N,nc+ns],
         u [N,nc], written straight into the layout of the slew-rate augmentation (mpc/mpc.py:362-445, mpc/dynamics.py:131-150),
         na = ns + nc: aF [N,na,na+nc] = [[0 0 I], [0 F]], af [N,na] = [0; f] -- every element by the one launch."""
+        if z.dtype != torch.float32:
+            raise TypeError("mlp_linearize_carry is float32 only (mpc_mlp_linearize_carry), got %s" % z.dtype)
         return self._mlp_linearize("mpc_mlp_linearize_carry", True, net, z, u, out_F, out_f)
 
     def _mlp_linearize(self, entry, carry, net, x, u, out_F, out_f):
@@ -1060,6 +1083,11 @@ class HipBackend:
         f = torch.empty(N, rows, **kw) if out_f is None else out_f
         assert F.is_contiguous() and f.is_contiguous() and F.numel() == N * rows * (rows + nc) and f.numel() == N * rows
         e, ws, nbytes, keep_e = net.to_struct(x)
+        if x.dtype == torch.float64:
+            assert not carry and u.dtype == torch.float64
+            _check(load().mpc_mlp_linearize_dtype(ctypes.byref(e), MPC_F64, rows, nc, N, x.data_ptr(), u.data_ptr(), F.data_ptr(),
+                                                  f.data_ptr(), ws.data_ptr(), nbytes, _stream(dev)), "mpc_mlp_linearize_dtype")
+            return F, f
         _check(getattr(load(), entry)(ctypes.byref(e), rows - nc if carry else rows, nc, N, x.data_ptr(), u.data_ptr(), F.data_ptr(),
                                       f.data_ptr(), ws.data_ptr(), nbytes, _stream(dev)), entry)
         return F, f
@@ -1069,6 +1097,8 @@ class HipBackend:
         the cotangents gF [N,ns,ns+nc], gf [N,ns] of (F, f) -> [gW_1, gb_1, ..., gW_L, gb_L], float32 on the device, in
         nn.Linear's layouts (mpc_mlp_param_grad: MFMA over sixteen points per wavefront, one partial per block, a second
         launch adds them in a fixed order -- bitwise reproducible)."""
+        if any(t.dtype != torch.float32 for t in (x, u, gF, gf)):
+            raise TypeError("mlp_linearize_backward is float32 only (mpc_mlp_param_grad): a float64 linearisation keeps the module's autograd")
         dev = _require_device(x, u, gF, gf)
         L = load()
         N, ns = x.shape
@@ -1112,10 +1142,13 @@ class HipBackend:
         N = (T - 1) * B
         F, f = torch.empty(T - 1, B, ns, n, **kw), torch.empty(T - 1, B, ns, **kw)
         K, k = torch.empty(T, B, nc, ns, **kw), torch.empty(T, B, nc, **kw)
+        f64 = C.dtype == torch.float64
         e, mws, mbytes, keep_e = net.to_struct(C)
         if net.ctrl_carry:
             if net.inner is None or net.ctrl_carry != nc:
                 raise ValueError("plan_network_iteration: a ctrl_carry spec comes from MlpSpec.augmented()")
+            if f64:
+                raise TypeError("plan_network_iteration: the augmented linearisation (mpc_mlp_linearize_carry) is float32 only")
             le, lws, lbytes, keep_l = net.inner.to_struct(C)
             lin_fn, lin_ns = L.mpc_mlp_linearize_carry, ns - nc
         else:
@@ -1159,7 +1192,9 @@ class HipBackend:
                 sweeps[j][1], sweeps[j][2] = st_, sout
             keeps.append(keep_s)
         bind_sweeps(so)
-        step_fn, roll_fn = L.mpc_lqr_step, L.mpc_mlp_rollout
+        step_fn, roll_fn = L.mpc_lqr_step, (L.mpc_mlp_rollout_dtype if f64 else L.mpc_mlp_rollout)
+        if f64:          # (the dense float64 linearisation, behind the float32 entries' signature)
+            lin_fn = lambda e_, ns_, nc_, *rest: L.mpc_mlp_linearize_dtype(e_, MPC_F64, ns_, nc_, *rest)
         ep, rop, wsp, mwsp = ctypes.byref(e), ctypes.byref(ro_struct), ws.data_ptr(), mws.data_ptr()
         lep, lwsp = ctypes.byref(le), lws.data_ptr()
         Fp, fp, Kp, kp = F.data_ptr(), f.data_ptr(), K.data_ptr(), k.data_ptr()
@@ -1174,7 +1209,7 @@ class HipBackend:
             if rc == 0:
                 rc = roll_fn(ctypes.byref(rp), rop, ep, Kp, kp, outs[j]["old_costs"].data_ptr(), ctypes.byref(rout), mwsp, mbytes, st)
             if rc != 0:
-                _check(rc, "network iteration (mpc_mlp_linearize[_carry] / mpc_lqr_step / mpc_mlp_rollout)")
+                _check(rc, "network iteration (mpc_mlp_linearize[_carry / _dtype] / mpc_lqr_step / mpc_mlp_rollout[_dtype])")
             return outs[j]
 
         def vouch_c():

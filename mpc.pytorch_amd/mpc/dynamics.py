@@ -90,9 +90,10 @@ class NNDynamics(nn.Module):
         return out[0] if was_vector else out
 
     def native_net(self, like):
-        """The network as the kernels take it (csrc/nn_dynamics.hip: layers on MFMA, 16 problems per wavefront), or None
-        when this network / tensor is outside their limits (fp32 on the device, <= 4 layers, n_state <= 32) -- the
-        caller then calls the module timestep by timestep like the reference (mpc/lqr_step.py:223-225)."""
+        """The network as the kernels take it (float32, csrc/nn_dynamics.hip: layers on MFMA, 16 problems per wavefront; float64,
+        csrc/nn_dynamics64.hip: plain FMA, a wavefront per problem), or None when this network / tensor is outside their limits
+        (float32 or float64 on the device, the network in `like`'s dtype, <= 4 layers, n_state <= 32) -- the caller then calls
+        the module timestep by timestep like the reference (mpc/lqr_step.py:223-225)."""
         from ._native import MlpSpec
         # the kernels rebuild the computation from fcs / activation / passthrough: a subclass that overrides forward
         # (input normalisation, extra terms), a changed self.acts or a registered forward hook would be bypassed
@@ -151,7 +152,8 @@ class CtrlPassthroughDynamics(nn.Module):
         return out.squeeze() if was_vector else out
 
     def native_net(self, like):
-        """Around an NNDynamics the kernels can run (fp32, augmented n_state <= 32): the augmented network, else None."""
+        """Around an NNDynamics the kernels can run (float32 / float64, augmented n_state <= 32): the augmented network,
+        else None."""
         if type(self).forward is not CtrlPassthroughDynamics.forward or self._forward_hooks or self._forward_pre_hooks:
             return None
         inner = getattr(self.dynamics, "native_net", None)

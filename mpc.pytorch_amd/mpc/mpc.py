@@ -316,14 +316,15 @@ class MPC(Module):
         slew      a `slew_rate_penalty`, T > 1 and dynamics `_slew_plan` names: "lin" for a LinDx; the augmented EnvSpec of a
                   shipped simulator with one control under ANALYTIC / AUTO_DIFF (FINITE_DIFF keeps the reference's central
                   differences) on a backend whose lane-per-problem kernel carries the control; with `planned_network_slew` the
-                  augmented MlpSpec of a network as under `network`, n_state + n_ctrl <= 32, whose rollout kernels take the
-                  augmented widths.  The loop of `planned` / `network` on the augmented problem, built once (round 11).
+                  augmented MlpSpec of a network as under `network`, n_state + n_ctrl <= 32, in a dtype the backend's augmented
+                  linearisation exists in (HipBackend: float32), whose rollout kernels take the augmented widths.  The loop of
+                  `planned` / `network` on the augmented problem, built once (round 11).
                   Any other penalty: general.
         planned   a LinDx (any T); or T > 1 and a shipped simulator (`native_env`) under ANALYTIC / AUTO_DIFF: closed-form
                   linearisation and the simulator inside the step kernel.
-        network   T > 1, ANALYTIC, a backend with `plan_network_iteration` and an NNDynamics the kernels take (`native_net`: fp32
-                  on the device, <= 4 layers, n_state <= 32) that is not elu (no grad_input in the reference: the module refuses,
-                  mpc/dynamics.py:113-114): the whole iteration is three pre-bound C calls (round 5).
+        network   T > 1, ANALYTIC, a backend with `plan_network_iteration` and an NNDynamics the kernels take (`native_net`: float32
+                  or float64 on the device, <= 4 layers, n_state <= 32) that is not elu (no grad_input in the reference: the
+                  module refuses, mpc/dynamics.py:113-114): the whole iteration is three pre-bound C calls (round 5).
         general   everything else.
         `shared_ending`: `shared_grad_kernel` on a pre-bound loop without a penalty.  Which kernel such a loop forces
         (`narrow_step_kernel`, `row_carry_kernel`) is `_forced_impl`'s answer, at the sizes the loop runs at."""
@@ -534,7 +535,11 @@ class MPC(Module):
             if env.n_state == self.n_state + 1 and be.impl_supported(
                     env.n_state, 1, x_init.dtype, _native.IMPL_TINY, StepOptions(true_dynamics=env)):
                 return env
-        if self.planned_network_slew and self.n_state + self.n_ctrl <= 32:
+        # (a backend says in which dtypes its augmented-layout linearisation exists -- HipBackend: float32, so a float64 network
+        # keeps the general loop, whose CtrlPassthroughDynamics rollout may still run in the kernels; a backend that says nothing
+        # takes every dtype)
+        if (self.planned_network_slew and self.n_state + self.n_ctrl <= 32
+                and x_init.dtype in getattr(be, "carry_linearize_dtypes", (x_init.dtype,))):
             net = self._kernel_net(dx, be, x_init)
             if net is not None and net.n_state == self.n_state and net.n_ctrl == self.n_ctrl:
                 aug = net.augmented()
