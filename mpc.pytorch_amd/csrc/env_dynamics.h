@@ -98,6 +98,30 @@ MPC_HD float env_rsqrt(float x)
 }
 MPC_HD double env_rsqrt(double x) { return 1.0 / sqrt(x); }
 
+// th + dt * (w + dt * acc): the full pendulum's next angle (pendulum.py:73-76), up to 5000 rad at w = 1e5.  float: as the compiler
+// contracts it.  double: the reference's four roundings (dt * acc, w + ., dt * w2, th + .), NOT contracted -- an FMA puts the angle
+// one ulp of th2 off torch's, sin / cos of it move by that ulp, and d next / d w = -+(sin, cos)(th2) dt times w = 1e5 carries it into f
+// at 2.6 ... 7.5 times what tests/test_gpu_env_points.py grants float64 (docs/history/r29.md).  This is parity with the reference,
+// not accuracy: the contracted form is at least as close to the exact angle.  The simple pendulum's dt * (w + dt * acc) and the
+// cart-pole's dt * w stay contracted on purpose: they are inside the same bound as they are.
+// The barrier below is __builtin_canonicalize between product and sum; that the AMDGPU back end does not fuse across it is a
+// property of the compiler version, and test_linearize_and_transition_on_every_stratum[pendulum_full-*-f64] is what watches it.
+// (The template also serves env_param_grad.h's dual numbers, as before.)
+template <typename real> MPC_HD real env_next_angle(const real &th, const real &dt, const real &w, const real &acc) { return th + dt * (w + dt * acc); }
+MPC_HD double env_next_angle(double th, double dt, double w, double acc)
+{
+    double t1 = dt * acc;
+#if defined(__HIP_DEVICE_COMPILE__)       // (-ffp-contract=fast fuses in the back end, past `#pragma clang fp contract(off)`;
+    t1 = __builtin_canonicalize(t1);      // a canonicalize between product and sum keeps the two apart)
+#endif
+    const double w2 = w + t1;
+    double t2 = dt * w2;
+#if defined(__HIP_DEVICE_COMPILE__)
+    t2 = __builtin_canonicalize(t2);
+#endif
+    return th + t2;
+}
+
 // (cos, sin)(atan2(s, c) + delta) without forming the angle: (c, s) / |(c, s)| rotated by delta.  The reference takes
 // atan2 and then cos / sin of the sum (pendulum.py:68,76-77, cartpole.py:76,86-91); the rotation is the same
 // number in exact arithmetic and needs no atan2.
@@ -183,7 +207,7 @@ MPC_HD void env_step(const EnvDesc<real> &e, const real *x, real u, real *out, r
         const real d = e.params[3], b = e.params[4];
         acc = kg * env_sin(th + b) + ku * uc - d * th;            // pendulum.py:73-75
         acc_th = kg * env_cos(th + b) - d;
-        const real th2 = th + dt * (w + dt * acc);
+        const real th2 = env_next_angle(th, dt, w, acc);
         env_sincos(th2, s2, c2);
     }
     const real w2 = w + dt * acc;
