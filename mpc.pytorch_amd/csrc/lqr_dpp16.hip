@@ -10,22 +10,36 @@
 #include <string>
 #include "lqr_common.h"
 
-#define MPC_DEV __device__ __forceinline__
+// ---- the size of this compilation's staging array (wv::g_stage) --------------------------------------------------------------------
+#ifndef MPC_DPP16_NSTAGE
+#define MPC_DPP16_NSTAGE 4
+#endif
+// (MPC_KF_LDS_BYTES: the compilation that holds only the PADDED fused KKT kernel -- Makefile, lqr_dpp16_padkkt.o -- sweeps on two slots
+// like every padded sweep but gives its second pass the deep ring's 36 KiB)
+#ifdef MPC_KF_LDS_BYTES
+#define MPC_DPP16_LDS (MPC_KF_LDS_BYTES)
+#elif defined(MPC_DPP16_RESIDENT)
+// (the resident-F compilation, lqr_dpp16_res.o: seven 3072-byte blocks of F behind the ring -- lqr_dpp16_body.h, RES_STAGES)
+#define MPC_DPP16_LDS (MPC_DPP16_NSTAGE * 9216 + 7 * 3072)
+static_assert(MPC_DPP16_LDS <= 40960, "resident F: a wavefront's quarter of the CU's 160 KiB");
+#else
+#define MPC_DPP16_LDS (MPC_DPP16_NSTAGE * 9216)
+#endif
+// the KKT kernel shares this file's staging array: it lives in the compilation whose array fits its ring (-DMPC_DPP16_WITH_KKT; the
+// other builds' -DMPC_DPP16_NO_KKT says the same by its absence and is read by nothing)
+#ifndef MPC_KKT16_NSTAGE
+#define MPC_KKT16_NSTAGE 4
+#endif
+#define MPC_WV_STAGE_BYTES MPC_DPP16_LDS
+#include "wv_gfx950.h"
+
 #define DPPM " row_mask:0xf bank_mask:0xf\n"
 
 namespace mpclqr {
 namespace wv {
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-MPC_DEV int lane() { return (int)threadIdx.x; }
-MPC_DEV int problem() { return (int)blockIdx.x; }
-MPC_DEV unsigned long long clock() { return (unsigned long long)clock64(); }
 MPC_DEV float rcp(float x) { return __builtin_amdgcn_rcpf(x); }     // 1 ulp
-// an opaque register-to-register identity: keeps hipcc from folding a chain of selects back into scalar mask logic
-MPC_DEV void pin(float &x) { asm volatile("" : "+v"(x)); }
 MPC_DEV bool uniform(bool c) { return c; }
 MPC_DEV int uniform(int v) { return v; }
-MPC_DEV bool any(bool c) { return __ballot(c) != 0ull; }
-MPC_DEV unsigned long long ballot(bool c) { return __ballot(c); }
 // the value of lane l (wave-uniform l)
 MPC_DEV float readlane(float x, int l) { return __int_as_float(__builtin_amdgcn_readlane(__float_as_int(x), __builtin_amdgcn_readfirstlane(l))); }
 MPC_DEV double readlane_f64(double x, int l)
@@ -48,28 +62,7 @@ template <int ABID> MPC_DEV f32x4 mfma4(float a, float b, f32x4 c)
     return __builtin_amdgcn_mfma_f32_4x4x1f32(a, b, c, 2, ABID, 0);
 }
 
-// nothing is scheduled across this point
-MPC_DEV void sched_fence() { __builtin_amdgcn_sched_barrier(0); }
-
-// ---- DPP row broadcasts ----------------------------------------------------------------------
-template <int N> MPC_DEV float bcast(float x)
-{
-    return __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(x), 0x150 + N, 0xf, 0xf, true));
-}
-// acc += bcast_N(src) * mul
-template <int N> MPC_DEV void fmac_bcast(float &acc, float src, float mul)
-{
-    asm("s_nop 1\n"
-        "v_fmac_f32_dpp %0, %1, %2 row_newbcast:%3" DPPM
-        : "+v"(acc) : "v"(src), "v"(mul), "n"(N));
-}
-// the same where src was written at least three instructions earlier (or has just been read through DPP by the instruction in
-// front): no read-after-write wait states -- each s_nop is an issue slot on a chain that has nothing to fill it with (round 4)
-template <int N> MPC_DEV void fmac_bcast_settled(float &acc, float src, float mul)
-{
-    asm("v_fmac_f32_dpp %0, %1, %2 row_newbcast:%3" DPPM
-        : "+v"(acc) : "v"(src), "v"(mul), "n"(N));
-}
+// ---- DPP row broadcasts (bcast, fmac_bcast, fmac_bcast_settled: wv_gfx950.h) -------------------------------------------
 // acc += sum_i bcast_i(src) * mul[i]   (two accumulation chains)
 MPC_DEV void dot_bcast16(float &acc, float src, const float (&m)[16])
 {
@@ -130,16 +123,6 @@ MPC_DEV void dot_bcast12(float &acc, float src, const float (&m)[12])
         : "v"(src), "v"(m[0]), "v"(m[1]), "v"(m[2]), "v"(m[3]), "v"(m[4]), "v"(m[5]), "v"(m[6]), "v"(m[7]),
           "v"(m[8]), "v"(m[9]), "v"(m[10]), "v"(m[11]));
 }
-// sum over the 16 lanes of the row, result in every lane (compiler-visible DPP: hazards handled)
-MPC_DEV float row_sum(float x)
-{
-    x += __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(x), 0xB1, 0xf, 0xf, true));    // quad_perm [1,0,3,2]
-    x += __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(x), 0x4E, 0xf, 0xf, true));    // quad_perm [2,3,0,1]
-    x += __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(x), 0x141, 0xf, 0xf, true));   // row_half_mirror
-    x += __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(x), 0x140, 0xf, 0xf, true));   // row_mirror
-    return x;
-}
-
 // max over the 16 lanes of the row, result in every lane (x >= 0, no NaN handling wanted)
 MPC_DEV float row_max(float x)
 {
@@ -148,11 +131,6 @@ MPC_DEV float row_max(float x)
     x = __builtin_fmaxf(x, __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(x), 0x141, 0xf, 0xf, true)));
     x = __builtin_fmaxf(x, __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(x), 0x140, 0xf, 0xf, true)));
     return x;
-}
-// acc = max(acc, |a|, |b|): one v_max3_f32 with source modifiers (fmaxf() costs a canonicalising v_max per operand)
-MPC_DEV void absmax3(float &acc, float a, float b)
-{
-    asm("v_max3_f32 %0, %0, |%1|, |%2|" : "+v"(acc) : "v"(a), "v"(b));
 }
 
 // Four row sums in one go: lane j of a row comes back with sum over the row's 16 lanes of p_a, a = j & 3.
@@ -341,33 +319,7 @@ MPC_DEV double row_sum_f64(double x)
     return x;
 }
 
-// ---- HBM -> LDS staging --------------------------------------------------------------------
-#ifndef MPC_DPP16_NSTAGE
-#define MPC_DPP16_NSTAGE 4
-#endif
-// (MPC_KF_LDS_BYTES: the compilation that holds only the PADDED fused KKT kernel -- Makefile, lqr_dpp16_padkkt.o -- sweeps on two slots
-// like every padded sweep but gives its second pass the deep ring's 36 KiB)
-#ifdef MPC_KF_LDS_BYTES
-#define MPC_DPP16_LDS (MPC_KF_LDS_BYTES)
-#elif defined(MPC_DPP16_RESIDENT)
-// (the resident-F compilation, lqr_dpp16_res.o: seven 3072-byte blocks of F behind the ring -- lqr_dpp16_body.h, RES_STAGES)
-#define MPC_DPP16_LDS (MPC_DPP16_NSTAGE * 9216 + 7 * 3072)
-static_assert(MPC_DPP16_LDS <= 40960, "resident F: a wavefront's quarter of the CU's 160 KiB");
-#else
-#define MPC_DPP16_LDS (MPC_DPP16_NSTAGE * 9216)
-#endif
-// the KKT kernel shares this file's staging array: it lives in the compilation whose array fits its ring (-DMPC_DPP16_WITH_KKT; the
-// other builds' -DMPC_DPP16_NO_KKT says the same by its absence and is read by nothing)
-#ifndef MPC_KKT16_NSTAGE
-#define MPC_KKT16_NSTAGE 4
-#endif
-__shared__ __attribute__((aligned(16))) char g_stage16[MPC_DPP16_LDS];
-typedef __attribute__((address_space(3))) void lds_void_t;
-typedef __attribute__((address_space(1))) const void glb_void_t;
-// cache policy bits of the stage DMAs (see dma16_at).  C is read exactly once per launch: nt (measured
-// 129-132 -> 123-124 us).  F in the rollout is its second and last read -- yet nt there is 6 % SLOWER: the first
-// part of the rollout finds the blocks the sweep touched last still in the Infinity Cache.
-constexpr int C_AUX = 2, FR_AUX = 0;
+// ---- HBM -> LDS staging: what only this kernel uses (the array and the shared primitives: wv_gfx950.h, part 3) ----
 // results nobody in this launch reads again
 MPC_DEV void store_out(float *g, float v)
 {
@@ -380,9 +332,8 @@ MPC_DEV void store_out(float *g, float v)
 constexpr int KKT_LD_AUX = 0;
 MPC_DEV void dma16_once(const void *g, unsigned off)
 {
-    __builtin_amdgcn_global_load_lds((glb_void_t *)g, (lds_void_t *)(g_stage16 + off), 16, 0, KKT_LD_AUX);
+    __builtin_amdgcn_global_load_lds((glb_void_t *)g, (lds_void_t *)(g_stage + off), 16, 0, KKT_LD_AUX);
 }
-MPC_DEV void store_f32_out(float *g, float v) { *g = v; }
 typedef float f32x2 __attribute__((ext_vector_type(2)));
 // Gradients (dC, dF, dc, df, dx, du) are written once and never read back by the kernel: NON-TEMPORAL stores.  Round 4,
 // same box, fused backward at the headline shape: 218 -> 185 us (0.46 -> 0.54 of its roofline) -- as cached stores the 380 MB of
@@ -404,25 +355,8 @@ MPC_DEV void store_f32x4_grad(float *g, float __attribute__((ext_vector_type(4))
 }
 // the value of the neighbouring lane j ^ 1 (quad_perm [1,0,3,2])
 MPC_DEV float swap1(float x) { return __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(x), 0xB1, 0xf, 0xf, true)); }
-MPC_DEV void dma16_if(bool active, const void *g, unsigned off)
-{
-    if (active) __builtin_amdgcn_global_load_lds((glb_void_t *)g, (lds_void_t *)(g_stage16 + off), 16, 0, 0);
-}
-// ---- the padded instantiation's staging (lqr_dpp16_body.h, PADK; the same two primitives as lqr_mfma40.hip) ----------------
-// 4 bytes per lane from `base + voff` (base wave-uniform: a raw buffer of `nbytes`, voff per lane) to LDS offset `off` + 4 * lane.
-// A lane whose voff lies beyond the buffer writes ZERO (the hardware's range check; measured, tools/ubench/buffer_lds_probe.hip).
-template <int G> MPC_DEV void dma_buf(bool active, const void *base, unsigned nbytes, unsigned voff, unsigned off)
-{
-    static_assert(G == 4, "dword gathers");
-    if (active) {
-        __amdgpu_buffer_rsrc_t rs = __builtin_amdgcn_make_buffer_rsrc((void *)base, (short)0, (int)nbytes, 0x00020000);
-        __builtin_amdgcn_raw_ptr_buffer_load_lds(rs, (lds_void_t *)(g_stage16 + off), 4, (int)voff, 0, 0, 0);
-    }
-}
-MPC_DEV void dma4_if(bool active, const void *g, unsigned off)
-{
-    if (active) __builtin_amdgcn_global_load_lds((glb_void_t *)g, (lds_void_t *)(g_stage16 + off), 4, 0, 0);
-}
+// ---- the padded instantiation's staging (lqr_dpp16_body.h, PADK) ------------------------------------------------------------
+// wv_gfx950.h's dma_buf<4> (dword gathers through a raw buffer whose range check writes ZERO beyond the block)
 // ... with the instruction's immediate offset IMM: it moves the LDS destination and the buffer offset together (like dma16_at: one M0 per
 // group of gathers instead of one per gather -- three instructions a gather became one).  `voff` = source offset - IMM + BIAS, `base_biased` =
 // the block's base - BIAS, `nbytes_biased` = its size + BIAS: the bias keeps voff non-negative, the hardware's range check of voff + IMM
@@ -431,57 +365,15 @@ template <int IMM, int BIAS> MPC_DEV void dma_buf_at(const void *base_biased, un
 {
     static_assert(IMM >= 0 && IMM < 4096, "12-bit unsigned immediate");
     __amdgpu_buffer_rsrc_t rs = __builtin_amdgcn_make_buffer_rsrc((void *)base_biased, (short)0, (int)nbytes_biased, 0x00020000);
-    __builtin_amdgcn_raw_ptr_buffer_load_lds(rs, (lds_void_t *)(g_stage16 + anchor), 4, (int)voff, 0, IMM, 0);
+    __builtin_amdgcn_raw_ptr_buffer_load_lds(rs, (lds_void_t *)(g_stage + anchor), 4, (int)voff, 0, IMM, 0);
 }
 template <int IMM> MPC_DEV void dma4_at_if(bool active, const void *g, unsigned anchor)
 {
-    if (active) __builtin_amdgcn_global_load_lds((glb_void_t *)g, (lds_void_t *)(g_stage16 + anchor), 4, IMM, 0);
+    if (active) __builtin_amdgcn_global_load_lds((glb_void_t *)g, (lds_void_t *)(g_stage + anchor), 4, IMM, 0);
 }
-MPC_DEV void lds_store_f32x4(unsigned off, f32x4 v) { *(f32x4 *)(g_stage16 + off) = v; }
-MPC_DEV void lds_store_f32(unsigned off, float v) { *(float *)(g_stage16 + off) = v; }
-// DS instructions of one wave execute in program order: a compiler barrier is all there is to ask for
-MPC_DEV void lds_sync() { asm volatile("" ::: "memory"); }
-// The immediate offset of an LDS-DMA moves the LDS destination together with the global source
-// (tools/ubench/dma_offset_probe.hip).  With the source pointer biased by -IMM once, at set-up, every DMA of a
-// stage names the same LDS anchor `mid` and differs only in IMM: one M0 write per stage instead of one per
-// instruction.  `g` is the biased pointer (true source - IMM), -4096 <= IMM < 4096.
-enum { DMA_PLAIN = 0, DMA_C = 1, DMA_LAST = 2 };
-template <int IMM, int KIND = DMA_PLAIN> MPC_DEV void dma16_at(const void *g, unsigned mid)
-{
-    static_assert(IMM >= -4096 && IMM < 4096, "13-bit signed immediate");
-    __builtin_amdgcn_global_load_lds((glb_void_t *)g, (lds_void_t *)(g_stage16 + mid), 16, IMM,
-                                     KIND == DMA_C ? C_AUX : (KIND == DMA_LAST ? FR_AUX : 0));
-}
-template <int IMM> MPC_DEV void dma16_at_if(bool active, const void *g, unsigned mid)
-{
-    if (active) __builtin_amdgcn_global_load_lds((glb_void_t *)g, (lds_void_t *)(g_stage16 + mid), 16, IMM, 0);
-}
-// a dword at a wave-uniform address, through the scalar cache (s_load_dword: lgkmcnt, not vmcnt); the memory is
-// read-only for the lifetime of the launch
-MPC_DEV unsigned load_uniform_u32(const unsigned *g)
-{
-    typedef const __attribute__((address_space(4))) unsigned const_u32_t;
-    return *(const_u32_t *)(unsigned long)g;
-}
-MPC_DEV float lds_f32(unsigned off) { return *(const float *)(g_stage16 + off); }
 // a word of flag bits travelling in a float slot of a record (moves and selects keep the bits)
 MPC_DEV float bits_f32(unsigned u) { return __uint_as_float(u); }
 MPC_DEV unsigned f32_bits(float f) { return __float_as_uint(f); }
-MPC_DEV f32x4 lds_f32x4(unsigned off) { return *(const f32x4 *)(g_stage16 + off); }
-MPC_DEV void store_f32x4(float *g, f32x4 v) { *(f32x4 *)g = v; }
-template <int N> MPC_DEV void dma_wait()
-{
-    static_assert(N >= 0 && N < 64, "vmcnt is 6 bits on gfx9");
-    // (the trailing comment marks the wait as written by hand: tools/isa_lint.py looks for the UNMARKED vmcnt(0) the
-    // compiler puts in front of a vector load it cannot count across a loop)
-    asm volatile("s_waitcnt vmcnt(%0) ; counted" ::"n"(N) : "memory");
-}
-MPC_DEV void fence_own_stores()
-{
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
-    __builtin_amdgcn_s_waitcnt(0);
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup");
-}
 }  // namespace wv
 }  // namespace mpclqr
 

@@ -7,22 +7,13 @@
 // timesteps ahead of their use; the matrix work runs on v_mfma_f32_16x16x4_f32.
 #include <string>
 #include "lqr_common.h"
-
-#define MPC_DEV __device__ __forceinline__
+#include "wv_gfx950.h"          // (no MPC_WV_STAGE_BYTES: this kernel has two typed staging arrays and its own family for them, below)
 
 namespace mpclqr {
 namespace wv {
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-typedef double f64x4 __attribute__((ext_vector_type(4)));
 template <typename T> struct vec4_of;
 template <> struct vec4_of<float> { typedef f32x4 type; };
 template <> struct vec4_of<double> { typedef f64x4 type; };
-MPC_DEV int lane() { return (int)threadIdx.x; }
-MPC_DEV int problem() { return (int)blockIdx.x; }
-MPC_DEV f32x4 mfma(float a, float b, f32x4 c) { return __builtin_amdgcn_mfma_f32_16x16x4f32(a, b, c, 0, 0, 0); }
-// (round 5) v_mfma_f64_16x16x4_f64: lane 16 g + j holds A[i=j][k=g], B[k=g][j] like the float32 instruction, but D[4r+g][j] in element r
-// (float32: D[4g+r][j]; measured, tools/ubench/mfma_f64_probe.hip) -- lqr_mfma16_body.h's SLOT_T
-MPC_DEV f64x4 mfma(double a, double b, f64x4 c) { return __builtin_amdgcn_mfma_f64_16x16x4f64(a, b, c, 0, 0, 0); }
 MPC_DEV float readlane(float x, int l) { return __int_as_float(__builtin_amdgcn_readlane(__float_as_int(x), l)); }
 MPC_DEV double readlane(double x, int l)
 {
@@ -31,21 +22,14 @@ MPC_DEV double readlane(double x, int l)
     return __longlong_as_double(((long long)hi << 32) | (unsigned)lo);
 }
 MPC_DEV int readlane_i(int x, int l) { return __builtin_amdgcn_readlane(x, l); }
-MPC_DEV float shfl_xor(float x, int m) { return __shfl_xor(x, m, 64); }
-MPC_DEV double shfl_xor(double x, int m) { return __shfl_xor(x, m, 64); }
 MPC_DEV float rcp(float x)
 {
     float r = __builtin_amdgcn_rcpf(x);
     return fmaf(fmaf(-x, r, 1.f), r, r);     // one Newton step: <= 1 ulp
 }
 MPC_DEV double rcp(double x) { return 1.0 / x; }
-// an opaque register-to-register identity: keeps hipcc from folding a chain of selects back into scalar mask logic
-MPC_DEV void pin(float &x) { asm volatile("" : "+v"(x)); }
-MPC_DEV void pin(double &x) { asm volatile("" : "+v"(x)); }
 MPC_DEV bool uniform(bool c) { return __builtin_amdgcn_readfirstlane((int)c) != 0; }
 MPC_DEV int uniform(int v) { return __builtin_amdgcn_readfirstlane(v); }
-MPC_DEV unsigned long long ballot(bool c) { return __ballot(c); }
-MPC_DEV int ctz64(unsigned long long m) { return __builtin_ctzll(m); }
 // ---- HBM -> LDS staging --------------------------------------------------------------------
 // One ring of NSTAGE stage buffers per wavefront (= per workgroup); one array per element type, so that the float32 kernels keep
 // their 9 KiB (four wavefronts per SIMD) beside the float64 instantiation's 18 KiB.
@@ -55,8 +39,6 @@ __shared__ __attribute__((aligned(16))) char g_stage_d[MPC_LDS_BYTES(8)];
 template <typename T> MPC_DEV char *stage_of();
 template <> MPC_DEV char *stage_of<float>() { return g_stage; }
 template <> MPC_DEV char *stage_of<double>() { return g_stage_d; }
-typedef __attribute__((address_space(3))) void lds_void_t;
-typedef __attribute__((address_space(1))) const void glb_void_t;
 // 16 (4) bytes per lane from the lane's own global address to LDS[off + 16 (4) * lane]
 template <typename T> MPC_DEV void dma16r(const void *g, unsigned off)
 {
@@ -85,23 +67,6 @@ MPC_DEV void lds_store_r4(unsigned off, f64x4 v)
 {
     *(f64x2 *)(g_stage_d + off) = f64x2{v[0], v[1]};
     *(f64x2 *)(g_stage_d + off + 16) = f64x2{v[2], v[3]};
-}
-// LDS traffic between lanes of ONE wave: DS instructions execute in program order, so a compiler
-// barrier is all the ordering there is to ask for.
-MPC_DEV void lds_sync() { asm volatile("" ::: "memory"); }
-// Wait until at most N of this wave's vector-memory operations are outstanding.  hipcc does not
-// order LDS reads behind an LDS-DMA by itself; this is the ordering point (and a compiler barrier).
-template <int N> MPC_DEV void dma_wait()
-{
-    static_assert(N >= 0 && N < 64, "vmcnt is 6 bits on gfx9");
-    asm volatile("s_waitcnt vmcnt(%0) ; counted" ::"n"(N) : "memory");
-}
-MPC_DEV void fence_own_stores()
-{
-    // same-CU visibility of this wave's own global stores to its later loads
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
-    __builtin_amdgcn_s_waitcnt(0);
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup");
 }
 }  // namespace wv
 }  // namespace mpclqr

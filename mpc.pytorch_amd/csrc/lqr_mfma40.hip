@@ -4,20 +4,41 @@
 #include <string>
 #include "lqr_common.h"
 
-#define MPC_DEV __device__ __forceinline__
+// Compiled eleven times (Makefile): the step kernels on the three-slot sweep ring (launch_step_mfma40), the same with
+// -DMPC_MFMA40_SWEEP_NSTAGE=2 (launch_step_mfma40_ring2), with -DMPC_MFMA40_KKT the fused KKT backward (three slots); the padded
+// instantiation -DMPC_MFMA40_PAD=4 | 16 on two slots, as step kernels and as fused KKT backward (four objects); and the padded step
+// kernels on one state tile, -DMPC_MFMA40_XT=1 with either granule, on three slots (launch_step_mfma40_narrow4 / _narrow16), and
+// that tile's fused KKT backward the same way (launch_kkt_fused_mfma40_narrow4 / _narrow16).
+#ifndef MPC_MFMA40_SWEEP_NSTAGE
+#define MPC_MFMA40_SWEEP_NSTAGE 3              // (lqr_mfma40_body.h: why the sweep looks two timesteps ahead)
+#endif
+// state tiles of 16 rows (lqr_mfma40_body.h): 2 = the 32/8 kernel, 1 = its narrow instantiation (n_state <= 16, padded only)
+#ifndef MPC_MFMA40_XT
+#define MPC_MFMA40_XT 2
+#endif
+#define MPC_MFMA40_NS_ (16 * MPC_MFMA40_XT)
+#define MPC_MFMA40_N_ (MPC_MFMA40_NS_ + 8)
+// a sweep stage C | F | record and a pricing-rollout stage C | F | K | record: 12032 and 13056 B at two state tiles, 4352 and 4864 at one
+#define MPC_MFMA40_STAGE_ (4 * MPC_MFMA40_N_ * MPC_MFMA40_N_ + 4 * MPC_MFMA40_NS_ * MPC_MFMA40_N_ + 512)
+#define MPC_MFMA40_RSTAGE_ (MPC_MFMA40_STAGE_ + 32 * MPC_MFMA40_NS_)
+// pass 2's stage of the fused backward, F | K | record | V: 10752 B at two state tiles
+#define MPC_MFMA40_KSTAGE_ (4 * MPC_MFMA40_NS_ * MPC_MFMA40_N_ + 32 * MPC_MFMA40_NS_ + 512 + 1024 * MPC_MFMA40_XT * MPC_MFMA40_XT)
+// the sweep's slots or the pricing rollout's two, + the layout-turn words; the fused backward's second ring (31.5 KiB) lies inside
+// its three sweep slots
+#define MPC_MFMA40_LDS_STEP ((MPC_MFMA40_SWEEP_NSTAGE * MPC_MFMA40_STAGE_ > 2 * MPC_MFMA40_RSTAGE_ ? MPC_MFMA40_SWEEP_NSTAGE * MPC_MFMA40_STAGE_ : 2 * MPC_MFMA40_RSTAGE_) + 512)
+// (the padded fused backward sweeps on two slots: its second ring alone sets the size then)
+#if defined(MPC_MFMA40_KKT) && MPC_MFMA40_LDS_STEP < 3 * MPC_MFMA40_KSTAGE_
+#define MPC_MFMA40_LDS (3 * MPC_MFMA40_KSTAGE_)
+#else
+#define MPC_MFMA40_LDS MPC_MFMA40_LDS_STEP
+#endif
+#define MPC_WV_STAGE_BYTES MPC_MFMA40_LDS
+#include "wv_gfx950.h"
 
 namespace mpclqr {
 namespace wv {
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-MPC_DEV int lane() { return (int)threadIdx.x; }
-MPC_DEV int problem() { return (int)blockIdx.x; }
-MPC_DEV unsigned long long clock() { return (unsigned long long)clock64(); }
-MPC_DEV f32x4 mfma(float a, float b, f32x4 c) { return __builtin_amdgcn_mfma_f32_16x16x4f32(a, b, c, 0, 0, 0); }
 MPC_DEV float readlane(float x, int l) { return __int_as_float(__builtin_amdgcn_readlane(__float_as_int(x), l)); }
-MPC_DEV float shfl_xor(float x, int m) { return __shfl_xor(x, m, 64); }
 MPC_DEV bool uniform(bool c) { return __builtin_amdgcn_readfirstlane((int)c) != 0; }
-MPC_DEV bool any(bool c) { return __ballot(c) != 0ull; }
-MPC_DEV unsigned long long ballot(bool c) { return __ballot(c); }
 // sum over the four 16-lane rows, result in every lane: two row swaps (gfx950 v_permlane{16,32}_swap), no LDS
 MPC_DEV float sum_rows(float x)
 {
@@ -49,31 +70,6 @@ MPC_DEV float lower_halves(float a, float b)
     auto r = __builtin_amdgcn_permlane32_swap(__float_as_uint(a), __float_as_uint(b), false, false);
     return __uint_as_float(r[0]);
 }
-// DPP row broadcast: lane N of the caller's 16-lane row
-template <int N> MPC_DEV float bcast(float x)
-{
-    return __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(x), 0x150 + N, 0xf, 0xf, true));
-}
-// acc += bcast_N(src) * mul (src written long before: no DPP read-after-write wait states needed)
-template <int N> MPC_DEV void fmac_bcast_settled(float &acc, float src, float mul)
-{
-    asm("v_fmac_f32_dpp %0, %1, %2 row_newbcast:%3 row_mask:0xf bank_mask:0xf" : "+v"(acc) : "v"(src), "v"(mul), "n"(N));
-}
-// the same right behind the instruction that wrote src
-template <int N> MPC_DEV void fmac_bcast(float &acc, float src, float mul)
-{
-    asm("s_nop 1\n"
-        "v_fmac_f32_dpp %0, %1, %2 row_newbcast:%3 row_mask:0xf bank_mask:0xf" : "+v"(acc) : "v"(src), "v"(mul), "n"(N));
-}
-// sum over the 16 lanes of a row, in every lane of it
-MPC_DEV float row_sum(float x)
-{
-    x += __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(x), 0xB1, 0xf, 0xf, true));    // quad_perm [1,0,3,2]
-    x += __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(x), 0x4E, 0xf, 0xf, true));    // quad_perm [2,3,0,1]
-    x += __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(x), 0x141, 0xf, 0xf, true));   // row_half_mirror
-    x += __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(x), 0x140, 0xf, 0xf, true));   // row_mirror
-    return x;
-}
 // the sum over lanes 0..7 of a row, in lanes 0..7 of it (lanes 8..15: their own): the first three of row_sum's four steps --
 // for the box QP's vectors, which live in lanes 0..7 and whose sums are read in lane 0 (wv::first_lane)
 MPC_DEV float row_sum8(float x)
@@ -91,76 +87,18 @@ MPC_DEV float rcp(float x)
     float r = __builtin_amdgcn_rcpf(x);
     return fmaf(fmaf(-x, r, 1.f), r, r);     // one Newton step: <= 1 ulp
 }
-// a dword at a wave-uniform address through the scalar cache (s_load_dword: lgkmcnt, not vmcnt); read-only data
-MPC_DEV unsigned load_uniform_u32(const unsigned *g)
-{
-    typedef const __attribute__((address_space(4))) unsigned const_u32_t;
-    return *(const_u32_t *)(unsigned long)g;
-}
-// nothing is scheduled across this point
-MPC_DEV void sched_fence() { __builtin_amdgcn_sched_barrier(0); }
-// an opaque register-to-register identity (see mfma40::pick)
-MPC_DEV void pin(float &x) { asm volatile("" : "+v"(x)); }
-// Compiled eleven times (Makefile): the step kernels on the three-slot sweep ring (launch_step_mfma40), the same with
-// -DMPC_MFMA40_SWEEP_NSTAGE=2 (launch_step_mfma40_ring2), with -DMPC_MFMA40_KKT the fused KKT backward (three slots); the padded
-// instantiation -DMPC_MFMA40_PAD=4 | 16 on two slots, as step kernels and as fused KKT backward (four objects); and the padded step
-// kernels on one state tile, -DMPC_MFMA40_XT=1 with either granule, on three slots (launch_step_mfma40_narrow4 / _narrow16), and
-// that tile's fused KKT backward the same way (launch_kkt_fused_mfma40_narrow4 / _narrow16).
-#ifndef MPC_MFMA40_SWEEP_NSTAGE
-#define MPC_MFMA40_SWEEP_NSTAGE 3              // (lqr_mfma40_body.h: why the sweep looks two timesteps ahead)
-#endif
-// state tiles of 16 rows (lqr_mfma40_body.h): 2 = the 32/8 kernel, 1 = its narrow instantiation (n_state <= 16, padded only)
-#ifndef MPC_MFMA40_XT
-#define MPC_MFMA40_XT 2
-#endif
-#define MPC_MFMA40_NS_ (16 * MPC_MFMA40_XT)
-#define MPC_MFMA40_N_ (MPC_MFMA40_NS_ + 8)
-// a sweep stage C | F | record and a pricing-rollout stage C | F | K | record: 12032 and 13056 B at two state tiles, 4352 and 4864 at one
-#define MPC_MFMA40_STAGE_ (4 * MPC_MFMA40_N_ * MPC_MFMA40_N_ + 4 * MPC_MFMA40_NS_ * MPC_MFMA40_N_ + 512)
-#define MPC_MFMA40_RSTAGE_ (MPC_MFMA40_STAGE_ + 32 * MPC_MFMA40_NS_)
-// pass 2's stage of the fused backward, F | K | record | V: 10752 B at two state tiles
-#define MPC_MFMA40_KSTAGE_ (4 * MPC_MFMA40_NS_ * MPC_MFMA40_N_ + 32 * MPC_MFMA40_NS_ + 512 + 1024 * MPC_MFMA40_XT * MPC_MFMA40_XT)
-// the sweep's slots or the pricing rollout's two, + the layout-turn words; the fused backward's second ring (31.5 KiB) lies inside
-// its three sweep slots
-#define MPC_MFMA40_LDS_STEP ((MPC_MFMA40_SWEEP_NSTAGE * MPC_MFMA40_STAGE_ > 2 * MPC_MFMA40_RSTAGE_ ? MPC_MFMA40_SWEEP_NSTAGE * MPC_MFMA40_STAGE_ : 2 * MPC_MFMA40_RSTAGE_) + 512)
-// (the padded fused backward sweeps on two slots: its second ring alone sets the size then)
-#if defined(MPC_MFMA40_KKT) && MPC_MFMA40_LDS_STEP < 3 * MPC_MFMA40_KSTAGE_
-#define MPC_MFMA40_LDS (3 * MPC_MFMA40_KSTAGE_)
-#else
-#define MPC_MFMA40_LDS MPC_MFMA40_LDS_STEP
-#endif
-__shared__ __attribute__((aligned(16))) char g_stage40[MPC_MFMA40_LDS];
-typedef __attribute__((address_space(3))) void lds_void_t;
-typedef __attribute__((address_space(1))) const void glb_void_t;
+// ---- HBM -> LDS staging: what only this kernel uses (the array and the shared primitives: wv_gfx950.h, part 3) ----
 MPC_DEV void dma16(const void *g, unsigned off)
 {
-    __builtin_amdgcn_global_load_lds((glb_void_t *)g, (lds_void_t *)(g_stage40 + off), 16, 0, 0);
+    __builtin_amdgcn_global_load_lds((glb_void_t *)g, (lds_void_t *)(g_stage + off), 16, 0, 0);
 }
-MPC_DEV void dma16_if(bool active, const void *g, unsigned off)
-{
-    if (active) __builtin_amdgcn_global_load_lds((glb_void_t *)g, (lds_void_t *)(g_stage40 + off), 16, 0, 0);
-}
-// the same with an immediate offset, which on gfx950 moves source AND destination: instructions of one block share pointer and M0
-template <int IMM> MPC_DEV void dma16_at(const void *g, unsigned off)
-{
-    static_assert(IMM >= 0 && IMM < 4096, "13-bit signed immediate");
-    __builtin_amdgcn_global_load_lds((glb_void_t *)g, (lds_void_t *)(g_stage40 + off), 16, IMM, 0);
-}
-template <int IMM> MPC_DEV void dma16_at_if(bool active, const void *g, unsigned off)
-{
-    if (active) __builtin_amdgcn_global_load_lds((glb_void_t *)g, (lds_void_t *)(g_stage40 + off), 16, IMM, 0);
-}
-// ... of a block read exactly once per launch: the non-temporal policy (aux bit 1)
-constexpr int C_AUX = 2;
+// dma16_at (wv_gfx950.h) of a block read exactly once per launch: the non-temporal policy (C_AUX, aux bit 1)
 template <int IMM> MPC_DEV void dma16_once_at(const void *g, unsigned off)
 {
     static_assert(IMM >= 0 && IMM < 4096, "13-bit signed immediate");
-    __builtin_amdgcn_global_load_lds((glb_void_t *)g, (lds_void_t *)(g_stage40 + off), 16, IMM, C_AUX);
+    __builtin_amdgcn_global_load_lds((glb_void_t *)g, (lds_void_t *)(g_stage + off), 16, IMM, C_AUX);
 }
-// ---- the padded instantiation's staging (lqr_mfma40_body.h, PADK) -------------------------------------------------------------
-// G bytes per lane from `base + voff` (base wave-uniform: a raw buffer of `nbytes`, voff per lane) to LDS offset `off` + G * lane.
-// A lane whose voff lies beyond the buffer writes ZERO (the hardware's range check; measured, tools/ubench/buffer_lds_probe.hip):
-// that is the zero padding of the kernel's 40 x 40 / 32 x 40 blocks, at no instruction.
+// ---- the padded instantiation's staging (lqr_mfma40_body.h, PADK; dma_buf and dma4_if: wv_gfx950.h) ------------------------------
 // a wave-uniform pointer / word the compiler has moved to vector registers, back in scalar ones (two / one v_readfirstlane): the dword build's
 // C block address is computed on the vector ALU next to the timestep counter, and a buffer descriptor made from it was then wrapped in a
 // readfirstlane LOOP -- per gather, 25 a timestep (round 6)
@@ -171,18 +109,7 @@ MPC_DEV const void *uniform_ptr(const void *q)
     return (const void *)(((unsigned long long)hi << 32) | (unsigned long long)lo);
 }
 MPC_DEV unsigned uniform_u32(unsigned x) { return (unsigned)__builtin_amdgcn_readfirstlane((int)x); }
-template <int G> MPC_DEV void dma_buf(bool active, const void *base, unsigned nbytes, unsigned voff, unsigned off)
-{
-    static_assert(G == 4 || G == 16, "dword or dwordx4");
-    if (active) {
-        __amdgpu_buffer_rsrc_t rs = __builtin_amdgcn_make_buffer_rsrc((void *)base, (short)0, (int)nbytes, 0x00020000);
-        if constexpr (G == 4) __builtin_amdgcn_raw_ptr_buffer_load_lds(rs, (lds_void_t *)(g_stage40 + off), 4, (int)voff, 0, 0, 0);
-        else __builtin_amdgcn_raw_ptr_buffer_load_lds(rs, (lds_void_t *)(g_stage40 + off), 16, (int)voff, 0, 0, 0);
-    }
-}
 // a dword to `base + voff` through a raw buffer of `nbytes`: a lane whose voff lies beyond the buffer stores nothing
-MPC_DEV const void *uniform_ptr(const void *q);
-MPC_DEV unsigned uniform_u32(unsigned x);
 MPC_DEV void st_buf(float *base, unsigned nbytes, unsigned voff, float v)
 {
     __amdgpu_buffer_rsrc_t rs = __builtin_amdgcn_make_buffer_rsrc((void *)base, (short)0, (int)nbytes, 0x00020000);
@@ -194,37 +121,6 @@ MPC_DEV void st_buf(float *base, unsigned nbytes, unsigned voff, float v)
 MPC_DEV void st_buf_u(float *base, unsigned nbytes, unsigned voff, float v)
 {
     st_buf((float *)uniform_ptr(base), uniform_u32(nbytes), voff, v);
-}
-MPC_DEV void dma4_if(bool active, const void *g, unsigned off)
-{
-    if (active) __builtin_amdgcn_global_load_lds((glb_void_t *)g, (lds_void_t *)(g_stage40 + off), 4, 0, 0);
-}
-MPC_DEV void lds_store_f32x4(unsigned off, f32x4 v) { *(f32x4 *)(g_stage40 + off) = v; }
-MPC_DEV float lds_f32(unsigned off) { return *(const float *)(g_stage40 + off); }
-MPC_DEV f32x4 lds_f32x4(unsigned off) { return *(const f32x4 *)(g_stage40 + off); }
-MPC_DEV void lds_store_f32(unsigned off, float v) { *(float *)(g_stage40 + off) = v; }
-MPC_DEV void store_f32x4(float *g, f32x4 v) { *(f32x4 *)g = v; }
-// (the gains the sweep parks for its rollout: a plain store here, a store the emulator can hold back -- tests/emu/emu_mfma16.cpp)
-MPC_DEV void store_f32_out(float *g, float v) { *g = v; }
-MPC_DEV void fence_own_stores()
-{
-    // same-CU visibility of this wave's own global stores (the gains) to its later LDS-DMA reads
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
-    __builtin_amdgcn_s_waitcnt(0);
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup");
-}
-// DS instructions of one wave execute in program order: a compiler barrier is all there is to ask for
-MPC_DEV void lds_sync() { asm volatile("" ::: "memory"); }
-// hipcc does not order LDS reads behind an LDS-DMA by itself; this is the ordering point
-template <int N> MPC_DEV void dma_wait()
-{
-    static_assert(N >= 0 && N < 64, "vmcnt is 6 bits on gfx9");
-    asm volatile("s_waitcnt vmcnt(%0) ; counted" ::"n"(N) : "memory");
-}
-// acc = max(acc, |a|, |b|): one v_max3_f32 with source modifiers (fmaxf() costs a canonicalising v_max per operand)
-MPC_DEV void absmax3(float &acc, float a, float b)
-{
-    asm("v_max3_f32 %0, %0, |%1|, |%2|" : "+v"(acc) : "v"(a), "v"(b));
 }
 }  // namespace wv
 }  // namespace mpclqr

@@ -3,20 +3,15 @@
 // lockstep fibers).
 #pragma once
 #include "lqr_common.h"
-
-#define MPC_DEV __device__ __forceinline__
+// lane, problem, bcast, ballot, any, ctz64 are the shared ones; lds_sync and fmac_bcast are bound below for this kernel (wv_gfx950.h says
+// under "the names a kernel binds for itself" how they differ), so the header's asm forms of them are left out
+#define MPC_WV_ROW_PER_PROBLEM
+#include "wv_gfx950.h"
 
 namespace mpclqr {
 namespace wv {
 extern __shared__ float g_sm[];
 MPC_DEV float &sm(int i) { return g_sm[i]; }
-MPC_DEV int lane() { return (int)threadIdx.x; }
-MPC_DEV int problem() { return (int)blockIdx.x; }
-// lane N of the caller's 16-lane row (DPP row_newbcast)
-template <int N> MPC_DEV float bcast(float x)
-{
-    return __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(x), 0x150 + N, 0xf, 0xf, true));
-}
 // acc += bcast_N(src) * mul.  A v_mov_b32_dpp and a v_fmac the compiler schedules among the neighbouring chains and
 // whose DPP wait states it places itself: measured 4 % faster here than `s_nop 1; v_fmac_f32_dpp` in an asm block it cannot
 // see into (57.8 against 60.5 us per cart-pole step).
@@ -30,9 +25,6 @@ MPC_DEV double row_sum_f64(double x)
 MPC_DEV double shfl_xor_f64(double x, int off) { return __shfl_xor(x, off); }
 MPC_DEV double readlane_f64(double x, int src) { return __shfl(x, src); }
 MPC_DEV float readlane(float x, int src) { return __shfl(x, src); }
-MPC_DEV unsigned long long ballot(bool c) { return __ballot(c); }
-MPC_DEV bool any(bool c) { return __ballot(c) != 0ull; }
-MPC_DEV int ctz64(unsigned long long m) { return __builtin_ctzll(m); }
 // the workgroup is this one wavefront and its LDS instructions execute in order: the phases only have to be kept apart
 MPC_DEV void lds_sync()
 {
