@@ -264,7 +264,10 @@ int64_t mpc_lqr_resident_launches(void);
  * ignores the hint: with out->k given, that is the array). */
 int mpc_lqr_qp_record(const mpc_lqr_problem *p, const mpc_lqr_options *o, int impl, int64_t *offset_bytes, int64_t *st, int64_t *sb);
 
-/* Does kernel `impl` (1 generic, 2 fused MFMA, 3 DPP, 4 lane-per-problem, 5 MFMA sweep, 6 wavefront-per-problem, 7 padded 32/8, 8 padded 12/4, 9 narrow 16/8, 10 row-per-problem carry) accept this problem/options pair?  1 yes, 0 no. */
+/* Does kernel `impl` (1 generic, 2 fused MFMA, 3 DPP, 4 lane-per-problem, 5 MFMA sweep, 6 wavefront-per-problem, 7 padded 32/8, 8 padded 12/4, 9 narrow 16/8, 10 row-per-problem carry) accept this problem/options pair?  1 yes, 0 no.
+ * Sizes, dtype and options decide; pointers are never dereferenced and may all be NULL (a query by sizes).  Where p names its blocks, the
+ * two kernels that stream them in 16-byte granules (3, 5) also answer 0 for a C, c, F, f, x_init (5) or nominal whose base or T / B stride
+ * is off the 16-byte grid -- the call a forced mpc_lqr_step refuses with MPC_E_DIMS. */
 int mpc_lqr_impl_supported(const mpc_lqr_problem *p, const mpc_lqr_options *o, int impl);
 
 /* (ABI 9, additive) Is the row-per-problem carry kernel (impl 10) worth forcing for this call?  The rule by which auto prefers impl 6 to

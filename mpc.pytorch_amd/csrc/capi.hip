@@ -180,6 +180,17 @@ static StepParams<real> sizes_only(const StepParams<real> &sp)
     s.env.kind = sp.env.kind;
     return s;
 }
+// ... and the caller's blocks where the problem names them: pointers and strides of C, c, F, f, x_init and the nominal (a problem of
+// sizes alone has none, and so sits on every grid).  Default options still.
+template <typename real>
+static StepParams<real> sizes_and_blocks(const StepParams<real> &sp)
+{
+    StepParams<real> s = sizes_only(sp);
+    s.x_init = sp.x_init; s.cur_x = sp.cur_x; s.cur_u = sp.cur_u;
+    s.C = sp.C; s.C_st = sp.C_st; s.C_sb = sp.C_sb; s.c = sp.c; s.c_st = sp.c_st; s.c_sb = sp.c_sb;
+    s.F = sp.F; s.F_st = sp.F_st; s.F_sb = sp.F_sb; s.f = sp.f; s.f_st = sp.f_st; s.f_sb = sp.f_sb;
+    return s;
+}
 
 // What a kernel keeps in the workspace, in bytes from its start (-1: not there): the gains K | k where the caller passes none, its own
 // record Kk, all it asks for (`bytes`), and the k_t of its box QPs a later step may start from (qp: byte offset, element strides).
@@ -253,7 +264,8 @@ enum {
     K_CARRY_ONLY = 4,       // ... and nothing else (so: a whole step only)
     K_SWEEP_STOP = 8,       // can stop after its sweep (MPC_OPT_SWEEP_ONLY); a call heading for any other kernel takes the generic sweep
     K_PARKS_STATUS = 16,    // its layout counts where a caller's missing status words are parked (status_scratch_offset)
-    K_SIZES_QUERY = 32,     // its rule looks at the tensors: a query (mpc_lqr_impl_supported) is answered from the sizes alone, as ever
+    K_SIZES_QUERY = 32,     // its rule looks at the tensors and the options: a query (mpc_lqr_impl_supported) is answered from the sizes
+                            // and from the blocks the problem names (alignment of pointers and strides), the options left out as ever
     K_SIZES_RECORD = 64,    // ... and so is mpc_lqr_qp_record for a call that forces it
 };
 struct StepRefusal { int code; const char *text; };
@@ -370,7 +382,7 @@ template <typename real>
 static bool kernel_takes(const StepKernel &k, const StepParams<real> &sp, bool query = false)
 {
     const StepKernelIn<real> &d = in_dtype<real>(k);
-    return d.rule && d.rule(query && (k.flags & K_SIZES_QUERY) ? sizes_only(sp) : sp);
+    return d.rule && d.rule(query && (k.flags & K_SIZES_QUERY) ? sizes_and_blocks(sp) : sp);
 }
 template <typename real>
 static WsLayout ws_layout(int kernel, int T, int B, int ns, int nc) { return step_kernels[kernel].layout((int64_t)T * B, B, ns, nc, sizeof(real)); }
@@ -922,7 +934,8 @@ int mpc_lqr_impl_supported(const mpc_lqr_problem *p, const mpc_lqr_options *o, i
     // (MPC_ENV_CTRL_CARRY: the kernels that carry the control, see step_route)
     if (o && o->true_dynamics && (o->true_dynamics->kind & MPC_ENV_CTRL_CARRY) && !(k.flags & K_CARRIES)) return 0;
     if ((k.flags & K_CARRY_ONLY) && o && (o->flags & MPC_OPT_SWEEP_ONLY)) return 0;          // (a whole step only)
-    // sizes, dtype and options only: the alignment of the actual tensors is checked at launch
+    // sizes, dtype and options -- and, for the kernels that stream 16-byte granules (3, 5), the alignment of the blocks p names: the
+    // answer mpc_lqr_step gives a forced call for the same reason.  (Workspace and outputs are the call's: checked there.)
     return p->dtype == MPC_F32 ? kernel_takes<float>(k, make_params<float>(p, o, nullptr), true)
                                : kernel_takes<double>(k, make_params<double>(p, o, nullptr), true);
 }

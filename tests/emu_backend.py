@@ -91,12 +91,35 @@ def _ptr(a):
     return None if a is None else a.ctypes.data_as(ctypes.c_void_p).value
 
 
+def place_views(p, layouts, keep, C, c, F=None, f=None, o=None, qp_start=None):
+    """layouts: a row of tests/strided_views.py's table.  C, c, F, f (and qp_start into `o`) are carved as views out of NaN-filled
+    arenas and `p`'s pointers and eight strides are those of the views; `keep` holds the arenas alive."""
+    import strided_views as SV
+    pl = SV.place_problem(layouts, np, C, c, F if p.T > 1 else None, f, qp_start)
+    keep.append(pl)
+    for role in ("C", "c", "F", "f"):
+        v = pl[role]
+        if v is not None:
+            setattr(p, role, v.view.ctypes.data)
+            setattr(p, role + "_st", v.st)
+            setattr(p, role + "_sb", v.sb)
+    if pl["qp_start"] is not None:
+        q = pl["qp_start"]
+        o.qp_start, o.qp_start_st, o.qp_start_sb = q.view.ctypes.data, q.st, q.sb
+    return pl
+
+
 def lqr_step(x_init, C, c, F, f, cur_x, cur_u, u_lower=None, u_upper=None, u_zero_I=None, delta_u=None,
              linesearch_decay=0.2, max_linesearch_iter=10, pnqp_iter=20, force_general=False, dma_late=False,
-             kernel="mfma16", dtype=np.float32, env=None, nominal_on_dynamics=False, c_symmetric=False, qp_start=None):
+             kernel="mfma16", dtype=np.float32, env=None, nominal_on_dynamics=False, c_symmetric=False, qp_start=None, layouts=None):
     """Same signature as oracle.lqr_oracle.lqr_step.  Returns the kernel's outputs.  The fused
     kernels are float32; kernel="tiny" (lane-per-problem body, n_ctrl = 1) also runs in float64 and
-    takes env = (kind, params, dt, u_max): a shipped simulator as the rollout's true dynamics."""
+    takes env = (kind, params, dt, u_max): a shipped simulator as the rollout's true dynamics.
+
+    layouts: None (the dense layout, C_st = B n n, C_sb = n n and the like, as ever) or a row of tests/strided_views.py's table --
+    dense, shared, shared_b, shared_t, batch_major, slice_b, pitch_grid, pitch_off, mixed_a, mixed_b: C, c, F, f and a full
+    [T,B,nc] qp_start then reach the kernel as views of NaN-filled arenas, each through its own pair of strides.  A shared layout
+    shows the broadcast block's values: hand the dense equivalent (strided_views.place(...).dense) to whatever is compared."""
     f32 = np.dtype(dtype).type
     assert f32 == np.float32 or kernel in ("tiny", "mfma16")      # (mfma16: its float64 instantiation, round 5)
     C = np.ascontiguousarray(C, f32); c = np.ascontiguousarray(c, f32)
@@ -147,6 +170,8 @@ def lqr_step(x_init, C, c, F, f, cur_x, cur_u, u_lower=None, u_upper=None, u_zer
             full = np.ascontiguousarray(full)
         keep.append(full); keep.append(qs)
         o.qp_start, o.qp_start_st, o.qp_start_sb = full.ctypes.data, full.strides[0] // 4, full.strides[1] // 4
+    if layouts is not None:
+        place_views(p, layouts, keep, C, c, F, f, o, None if qp_start is None else np.ascontiguousarray(np.broadcast_to(qs, (T, B, nc))))
     res = dict(new_x=np.full((T, B, ns), np.nan, f32), new_u=np.full((T, B, nc), np.nan, f32),
                costs=np.empty(B, f32), old_costs=np.empty(B, f32), full_du_norm=np.empty(B, f32),
                alpha_du_norm=np.empty(B, f32), alphas=np.empty(B, f32),
@@ -202,7 +227,7 @@ def lqr_step(x_init, C, c, F, f, cur_x, cur_u, u_lower=None, u_upper=None, u_zer
     return res
 
 
-def kkt_grads(C, c, F, f, x_star, u_star, dx, du, dl_dx, dma_late=False, ring2=False):
+def kkt_grads(C, c, F, f, x_star, u_star, dx, du, dl_dx, dma_late=False, ring2=False, layouts=None):
     """The closed-form part of LQRStepFn.backward (mpc/lqr_step.py:346-404) through the emulated
     4-problems-per-wave kernel; n_state = 12, n_ctrl = 4, float32."""
     f32 = np.float32
@@ -220,6 +245,9 @@ def kkt_grads(C, c, F, f, x_star, u_star, dx, du, dl_dx, dma_late=False, ring2=F
         p.F, p.F_st, p.F_sb = _ptr(F), B * ns * n, ns * n
     p.cur_x, p.cur_u = _ptr(x_star), _ptr(u_star)
     has_f = f is not None and np.asarray(f).size > 0
+    keep = []
+    if layouts is not None:
+        place_views(p, layouts, keep, C, c, F)
     out = dict(dC=np.full((T, B, n, n), np.nan, f32), dc=np.full((T, B, n), np.nan, f32),
                dF=np.zeros((max(T - 1, 0), B, ns, n), f32), df=np.full((max(T - 1, 0), B, ns), np.nan, f32) if has_f else None,
                dx_init=np.full((B, ns), np.nan, f32))
@@ -237,7 +265,7 @@ MODEL_SRC_LATE, MODEL_STORES_LATE, MODEL_SKIP_IDLE = 1, 2, 4          # emu_set_
 
 
 def kkt_fused(C, c, F, f, x_star, u_star, dl_dx, dl_du, u_lower=None, u_upper=None, dma_late=False, ring2=True,
-              linesearch_decay=0.2, max_linesearch_iter=10, kernel="dpp16", model=0):
+              linesearch_decay=0.2, max_linesearch_iter=10, kernel="dpp16", model=0, layouts=None):
     """ALL of LQRStepFn.backward (mpc/lqr_step.py:312-407) through the emulated fused kernel (kkt_fused_wave,
     lqr_dpp16_body.h): n_state = 12, n_ctrl = 4, float32.  Returns dC, dc, dF, df, dx_init and the KKT
     solve's own (dx, du).  kernel="dpp16_pad": the padded instantiation, any n_state <= 12, n_ctrl <= 4 (the library's
@@ -269,6 +297,8 @@ def kkt_fused(C, c, F, f, x_star, u_star, dl_dx, dl_du, u_lower=None, u_upper=No
         keep += [lo, hi]
         o.bound_mode, o.lo, o.hi = N.BOUND_TENSOR, _ptr(lo), _ptr(hi)
     has_f = f is not None and np.asarray(f).size > 0
+    if layouts is not None:
+        place_views(p, layouts, keep, C, c, F)
     out = dict(dC=np.full((T, B, n, n), np.nan, f32), dc=np.full((T, B, n), np.nan, f32),
                dF=np.full((max(T - 1, 0), B, ns, n), np.nan, f32), df=np.full((max(T - 1, 0), B, ns), np.nan, f32) if has_f else None,
                dx_init=np.full((B, ns), np.nan, f32), dx=np.full((T, B, ns), np.nan, f32), du=np.full((T, B, nc), np.nan, f32),
@@ -287,7 +317,7 @@ def kkt_fused(C, c, F, f, x_star, u_star, dl_dx, dl_du, u_lower=None, u_upper=No
     return out
 
 
-def kkt_fused_mfma40(C, c, F, f, x_star, u_star, dl_dx, dl_du, u_lower=None, u_upper=None, dma_late=False, sweep3=True, pad=0, model=0):
+def kkt_fused_mfma40(C, c, F, f, x_star, u_star, dl_dx, dl_du, u_lower=None, u_upper=None, dma_late=False, sweep3=True, pad=0, model=0, layouts=None):
     """LQRStepFn.backward (mpc/lqr_step.py:312-407) at n_state = 32, n_ctrl = 8 through the emulated fused kernel
     (kkt_fused_wave, lqr_mfma40_body.h): dx, du, dx_init, df and the two costates from the kernel; dC, dc, dF are then the
     outer products kkt_outer_kernel (kkt_wave.hip) forms from exactly those vectors (:346-353, :387-396), here in numpy."""
@@ -320,6 +350,8 @@ def kkt_fused_mfma40(C, c, F, f, x_star, u_star, dl_dx, dl_du, u_lower=None, u_u
         keep += [lo, hi]
         o.bound_mode, o.lo, o.hi = N.BOUND_TENSOR, _ptr(lo), _ptr(hi)
     has_f = f is not None and np.asarray(f).size > 0
+    if layouts is not None:
+        place_views(p, layouts, keep, C, c, F if T > 1 else None)
     out = dict(dF=np.full((max(T - 1, 0), B, ns, n), np.nan, f32), df=np.full((max(T - 1, 0), B, ns), np.nan, f32) if has_f else None,
                dx_init=np.full((B, ns), np.nan, f32), dx=np.full((T, B, ns), np.nan, f32), du=np.full((T, B, nc), np.nan, f32),
                status=np.zeros(B, np.int32))

@@ -53,7 +53,7 @@ def lib(pad):
 
 
 def step(L, x_init, C, c, F, f, cur_x, cur_u, full=True, u_lower=None, u_upper=None, u_zero_I=None, delta_u=None,
-         nominal_on_dynamics=False, c_symmetric=False, max_linesearch_iter=10, linesearch_decay=0.2, pnqp_iter=20, dma_late=False, model=0):
+         nominal_on_dynamics=False, c_symmetric=False, max_linesearch_iter=10, linesearch_decay=0.2, pnqp_iter=20, dma_late=False, model=0, layouts=None):
     """emu_lqr_sweep_mfma40 of the emulator library L (full: the whole step; else the sweep alone) on one float32 problem.
     Returns every output, the caller's K / k among them.  dma_late, model: the emulator's switches (emu_backend.MODEL_*)."""
     f32 = np.float32
@@ -92,6 +92,8 @@ def step(L, x_init, C, c, F, f, cur_x, cur_u, full=True, u_lower=None, u_upper=N
         zm = np.ascontiguousarray((np.asarray(u_zero_I) != 0).astype(np.uint8))
         keep.append(zm)
         o.zero_mask = E._ptr(zm)
+    if layouts is not None:          # (a row of tests/strided_views.py's table; None: the dense layout as ever)
+        E.place_views(p, layouts, keep, C, c, F, f)
     res = dict(new_x=np.full((T, B, ns), np.nan, f32), new_u=np.full((T, B, nc), np.nan, f32),
                costs=np.full(B, np.nan, f32), old_costs=np.full(B, np.nan, f32), full_du_norm=np.full(B, np.nan, f32),
                alpha_du_norm=np.full(B, np.nan, f32), alphas=np.full(B, np.nan, f32),

@@ -49,7 +49,7 @@ def lib():
     return _LIB
 
 
-def step(kind, params, dt, u_max, x_init, C, c, F, cur_x, cur_u, lo, hi, max_linesearch_iter=10, linesearch_decay=0.2, carry=True):
+def step(kind, params, dt, u_max, x_init, C, c, F, cur_x, cur_u, lo, hi, max_linesearch_iter=10, linesearch_decay=0.2, carry=True, layouts=None):
     """One step of the emulated row-per-problem carry body: z = (u_prev, x) [B, ns + 1], C [T, B, n, n], scalar bounds, the simulator
     `kind` (MPC_ENV_*) behind the carry as true dynamics; F = None: the body linearises the simulator itself, else the caller's
     augmented F [T-1, B, ns + 1, ns + 2] is the sweep's model.  Returns (rc, outputs): rc != 0 is the body's refusal."""
@@ -81,6 +81,8 @@ def step(kind, params, dt, u_max, x_init, C, c, F, cur_x, cur_u, lo, hi, max_lin
         e.params, e.dt, e.u_max, e.linearize = E._ptr(prm), float(dt), float(u_max), int(F is None)
         keep.append(e)
         o.true_dynamics = ctypes.pointer(e)
+    if layouts is not None:          # (a row of tests/strided_views.py's table; None: the dense layout as ever)
+        E.place_views(p, layouts, keep, C, c, F if (F is not None and T > 1) else None)
     res = dict(new_x=np.full((T, B, ns), np.nan, f32), new_u=np.full((T, B, 1), np.nan, f32),
                costs=np.full(B, np.nan, f32), old_costs=np.full(B, np.nan, f32), full_du_norm=np.full(B, np.nan, f32),
                alpha_du_norm=np.full(B, np.nan, f32), alphas=np.full(B, np.nan, f32),
