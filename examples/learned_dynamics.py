@@ -8,6 +8,8 @@ rollout: csrc/nn_dynamics.hip).  The last, differentiable linearisation of a sol
 default; a controller built with `weight_grad_kernel=True` runs it as a kernel pair instead -- the same linearisation
 kernel forward, the weight-gradient kernel backward (csrc/nn_param_grad.h, _native.MlpLinearizeFn).  An opt-in because it
 is faster than the module route at (12, 4, [100]) and slower at (32, 8, [100]): docs/history/r10.md.
+A float64 network (`.double()` throughout, the dtype of finite-difference gradient checks) has the same pair behind a flag of
+its own, `f64_weight_grad_kernel=True` (csrc/nn_param_grad64.h, docs/history/r32.md); `weight_grad_kernel` governs float32 only.
 
     python examples/learned_dynamics.py [n_batch] [epochs]"""
 import os

@@ -548,7 +548,8 @@ int mpc_mlp_linearize_carry(const mpc_mlp_dynamics *net, int n_state, int n_ctrl
  *      reproducible and depend on the prior contents of neither the outputs nor the workspace -- with one exception, shared with
  *      (6d): out->status is OR-ed into (MPC_ST_NONFINITE is added to what the word held), so the caller zeroes it first.
  *      mpc_mlp_supported_dtype(MPC_F64) answers bits 0 and 1 only (n_state <= 32, 1..4 layers, widths 1..4096 whose per-wavefront
- *      areas fit 160 KiB of LDS); bit 2, the weight gradient, stays float32, as does mpc_mlp_linearize_carry.  Any other dtype: 0.
+ *      areas fit 160 KiB of LDS); the float64 weight gradient has a query of its own, mpc_mlp_param_grad_supported_dtype below;
+ *      mpc_mlp_linearize_carry stays float32.  Any other dtype: 0.
  *      mpc_mlp_workspace_bytes_dtype(MPC_F64): a small positive size for a legal layer count (0 otherwise); the float64 kernels
  *      keep no packed copy, the workspace is checked (shorter, NULL or not 16-byte aligned: MPC_E_ARG, as in (6d)) and reserved.
  *      Refusals -- NULL, sizes, the workspace, options.true_dynamics, ctrl_carry handed to the linearisation, a dtype that is
@@ -590,6 +591,28 @@ int64_t mpc_mlp_param_grad_workspace_bytes(const mpc_mlp_dynamics *net, int64_t 
 int mpc_mlp_param_grad(const mpc_mlp_dynamics *net, int n_state, int n_ctrl, int64_t N, const void *x, const void *u,
                        const void *gF, const void *gf, const mpc_mlp_param_grads *out, void *workspace,
                        int64_t workspace_bytes, void *stream);
+
+/*      (6d') The weight gradient with a dtype (additive, the ABI number stays).  MPC_F32: each IS the entry above --
+ *      mpc_mlp_param_grad_supported_dtype answers bit 2 of mpc_mlp_supported as 1 / 0.  MPC_F64: x, u, gF, gf, W[l], b[l] and
+ *      out->gW[l] / out->gb[l] are doubles and the same recursion runs on plain float64 FMA in kernels of their own
+ *      (csrc/nn_param_grad64.h): a block of 512 threads works on one point at a time, its wavefronts split each product of the
+ *      chain, every entry of gW / gb is owned by one thread, which keeps its sums in registers across the block's grid-stride
+ *      loop over the points; a block writes one partial into the workspace and a second launch adds the partials in block
+ *      order.  min(N, MPC_MLP_PARAM_GRAD64_MAX_BLOCKS) blocks (that constant: csrc/nn_param_grad64.h).  No atomics, every
+ *      sum in a fixed order: bitwise reproducible, and independent of what outputs and workspace held.  Sigmoid and relu.
+ *      The float64 envelope (mpc_mlp_param_grad_supported_dtype, answered for a complete description only, as bit 2 is):
+ *      n_state <= 32, 1..4 layers, no ctrl_carry, at most 40 * 512 weights and biases, and one point's matrices within
+ *      160 KiB of LDS; the network is staged in LDS when it is at most 96 KiB and fits beside them, else read in place.
+ *      mpc_mlp_param_grad_workspace_bytes_dtype(MPC_F64): min(max(N, 1), MPC_MLP_PARAM_GRAD64_MAX_BLOCKS) partials of
+ *      KMAX * 512 doubles, KMAX in {8, 16, 40} the instantiation that owns the network's weights and biases
+ *      (non-decreasing in N; -1 where the query says no, and for any other dtype); 16-byte aligned (else MPC_E_ARG).
+ *      Codes and their order as mpc_mlp_param_grad; a dtype that is neither: MPC_E_DTYPE.  Every refusal comes before
+ *      anything touches the device.  N = 0 succeeds and writes zeros. */
+int mpc_mlp_param_grad_supported_dtype(const mpc_mlp_dynamics *net, int n_state, int n_ctrl, int dtype);
+int64_t mpc_mlp_param_grad_workspace_bytes_dtype(const mpc_mlp_dynamics *net, int dtype, int64_t N);
+int mpc_mlp_param_grad_dtype(const mpc_mlp_dynamics *net, int dtype, int n_state, int n_ctrl, int64_t N, const void *x, const void *u,
+                             const void *gF, const void *gf, const mpc_mlp_param_grads *out, void *workspace,
+                             int64_t workspace_bytes, void *stream);
 
 /* (7) Device-side pieces of the iLQR driver loop (mpc/mpc.py:271-285, 299):
  *     per-problem best-iterate select without host round trips, ONE launch.

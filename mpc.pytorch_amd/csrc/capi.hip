@@ -890,7 +890,7 @@ int mpc_lqr_abi_version(void) { return MPC_LQR_ABI_VERSION; }
 const char *mpc_lqr_build_info(void)
 {
     return "libmpc_lqr_hip gfx950 (CDNA4) | kernels: lqr_step_generic<f32,f64>, lqr_step_mfma16<f32,f64>, lqr_step_dpp16<f32>, lqr_step_dpp16_padded<f32>, "
-           "lqr_step_tiny<f32,f64>, lqr_step_wave1<f32>, lqr_step_wave1_carry<f32>, lqr_step_mfma40<f32>, lqr_step_mfma40_padded<f32>, lqr_step_mfma40_narrow<f32>, nn_rollout<f32,f64>, nn_linearize<f32,f64>, nn_param_grad<f32>, env_linearize, env_param_grad<f32,f64>, kkt_grads, kkt_grads_shared<f32>, kkt_fused<f32>, kkt_fused_padded<f32>, kkt_fused_narrow<f32>, pnqp, traj_cost, select_best, slew_augment<f32,f64>, kkt_grads_wave<f64> | built " __DATE__ " " __TIME__;
+           "lqr_step_tiny<f32,f64>, lqr_step_wave1<f32>, lqr_step_wave1_carry<f32>, lqr_step_mfma40<f32>, lqr_step_mfma40_padded<f32>, lqr_step_mfma40_narrow<f32>, nn_rollout<f32,f64>, nn_linearize<f32,f64>, nn_param_grad<f32>, nn_param_grad64, env_linearize, env_param_grad<f32,f64>, kkt_grads, kkt_grads_shared<f32>, kkt_fused<f32>, kkt_fused_padded<f32>, kkt_fused_narrow<f32>, pnqp, traj_cost, select_best, slew_augment<f32,f64>, kkt_grads_wave<f64> | built " __DATE__ " " __TIME__;
 }
 
 const char *mpc_lqr_last_error(void) { return g_last_error.c_str(); }
@@ -1318,6 +1318,35 @@ int mpc_mlp_param_grad(const mpc_mlp_dynamics *net, int n_state, int n_ctrl, int
             if (!out->gW[l] || !out->gb[l]) return fail(MPC_E_NULL, "mlp_param_grad: gradient pointer is NULL");
     return launch_nn_param_grad(net, (long)N, n_state, n_ctrl, (const float *)x, (const float *)u, (const float *)gF,
                                 (const float *)gf, out, workspace, workspace_bytes, (hipStream_t)stream);
+}
+
+// (6d') the weight gradient with a dtype: MPC_F32 is the entries above, MPC_F64 the kernels of nn_param_grad64.h
+int mpc_mlp_param_grad_supported_dtype(const mpc_mlp_dynamics *net, int n_state, int n_ctrl, int dtype)
+{
+    if (dtype == MPC_F32) return (nn_budget(net, n_state, n_ctrl) & 4) ? 1 : 0;
+    return dtype == MPC_F64 ? nn64_param_grad_supported(net, n_state, n_ctrl) : 0;
+}
+
+int64_t mpc_mlp_param_grad_workspace_bytes_dtype(const mpc_mlp_dynamics *net, int dtype, int64_t N)
+{
+    if (dtype == MPC_F32) return nn_param_grad_workspace_bytes(net, N);
+    return dtype == MPC_F64 ? nn64_param_grad_workspace_bytes(net, N) : -1;
+}
+
+int mpc_mlp_param_grad_dtype(const mpc_mlp_dynamics *net, int dtype, int n_state, int n_ctrl, int64_t N, const void *x, const void *u,
+                             const void *gF, const void *gf, const mpc_mlp_param_grads *out, void *workspace,
+                             int64_t workspace_bytes, void *stream)
+{
+    if (dtype == MPC_F32) return mpc_mlp_param_grad(net, n_state, n_ctrl, N, x, u, gF, gf, out, workspace, workspace_bytes, stream);
+    if (dtype != MPC_F64) return fail(MPC_E_DTYPE, "bad dtype");
+    if (n_state < 1 || n_ctrl < 1 || N < 0) return fail(MPC_E_DIMS, "need n_state>=1, n_ctrl>=1, N>=0");
+    if (!net || !out || !workspace) return fail(MPC_E_NULL, "mlp_param_grad: NULL argument");
+    if (N > 0 && (!x || !u || !gF || !gf)) return fail(MPC_E_NULL, "mlp_param_grad: NULL argument");
+    if (net->n_layers >= 1 && net->n_layers <= MPC_MLP_MAX_LAYERS)
+        for (int l = 0; l < net->n_layers; ++l)
+            if (!out->gW[l] || !out->gb[l]) return fail(MPC_E_NULL, "mlp_param_grad: gradient pointer is NULL");
+    return launch_nn64_param_grad(net, (long)N, n_state, n_ctrl, (const double *)x, (const double *)u, (const double *)gF,
+                                  (const double *)gf, out, workspace, workspace_bytes, (hipStream_t)stream);
 }
 
 int mpc_lqr_kkt_prepare(int dtype, int B, int T, int ns, int nc, const void *dl_dx, const void *dl_du,

@@ -207,12 +207,18 @@ int launch_nn_param_grad(const mpc_mlp_dynamics *net, long N, int ns, int nc, co
                          const float *gf, const mpc_mlp_param_grads *out, void *workspace, int64_t bytes, hipStream_t st);
 
 // ... and the same network in float64 on plain FMA, one wavefront per problem / point (nn_dynamics64.hip): rollout / line search and the
-// dense linearisation; no weight gradient, no augmented-layout linearisation
+// dense linearisation; no augmented-layout linearisation
 int nn64_budget(const mpc_mlp_dynamics *net, int ns, int nc);   // bits 0 and 1 as nn_budget
 int64_t nn64_workspace_bytes(const mpc_mlp_dynamics *net);       // 0: illegal layer count
 int launch_nn64_rollout(const StepParams<double> &p, const mpc_mlp_dynamics *net, void *workspace, int64_t bytes, hipStream_t st);
 int launch_nn64_linearize(const mpc_mlp_dynamics *net, long N, int ns, int nc, const double *x, const double *u, double *F, double *f,
                           void *workspace, int64_t bytes, hipStream_t st);
+// ... and the linearisation's weight gradient in float64, one point a block and pass (nn_param_grad64.h): sigmoid / relu, no
+// ctrl_carry, a complete description
+int nn64_param_grad_supported(const mpc_mlp_dynamics *net, int ns, int nc);                 // 1 / 0
+int64_t nn64_param_grad_workspace_bytes(const mpc_mlp_dynamics *net, int64_t N);            // -1: outside the kernel
+int launch_nn64_param_grad(const mpc_mlp_dynamics *net, long N, int ns, int nc, const double *x, const double *u, const double *gF,
+                           const double *gf, const mpc_mlp_param_grads *out, void *workspace, int64_t bytes, hipStream_t st);
 
 // fused MFMA path for n <= 16, f32 (lqr_mfma16.hip)
 bool mfma16_supported(const StepParams<float> &p);

@@ -8,8 +8,11 @@
 //
 // Memory: the network is nn.Linear's own tensors, copied into LDS by each block when it fits beside the wavefronts' areas
 // (rows on an odd stride), else read in place through the caches.  The float32 kernels of nn_dynamics.hip are not touched.
-// The workspace argument of the entries is checked like the float32 one (size, 16-byte alignment) and reserved: nothing reads
-// or writes it today.
+// The workspace argument of the rollout and linearisation entries is checked like the float32 one (size, 16-byte alignment) and
+// reserved: nothing reads or writes it today.
+// The linearisation's weight gradient (mpc_mlp_param_grad_dtype, csrc/nn_param_grad64.h) is a BLOCK per point: nn64_param_grad_kernel
+// keeps each thread's share of the sums in registers across its points and leaves one partial per block in the workspace,
+// nn64_param_grad_final_kernel adds the partials in block order.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include <atomic>
@@ -17,6 +20,7 @@
 
 #include "lqr_common.h"
 #include "nn_dynamics64.h"
+#include "nn_param_grad64.h"
 
 namespace mpclqr {
 namespace {
@@ -68,6 +72,47 @@ __global__ void __launch_bounds__(512) nn64_linearize_kernel(Net arg, long N, in
     WaveExec ex;
     for (long i = (long)blockIdx.x * nwave + wave; i < N; i += (long)gridDim.x * nwave)
         nn64::linearize_point<WL>(ex, m, lds64, area, ns, nc, x + i * ns, u + i * nc, F + i * ns * n, f + i * ns);
+}
+
+// the block as the executor of nn_param_grad64.h: the wavefront's lanes as above, the block's barrier
+struct BlockExec {
+    __device__ __forceinline__ int lane() const { return threadIdx.x & 63; }
+    __device__ __forceinline__ int tid() const { return threadIdx.x; }
+    __device__ __forceinline__ void sync() const { __syncthreads(); }
+    __device__ __forceinline__ double xor_get(double v, int mask) const { return __shfl_xor(v, mask); }
+};
+
+// grid-stride over the points, one point a block and pass; the block's sums leave as one partial (nn_param_grad64.h)
+template <bool WL, int KMAX>
+__global__ void __launch_bounds__(nn64::PG64_THREADS) nn64_param_grad_kernel(Net arg, nn64::GradLayout g, long N, int ns, int nc, const double *x,
+                                                                             const double *u, const double *gF, const double *gf,
+                                                                             double *partials)
+{
+    extern __shared__ __attribute__((aligned(16))) double lds64[];
+    __shared__ Net m;
+    if (threadIdx.x == 0) m = arg;
+    __syncthreads();
+    if (WL) {
+        nn64::stage_net(m, lds64, threadIdx.x, blockDim.x);
+        __syncthreads();
+    }
+    double acc[KMAX];
+#pragma unroll
+    for (int k = 0; k < KMAX; ++k) acc[k] = 0.0;
+    double *area = lds64 + (WL ? m.total : 0);
+    const long n = ns + nc;
+    BlockExec ex;
+    for (long i = blockIdx.x; i < N; i += gridDim.x)
+        nn64::param_grad_point<WL, KMAX>(ex, m, g, lds64, area, x + i * ns, u + i * nc, gF + i * ns * n, gf + i * ns, acc);
+    double *out = partials + (long)blockIdx.x * KMAX * nn64::PG64_THREADS;
+#pragma unroll
+    for (int k = 0; k < KMAX; ++k) out[k * nn64::PG64_THREADS + threadIdx.x] = acc[k];
+}
+
+__global__ void __launch_bounds__(256) nn64_param_grad_final_kernel(nn64::GradFinal a, long entries)
+{
+    const long e = (long)blockIdx.x * 256 + threadIdx.x;
+    if (e < entries) nn64::sum_partials(a, e);
 }
 
 inline int check_launch(const char *what)
@@ -175,6 +220,56 @@ template <auto Kernel, typename... A> int launch(const char *name, const Plan &p
     return check_launch(name);
 }
 
+// The weight gradient's launch (nn_param_grad64.h): the KMAX instantiation that owns the network's weights and biases, the
+// network staged beside the block's area or read in place.  fits == false: outside the kernel
+struct GradPlan {
+    bool fits, wl;
+    int kmax;
+    nn64::GradLayout g;
+    size_t lds;
+};
+
+GradPlan grad_plan(const Net &m)
+{
+    GradPlan pl = {};
+    pl.g = nn64::grad_layout(m);
+    pl.kmax = nn64::grad_kmax(pl.g.entries);
+    const size_t wbytes = (size_t)m.total * 8, area = (size_t)pl.g.doubles * 8;
+    pl.fits = pl.kmax > 0 && area <= LDS_MAX;
+    pl.wl = wbytes <= WEIGHTS_IN_LDS_MAX && wbytes + area <= LDS_MAX;
+    pl.lds = (pl.wl ? wbytes : 0) + area;
+    return pl;
+}
+
+inline long grad_blocks(long N) { return N < MPC_MLP_PARAM_GRAD64_MAX_BLOCKS ? N : MPC_MLP_PARAM_GRAD64_MAX_BLOCKS; }
+// one partial of kmax * PG64_THREADS doubles a block (room for one at N = 0: the size never shrinks with N)
+inline int64_t grad_workspace_bytes(const GradPlan &pl, long N)
+{
+    const long blocks = grad_blocks(N < 1 ? 1 : N);
+    return (int64_t)blocks * pl.kmax * nn64::PG64_THREADS * 8;
+}
+
+// a complete description of a network the weight-gradient kernel takes (silent)
+bool grad_describe(const mpc_mlp_dynamics *net, int ns, int nc, Net &m, GradPlan &pl)
+{
+    if (ns < 1 || nc < 1 || check_net(net, ns, nc, false, nullptr, 0).code) return false;
+    if ((net->activation != MPC_ACT_SIGMOID && net->activation != MPC_ACT_RELU) || net->ctrl_carry != 0) return false;
+    for (int l = 0; l < net->n_layers; ++l)
+        if (!net->W[l] || !net->b[l]) return false;
+    describe(net, m);
+    pl = grad_plan(m);
+    return pl.fits;
+}
+
+template <bool WL, int KMAX, typename... A> int launch_grad(const GradPlan &pl, unsigned blocks, hipStream_t st, A... args)
+{
+    Plan lp = {};
+    lp.lds = pl.lds;
+    lp.nw = nn64::PG64_THREADS / 64;
+    lp.grid = blocks;
+    return launch<nn64_param_grad_kernel<WL, KMAX>>("nn64_param_grad_kernel", lp, st, args...);
+}
+
 }  // namespace
 
 int64_t nn64_workspace_bytes(const mpc_mlp_dynamics *net)
@@ -216,6 +311,65 @@ int launch_nn64_linearize(const mpc_mlp_dynamics *net, long N, int ns, int nc, c
     if (!pl.fits) return refuse(TOO_WIDE);
     return pl.wl ? launch<nn64_linearize_kernel<true>>("nn64_linearize_kernel", pl, st, m, N, ns, nc, x, u, F, f, pl.wave_doubles)
                  : launch<nn64_linearize_kernel<false>>("nn64_linearize_kernel", pl, st, m, N, ns, nc, x, u, F, f, pl.wave_doubles);
+}
+
+int nn64_param_grad_supported(const mpc_mlp_dynamics *net, int ns, int nc)
+{
+    Net m;
+    GradPlan pl;
+    return grad_describe(net, ns, nc, m, pl) ? 1 : 0;
+}
+
+// -1: the network is outside the kernel
+int64_t nn64_param_grad_workspace_bytes(const mpc_mlp_dynamics *net, int64_t N)
+{
+    if (!net || net->n_layers < 1 || net->n_layers > MPC_MLP_MAX_LAYERS) return -1;
+    const int ns = net->widths[net->n_layers], nc = net->widths[0] - ns;
+    Net m;
+    GradPlan pl;
+    if (!grad_describe(net, ns, nc, m, pl)) return -1;
+    return grad_workspace_bytes(pl, N < 0 ? 0 : (long)N);
+}
+
+int launch_nn64_param_grad(const mpc_mlp_dynamics *net, long N, int ns, int nc, const double *x, const double *u, const double *gF,
+                           const double *gf, const mpc_mlp_param_grads *out, void *workspace, int64_t bytes, hipStream_t st)
+{
+    // the checks, codes and order of launch_nn_param_grad (nn_dynamics.hip)
+    if (net && net->ctrl_carry) return refuse({MPC_E_DIMS, "mlp_param_grad: ctrl_carry describes a rollout only (differentiate the network itself)"});
+    if (net && net->activation == MPC_ACT_ELU) return refuse({MPC_E_DIMS, "mlp_param_grad: sigmoid and relu only (an ELU network keeps the module path)"});
+    Check c = check_net(net, ns, nc, false, nullptr, 0);
+    if (c.code) return refuse(c);
+    if (net->activation < MPC_ACT_SIGMOID || net->activation > MPC_ACT_ELU) return refuse({MPC_E_ARG, "network: unknown activation"});
+    Net m;
+    GradPlan pl;
+    if (!grad_describe(net, ns, nc, m, pl))
+        return refuse({MPC_E_DIMS, "mlp_param_grad: the network is outside the float64 kernel (see mpc_mlp_param_grad_supported_dtype)"});
+    if (bytes < grad_workspace_bytes(pl, N)) return refuse({MPC_E_DIMS, "mlp_param_grad: workspace too small (see mpc_mlp_param_grad_workspace_bytes_dtype)"});
+    if ((uintptr_t)workspace & 15) return refuse({MPC_E_ARG, "mlp_param_grad: the workspace must be 16-byte aligned"});
+    double *partials = static_cast<double *>(workspace);
+    const long blocks = grad_blocks(N);
+    if (blocks > 0) {
+        int rc;
+        const unsigned gr = (unsigned)blocks;
+#define MPC_PG64_LAUNCH(WL, K) launch_grad<WL, K>(pl, gr, st, m, pl.g, N, ns, nc, x, u, gF, gf, partials)
+        if (pl.kmax == nn64::PG64_KMAX_SMALL) rc = pl.wl ? MPC_PG64_LAUNCH(true, nn64::PG64_KMAX_SMALL) : MPC_PG64_LAUNCH(false, nn64::PG64_KMAX_SMALL);
+        else if (pl.kmax == nn64::PG64_KMAX_MID) rc = pl.wl ? MPC_PG64_LAUNCH(true, nn64::PG64_KMAX_MID) : MPC_PG64_LAUNCH(false, nn64::PG64_KMAX_MID);
+        else rc = pl.wl ? MPC_PG64_LAUNCH(true, nn64::PG64_KMAX_LARGE) : MPC_PG64_LAUNCH(false, nn64::PG64_KMAX_LARGE);
+#undef MPC_PG64_LAUNCH
+        if (rc) return rc;
+    }
+    nn64::GradFinal a = {};
+    a.L = m.L;
+    a.blocks = (int)blocks;
+    a.stride = (long)pl.kmax * nn64::PG64_THREADS;
+    a.partials = partials;
+    for (int l = 0; l <= m.L; ++l) a.w[l] = m.w[l];
+    for (int l = 0; l < m.L; ++l) {
+        a.gW[l] = (double *)out->gW[l];
+        a.gb[l] = (double *)out->gb[l];
+    }
+    hipLaunchKernelGGL(nn64_param_grad_final_kernel, dim3((unsigned)((pl.g.entries + 255) / 256)), dim3(256), 0, st, a, pl.g.entries);
+    return check_launch("nn64_param_grad_final_kernel");
 }
 
 }  // namespace mpclqr

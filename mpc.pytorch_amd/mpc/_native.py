@@ -127,6 +127,14 @@ class MlpDynamics(ctypes.Structure):          # struct mpc_mlp_dynamics
                 ("widths", _i32 * (MLP_MAX_LAYERS + 1)), ("W", _vp * MLP_MAX_LAYERS), ("b", _vp * MLP_MAX_LAYERS)]
 
 
+# mpc_mlp_param_grad_dtype(MPC_F64), csrc/nn_param_grad64.h: MPC_MLP_PARAM_GRAD64_MAX_BLOCKS blocks at most, PG64_THREADS threads a
+# block, which takes one point a pass -- one pass of the grid covers MAX_BLOCKS * BLOCK_POINTS points; the workspace is one partial
+# of KMAX * THREADS doubles a block
+MLP_PARAM_GRAD64_MAX_BLOCKS = 512
+MLP_PARAM_GRAD64_BLOCK_POINTS = 1
+MLP_PARAM_GRAD64_THREADS = 512
+
+
 class MlpParamGrads(ctypes.Structure):       # struct mpc_mlp_param_grads
     _fields_ = [("gW", _vp * MLP_MAX_LAYERS), ("gb", _vp * MLP_MAX_LAYERS)]
 
@@ -197,10 +205,13 @@ class MlpSpec:
         return MlpSpec._describe([self.weights[0].shape[1]] + [W.shape[0] for W in self.weights], ACT_CODES[self.activation],
                                  int(self.passthrough), self.ctrl_carry, pointers)
 
-    def param_grad_supported(self):
-        """Bit 2 of mpc_mlp_supported: does mpc_mlp_param_grad (the weight gradient of the linearisation) take this network?
-        The library answers that bit for a complete description only -- activation, ctrl_carry and non-NULL weights."""
+    def param_grad_supported(self, dtype=torch.float32):
+        """Does the weight gradient of the linearisation take this network in `dtype`?  float32: bit 2 of mpc_mlp_supported
+        (mpc_mlp_param_grad); float64: mpc_mlp_param_grad_supported_dtype (mpc_mlp_param_grad_dtype, csrc/nn_param_grad64.h).
+        The library answers for a complete description only -- activation, ctrl_carry and non-NULL weights."""
         e = self._complete([(W.data_ptr() or 16, b.data_ptr() or 16) for W, b in zip(self.weights, self.biases)])
+        if dtype == torch.float64:
+            return bool(int(load().mpc_mlp_param_grad_supported_dtype(ctypes.byref(e), self.n_state, self.n_ctrl, MPC_F64)))
         return bool(int(load().mpc_mlp_supported(ctypes.byref(e), self.n_state, self.n_ctrl)) & 4)
 
     @staticmethod
@@ -231,6 +242,7 @@ EXPORTS = ("mpc_lqr_abi_version", "mpc_lqr_build_info", "mpc_lqr_last_error", "m
            "mpc_env_param_grad_workspace_bytes", "mpc_env_param_grad",
            "mpc_mlp_workspace_bytes", "mpc_mlp_rollout", "mpc_mlp_linearize", "mpc_mlp_linearize_carry",
            "mpc_mlp_param_grad_workspace_bytes", "mpc_mlp_param_grad",
+           "mpc_mlp_param_grad_supported_dtype", "mpc_mlp_param_grad_workspace_bytes_dtype", "mpc_mlp_param_grad_dtype",
            "mpc_mlp_supported", "mpc_mlp_supported_dtype", "mpc_mlp_workspace_bytes_dtype", "mpc_mlp_rollout_dtype", "mpc_mlp_linearize_dtype",
            "mpc_lqr_kkt_fused_supported", "mpc_lqr_kkt_fused_workspace_bytes", "mpc_lqr_kkt_fused",
            "mpc_du_norm_reference", "mpc_slew_augment",
@@ -322,6 +334,11 @@ def load():
     L.mpc_mlp_param_grad_workspace_bytes.restype = _i64
     L.mpc_mlp_param_grad_workspace_bytes.argtypes = [MP, _i64]
     L.mpc_mlp_param_grad.argtypes = [MP, ctypes.c_int, ctypes.c_int, _i64, _vp, _vp, _vp, _vp, ctypes.POINTER(MlpParamGrads), _vp, _i64, _vp]
+    L.mpc_mlp_param_grad_supported_dtype.argtypes = [MP, ctypes.c_int, ctypes.c_int, ctypes.c_int]
+    L.mpc_mlp_param_grad_workspace_bytes_dtype.restype = _i64
+    L.mpc_mlp_param_grad_workspace_bytes_dtype.argtypes = [MP, ctypes.c_int, _i64]
+    L.mpc_mlp_param_grad_dtype.argtypes = [MP, ctypes.c_int, ctypes.c_int, ctypes.c_int, _i64, _vp, _vp, _vp, _vp, ctypes.POINTER(MlpParamGrads), _vp,
+                                           _i64, _vp]
     if L.mpc_lqr_abi_version() != ABI_VERSION:
         raise RuntimeError("libmpc_lqr_hip ABI version mismatch")
     _lib = L
@@ -1121,6 +1138,34 @@ class HipBackend:
                                     ctypes.byref(out), ws.data_ptr(), nbytes, _stream(dev)), "mpc_mlp_param_grad")
         return grads
 
+    def mlp_linearize_backward64(self, net, x, u, gF, gf):
+        """`mlp_linearize_backward` in float64: x [N,ns], u [N,nc], gF [N,ns,ns+nc], gf [N,ns] doubles on the device ->
+        [gW_1, gb_1, ..., gW_L, gb_L], float64, in nn.Linear's layouts (mpc_mlp_param_grad_dtype with MPC_F64: plain FMA, a block
+        per point, one partial per block, a second launch adds them in block order -- bitwise reproducible)."""
+        if any(t.dtype != torch.float64 for t in (x, u, gF, gf)):
+            raise TypeError("mlp_linearize_backward64 is float64 only (mpc_mlp_param_grad_dtype with MPC_F64)")
+        dev = _require_device(x, u, gF, gf)
+        L = load()
+        N, ns = x.shape
+        nc = u.shape[1]
+        x = x.detach().contiguous(); u = u.detach().contiguous()
+        gF = gF.detach().contiguous(); gf = gf.detach().contiguous()
+        assert gF.numel() == N * ns * (ns + nc) and gf.numel() == N * ns
+        e, _, _, keep_e = net.to_struct(x)
+        nbytes = int(L.mpc_mlp_param_grad_workspace_bytes_dtype(ctypes.byref(e), MPC_F64, N))
+        if nbytes < 0:
+            raise RuntimeError("mpc_mlp_param_grad_dtype does not take this network in float64 (mpc_mlp_param_grad_supported_dtype)")
+        ws = torch.empty(nbytes, device=dev, dtype=torch.uint8)
+        out, grads = MlpParamGrads(), []
+        for l, (W, b) in enumerate(zip(net.weights, net.biases)):
+            gW = torch.empty(tuple(W.shape), device=dev, dtype=torch.float64)
+            gb = torch.empty(tuple(b.shape), device=dev, dtype=torch.float64)
+            out.gW[l], out.gb[l] = gW.data_ptr(), gb.data_ptr()
+            grads += [gW, gb]
+        _check(L.mpc_mlp_param_grad_dtype(ctypes.byref(e), MPC_F64, ns, nc, N, x.data_ptr(), u.data_ptr(), gF.data_ptr(), gf.data_ptr(),
+                                          ctypes.byref(out), ws.data_ptr(), nbytes, _stream(dev)), "mpc_mlp_param_grad_dtype")
+        return grads
+
     def plan_network_iteration(self, x_init, C, c, net, opts, nominals, scratch=None, impl=IMPL_AUTO):
         """One iLQR iteration on an NNDynamics network (mpc/mpc.py:245-306 with dx a module: util.get_traj is the previous
         rollout's own new_x, then MPC.linearize_dynamics(ANALYTIC) :495-512, lqr_backward :52-160, lqr_forward through the
@@ -1311,7 +1356,8 @@ class EnvLinearizeFn(torch.autograd.Function):
 
 class MlpLinearizeFn(torch.autograd.Function):
     """(F, f) = linearisation of an NNDynamics network at N points, differentiable in the network's weights and biases:
-    forward = backend().mlp_linearize, backward = backend().mlp_linearize_backward.  `params` are the module's own
+    forward = backend().mlp_linearize, backward = backend().mlp_linearize_backward (mlp_linearize_backward64 when the saved x is
+    float64).  `params` are the module's own
     tensors in the order [W_1, b_1, ..., W_L, b_L] (the ones `net` was built from): each gradient comes back in the dtype
     and on the device of its parameter.  x and u are constants (MPC.linearize_dynamics hands in detached leaves,
     mpc/mpc.py:495-497); the backward is not itself differentiable."""
@@ -1328,7 +1374,10 @@ class MlpLinearizeFn(torch.autograd.Function):
     @torch.autograd.function.once_differentiable
     def backward(ctx, gF, gf):
         x, u = ctx.saved_tensors
-        grads = ctx.be.mlp_linearize_backward(ctx.net, x, u, gF, gf)
+        if x.dtype == torch.float64:
+            grads = ctx.be.mlp_linearize_backward64(ctx.net, x, u, gF, gf)
+        else:
+            grads = ctx.be.mlp_linearize_backward(ctx.net, x, u, gF, gf)
         assert len(grads) == len(ctx.like)
         return (None, None, None) + tuple(g.to(device=d, dtype=t).view(s) for g, (d, t, s) in zip(grads, ctx.like))
 

@@ -172,7 +172,7 @@ class MPC(Module):
                  exit_unconverged=True, detach_unconverged=True, backprop=True, slew_rate_penalty=None,
                  prev_ctrl=None, not_improved_lim=5, best_cost_eps=1e-4, reference_du_norm=False,
                  narrow_step_kernel=False, narrow_kkt_kernel=False, row_carry_kernel=False, shared_grad_kernel=False,
-                 f64_grad_kernel=False, weight_grad_kernel=False, planned_network_slew=False):
+                 f64_grad_kernel=False, f64_weight_grad_kernel=False, weight_grad_kernel=False, planned_network_slew=False):
         super().__init__()
         assert (u_lower is None) == (u_upper is None)
         assert max_linesearch_iter > 0
@@ -205,6 +205,9 @@ class MPC(Module):
         # mpc_mlp_param_grad backward) instead of the module through torch autograd.  Off by default: measured faster than the
         # module route at (12, 4, [100]) but slower at (32, 8, [100]) (docs/history/r10.md)
         self.weight_grad_kernel = bool(weight_grad_kernel)
+        # OPT-IN: the same for a float64 NNDynamics (mpc_mlp_linearize_dtype forward, mpc_mlp_param_grad_dtype backward, both MPC_F64).
+        # `weight_grad_kernel` keeps governing float32 only; off by default (docs/history/r32.md)
+        self.f64_weight_grad_kernel = bool(f64_weight_grad_kernel)
         # OPT-IN: a slew-rate penalty around an NNDynamics on the pre-bound device loop (`_iterate_slew` -> `_iterate_network` on the
         # augmented problem, mpc_mlp_linearize_carry) instead of `_iterate_general` (which networks: `solve_route`).  Off by default
         # whatever it measures: tests/test_gpu_nn.py::test_slew_rate_penalty_on_the_network_kernels and tests/test_gpu_nn_wide.py::
@@ -859,16 +862,24 @@ class MPC(Module):
     def _param_grad_net(self, dynamics, x):
         """(MlpSpec, [W_1, b_1, ...]) of `dynamics` when its differentiable linearisation (GradMethods.ANALYTIC, diff=True)
         runs as _native.MlpLinearizeFn, else None (the module path through torch): the controller was built with
-        `weight_grad_kernel=True`, an NNDynamics the kernels take as it came
-        (`native_net`: no overridden forward, no hooks, stock activations, float32 on the device), not ELU, a network
-        mpc_mlp_param_grad covers (mpc_mlp_supported bit 2), T > 1, a backend that has the backward, and the `fcs` weights and
-        biases the module's only tensors that ask for a gradient."""
+        `weight_grad_kernel=True` (a float32 network) or `f64_weight_grad_kernel=True` (a float64 one), an NNDynamics the kernels
+        take as it came (`native_net`: no overridden forward, no hooks, stock activations, on the device), not ELU, a network
+        the weight-gradient kernel of that dtype covers (mpc_mlp_supported bit 2 / mpc_mlp_param_grad_supported_dtype), T > 1, a
+        backend that has the backward of that dtype, and the `fcs` weights and biases the module's only tensors that ask for a
+        gradient."""
         be = _native.backend()
-        if (not self.weight_grad_kernel or self.T <= 1 or not isinstance(dynamics, Module) or not hasattr(dynamics, "native_net") or not hasattr(dynamics, "fcs")
-                or not hasattr(be, "mlp_linearize_backward") or x.dtype != torch.float32):
+        if x.dtype == torch.float64:
+            # a float64 network: its own flag, its own backend method and its own query (mpc_mlp_param_grad_supported_dtype)
+            on, method = self.f64_weight_grad_kernel, "mlp_linearize_backward64"
+        else:
+            on, method = self.weight_grad_kernel and x.dtype == torch.float32, "mlp_linearize_backward"
+        if (not on or self.T <= 1 or not isinstance(dynamics, Module) or not hasattr(dynamics, "native_net") or not hasattr(dynamics, "fcs")
+                or not hasattr(be, method)):
             return None
         net = dynamics.native_net(x)
-        if net is None or net.activation == "elu" or net.ctrl_carry or not net.param_grad_supported():
+        if net is None or net.activation == "elu" or net.ctrl_carry:
+            return None
+        if not (net.param_grad_supported(torch.float64) if x.dtype == torch.float64 else net.param_grad_supported()):
             return None
         params = [t for layer in dynamics.fcs for t in (layer.weight, layer.bias)]
         if len(params) != 2 * len(net.weights) or any(a is not b for a, b in zip(params[0::2], net.weights)) \
